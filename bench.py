@@ -1,15 +1,26 @@
 #!/usr/bin/env python3
 """Headline benchmark: fused TRI3+EDGE2 elastic-energy forward+backward ("element-evals/s").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the result line: the
+headline (`value`, `ms_per_step`) and the workload's `config`, nothing else.  ``--full`` adds everything measured beside
+the headline: `roofline` (kernel-only legs, cache regimes, in-run PMC traffic), `cpu_baseline` (with the oracle check of
+the loss), `config.extra` and the other legs listed below, and at N > 1 the other exchange modes (the headline then
+becomes the fastest complete evaluation + exchange step; a plain run times the serial owner-sharded step).
+``--dump-outputs DIR`` writes what the last timed step computed, as a caller of the step receives it, to DIR/<name>.npy
+(fp64): `loss` (1,), `grad_node_coords_free` and `grad_u_free` (rows in the caller's numbering; at N > 1 rank 0's
+gradient buffer and the global loss).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 N > 1: one rank per GPU over RCCL -- either launched as ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 ...`` or, given plain ``python bench.py --gpus N``, bench.py starts its N ranks itself as child processes (self_launch: the
 parent never touches the GPU and never execs).  Every host plan is built ONCE per job (rank 0 writes the plan blob to the
 job's plan cache, the other ranks deserialise it).
 A *step* is one pass of the hot path over the synthetic mesh: loss + d/d node_coords_free + d/d u_free, inputs resident
-in HBM.  The timed region is ONE hipGraph of exactly K steps, bracketed by barrier + synchronize on both sides; it is
-replayed ``--repeats`` (9) times and the MEDIAN replay is reported (max over ranks per replay).
+in HBM.  The timed region is EXACTLY K steps, timed once and bracketed by barrier + synchronize on both sides (max over
+ranks): hipGraphs of at most HEADLINE_GRAPH_STEPS steps replayed back to back (one graph of K steps up to that size).
+The legs of --full time ``--repeats`` (9) replays of a graph of min(K, HEADLINE_GRAPH_STEPS) steps each and report the
+median.
 
 Workload at N = 1: BASELINE.json configs[3] "Example 4", reading (i) of SURVEY F11 = "T1M": plate [0,2]x[0,1], 1001x501
 nodes -> 1,000,000 TRI3 (each structured quad split in two), interior nodes jittered 0.2 h (seed 0), outer boundary fixed,
@@ -28,9 +39,9 @@ kernel's stream, the K steps in one hipGraph).  Beside it, in `config`:
   strong_scaling                    BASELINE configs[3] and [4] AS STATED: 10^6 TRI3 FIXED sharded over the N ranks (and, at
                                     N = 8, the 4.1 M-element Delaunay mesh), kernel-only per rank and end to end
 At N = 1 `config.strong_scaling_emulated` rehearses those shards on the one GPU: the kernel over the tile range rank r of
-N would evaluate (`--emulate-shard r/N` runs just that).
+N would evaluate (`--emulate-shard r/N` runs just that).  All of these legs run with --full only.
 
-One JSON line on stdout (rank 0).  ``roofline`` is for the dominant kernel (tri3_energy_pair_kernel): algorithmic bytes
+One JSON line on stdout (rank 0).  With --full, ``roofline`` is for the dominant kernel (tri3_energy_pair_kernel): algorithmic bytes
 (12 Ne + 64 Nn + 8) over its average launch time, HIP events on the launch stream.  ONE regime per line:
 the top level is the regime the timed step itself runs in (`replayed`: the same buffers every launch, a 44 MB working set the
 256 MB Infinity Cache holds -- what a training loop on this mesh sees), so `roofline.kernel_us <= ms_per_step`; the regime whose
@@ -55,6 +66,8 @@ np = torch = None            # imported by main(): the self-launching parent of 
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PROFILE_DIR = os.path.join(ROOT, "profiles", "r04")      # committed rocprofv3 summaries of this round (r03 as fallback)
+HEADLINE_GRAPH_STEPS = 1000  # longest hipGraph of the headline's timed region: capture cost and graph size stay bounded for any K
+DUMP_BYTES_MAX = 60 << 20    # --dump-outputs: array bytes in all (a fixed, seeded row sample of larger outputs; < 64 MB with headers)
 
 
 def parse():
@@ -62,7 +75,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=9, help="replays of the K-step graph, each timed on its own; the median is reported")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline as well: roofline, cpu_baseline, "
+                    "config.extra and the other legs (off: the headline step only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=9, help="legs of --full: replays of the K-step graph, each timed on its own; "
+                    "the median is reported")
     ap.add_argument("--nx", type=int, default=1001, help="nodes along x PER GPU (+1 shared column)")
     ap.add_argument("--ny", type=int, default=501)
     ap.add_argument("--tile-elems", type=int, default=0)
@@ -120,6 +137,27 @@ def cpu_baseline(mesh6, u_free, n_evals):
     return dict(value=conn.shape[0] / best, unit="element-evals/s", cores=torch.get_num_threads(), kind="port",
                 sample=f"same workload ({conn.shape[0]} TRI3, fp64), best of {n_evals} fwd+bwd evaluations "
                        f"after 1 warm-up, {best:.3f} s/eval"), loss.item()
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_BYTES_MAX):
+    """--dump-outputs: each float32 / float64 array of `arrays` (name -> numpy array) to ``out_dir/<name>.npy``.  When they
+    hold more than `max_bytes` in all, every array keeps its share of the bytes as a fixed sample of its rows (numpy seed 0,
+    ascending row order): two runs with the same arguments write the same rows.  Returns {name: shape written}."""
+    import numpy
+    arrays = {k: numpy.ascontiguousarray(v) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, v in arrays.items():
+        if v.dtype not in (numpy.float32, numpy.float64):
+            raise TypeError(f"--dump-outputs: {name} is {v.dtype}, not float32 / float64")
+        if total > max_bytes and v.ndim >= 1 and v.shape[0] > 1 and v.nbytes:
+            keep = max(1, int(max_bytes * v.nbytes / total) // (v.nbytes // v.shape[0]))
+            if keep < v.shape[0]:
+                v = v[numpy.sort(numpy.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        numpy.save(os.path.join(out_dir, name + ".npy"), v)
+        written[name] = list(v.shape)
+    return written
 
 
 def pmc_traffic_in_run(kernel_substr, timeout_s=150.0):
@@ -465,6 +503,74 @@ def main():
             note(f"eager: {why}")
         return sorted(regions)[len(regions) // 2], regions, launch
 
+    def time_headline(body, n, begin=None, end=None):
+        """The headline's timed region: EXACTLY n steps, timed once, bracketed by barrier + synchronize on both sides (max
+        over ranks).  The steps run as hipGraphs of at most HEADLINE_GRAPH_STEPS steps replayed back to back (plus one graph
+        of the remainder), each bracketed by begin() / end(), so that capture cost and graph size do not grow with n.
+        Untimed before it: the clock pre-warm, the W warm-up steps, one replay of each graph.  Returns (seconds, launch)."""
+        g_len = max(1, min(n, HEADLINE_GRAPH_STEPS))
+        q, r = divmod(n, g_len)
+        g, why = capture(body, g_len, begin, end)
+        g_rem = None
+        if g is not None and r:
+            g_rem, why = capture(body, r, begin, end)
+            if g_rem is None:
+                g = None
+
+        def run(graphs_only=False):
+            if g is not None:
+                for _ in range(1 if graphs_only else q):
+                    g.replay()
+                if g_rem is not None:
+                    g_rem.replay()
+            else:
+                if begin:
+                    begin()
+                for _ in range(n):
+                    body()
+                if end:
+                    end()
+        # untimed pre-warm (the chip's clocks ramp up), bounded by --prewarm whatever n is; a fixed count when N > 1 (every
+        # rank must issue the same number of collectives)
+        if world == 1 and g is not None:
+            t_pw = time.perf_counter()
+            while time.perf_counter() - t_pw < a.prewarm:
+                g.replay()
+                torch.cuda.synchronize()
+        else:
+            for _ in range(max(1, int(a.prewarm * 400 / g_len))):
+                if g is not None:
+                    g.replay()
+                    continue
+                if begin:
+                    begin()
+                for _ in range(g_len):
+                    body()
+                if end:
+                    end()
+        if begin:
+            begin()
+        for _ in range(a.warmup + (a.warmup & 1)):      # W warm-up steps (rounded up to even, as in timed_steps)
+            body()
+        if end:
+            end()
+        if g is not None:
+            run(graphs_only=True)                       # every graph replayed once before it is timed
+        sync_all()
+        t0 = time.perf_counter()
+        run()
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        if world > 1:
+            t = torch.tensor([el], dtype=f64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            el = t.item()
+        sync_all()
+        launch = (f"hipgraph ({q} x {g_len} steps" + (f" + 1 x {r}" if r else "") + ")") if g is not None else f"eager ({why})"
+        if g is None and why != "--no-graph" and f"eager: {why}" not in notes:
+            note(f"eager: {why}")
+        return el, launch
+
     stream_box = [torch.cuda.current_stream()]
 
     def time_launches(body, kreps):
@@ -745,20 +851,34 @@ def main():
         assert abs(loss_gpu - loss_dense) <= 1e-12 * abs(loss_dense), (loss_gpu, loss_dense)
 
     only = a.only_regime
+    dumped = None
     if not only and not a.only_extra:
-        elapsed, regions, launch = timed_steps(step, a.steps, begin, end)
+        elapsed, launch = time_headline(step, a.steps, begin, end)
+        regions = [elapsed]
+        timed_region = f"{a.steps} steps timed once, after {a.warmup} warm-up steps"
         if lagged:                  # the trailing flush delivered the last step's energy: same bits as the guard evaluation
             assert sh._views(sh.send)[0].item() == loss_gpu, (sh._views(sh.send)[0].item(), loss_gpu)
+        if a.dump_outputs and rank == 0:      # what the last timed step handed its caller, rows in the caller's numbering
+            loss_v, gx_v, gu_v = sh._views(sh.send)
+            if world > 1:
+                loss_v = sh.loss_global.reshape(1)
+            dumped = dump_outputs(a.dump_outputs, dict(
+                loss=loss_v.detach().cpu().numpy(),
+                grad_node_coords_free=model.to_caller_order(gx_v, "x").detach().cpu().numpy(),
+                grad_u_free=model.to_caller_order(gu_v, "u").detach().cpu().numpy()))
     else:
-        elapsed, regions, launch = float("nan"), [], "skipped"
+        elapsed, regions, launch, timed_region = float("nan"), [], "skipped", "skipped"
     ms_per_step = elapsed / a.steps * 1e3
     value = ne / (elapsed / a.steps)          # whole-job element-evals/s (all ranks' elements)
 
     # kernel-only time of this rank's launch (the roofline's numerator), taken HERE so that a multi-rank run has it on record
     # before its first exchange leg
-    kreps = max(a.steps, 200)      # kernel-only legs: >= 200 launches per graph whatever --steps is (amortises the ~20 us graph launch)
+    # the legs of --full: K steps per timed region, capped at HEADLINE_GRAPH_STEPS (a large K would only stretch the run)
+    kl = min(a.steps, HEADLINE_GRAPH_STEPS)
+    kreps = max(kl, 200)           # kernel-only legs: >= 200 launches per graph whatever --steps is (amortises the ~20 us graph launch)
     ko_main = KernelOnly(model, loss_fn, plan, lo, hi)
-    k_us, samples = time_launches(lambda i: ko_main(), kreps) if only in ("", "replayed") and not a.only_extra else (float("nan"), [])
+    k_us, samples = (time_launches(lambda i: ko_main(), kreps) if (a.full or only) and only in ("", "replayed") and not a.only_extra
+                     else (float("nan"), []))
     if world > 1:
         _, _, ab_ = range_work(plan, lo, hi)
         prov_state.update(value=value, ms_per_step=ms_per_step,
@@ -767,22 +887,23 @@ def main():
                                       exchange_mode="serial: evaluation -> pack -> all_gather -> unpack on one stream"),
                           roofline=dict(bound="hbm", achieved=ab_ / (k_us * 1e-6) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
                                         frac=ab_ / (k_us * 1e-6) / 1e9 / HBM_PEAK_GBS, traffic=None, kernel_us=k_us,
-                                        alg_bytes_per_launch=ab_, regime="replayed; this rank's tile range of the weak-scaling mesh"))
+                                        alg_bytes_per_launch=ab_, regime="replayed; this rank's tile range of the weak-scaling mesh")
+                          if a.full else None)
     progress("headline step timed")
     # ---- N = 1, reported beside the headline: the step of a caller that needs ITS OWN loss before it goes on (a line
     #      search, an L-BFGS check): the 1-block reduction launched right after every energy launch, on the critical path
     inline_step = None
-    if world == 1 and lagged and not a.no_extra and not only and not a.only_extra:
-        el_, _, ln_ = timed_steps(sh.evaluate_local, a.steps)
+    if world == 1 and a.full and lagged and not a.no_extra and not only and not a.only_extra:
+        el_, _, ln_ = timed_steps(sh.evaluate_local, kl)
         assert sh._views(sh.send)[0].item() == loss_gpu
         inline_step = dict(mode="loss of step k reduced by its own 1-block launch before step k+1 (--inline-loss-sum)",
-                           ms_per_step=el_ / a.steps * 1e3, value=ne / (el_ / a.steps), launch=ln_)
+                           ms_per_step=el_ / kl * 1e3, value=ne / (el_ / kl), launch=ln_)
 
     # ---- N > 1: the other readings of a multi-GPU step
     def leg(body, mode, n_elems, begin_=None, end_=None):
-        el, regs, ln = timed_steps(body, a.steps, begin_, end_)
-        return dict(mode=mode, value=n_elems / (el / a.steps), ms_per_step=el / a.steps * 1e3, launch=ln,
-                    ms_per_step_replays=[round(r / a.steps * 1e3, 5) for r in regs])
+        el, regs, ln = timed_steps(body, kl, begin_, end_)
+        return dict(mode=mode, value=n_elems / (el / kl), ms_per_step=el / kl * 1e3, launch=ln,
+                    ms_per_step_replays=[round(r / kl * 1e3, 5) for r in regs])
 
     def lbfgs_leg(sh_, what, emulate=False, outer=8):
         """Example 4's optimiser (examples/example4.py:68-78: torch.optim.LBFGS defaults, 20 inner iterations per step, history
@@ -829,7 +950,7 @@ def main():
 
     alt = train = train_ov = strong = eval_ov = train_fused = train_fused_ov = lbfgs_n = None
     exchange_mode = "serial: evaluation -> pack -> all_gather -> unpack on one stream"
-    if world > 1:
+    if world > 1 and a.full:
         how = comm_state
         eval_ov = leg(sh.owner_step_overlapped, "evaluation + interface exchange, the exchange of step k on a side stream under the "
                       "interior tiles of step k+1 (fork / join inside the hipGraph: ~15 us per step on one rank, so it pays "
@@ -839,6 +960,7 @@ def main():
         if eval_ov["value"] > value:
             value, ms_per_step, launch = eval_ov["value"], eval_ov["ms_per_step"], eval_ov["launch"]
             regions = [r * a.steps * 1e-3 for r in eval_ov["ms_per_step_replays"]]
+            timed_region = f"median of {len(regions)} replays of a hipGraph of {kl} steps (config.eval_exchange_overlap)"
             exchange_mode = "overlapped: the exchange of step k under the interior tiles of step k+1 (faster than the serial step on this topology)"
         alt = leg(step_dense, f"dense: sum all-reduce of [gX|gU|loss] fp64, {sh.send.numel() * 8} B per rank, {how}", ne)
         train = leg(sh.owner_train_step, "owner-sharded training iteration: energy -> Adam on the rows the rank owns -> pack "
@@ -847,7 +969,7 @@ def main():
         train_ov = leg(sh.owner_train_step_overlapped, "the same iteration, exchange of step k on a side stream under the "
                        f"interior tiles of step k+1 (boundary tiles {sh.mid - sh.lo} of {sh.hi - sh.lo} on this rank)", ne,
                        end_=sh.finish_overlapped)
-        if a.steps % 2 == 0:          # the fused steps alternate between two parameter buffers: an even number per hipGraph
+        if kl % 2 == 0:               # the fused steps alternate between two parameter buffers: an even number per hipGraph
             train_fused = leg(sh.owner_train_step_fused, "owner-sharded training iteration with Adam applied by the energy kernel's "
                               "write-out (hfem_tri3_energy_adam_step_ex on the rank's tile range): energy+Adam -> pack -> all_gather "
                               "-> unpack, three launches + the collective, no gradient traffic", ne)
@@ -856,7 +978,7 @@ def main():
         else:
             note("fused training legs skipped: --steps must be even (ping-pong parameter buffers inside one hipGraph)")
 
-    if world > 1:
+    if world > 1 and a.full:
         prov_state.update(value=value, ms_per_step=ms_per_step)
         prov_state["config"].update(exchange_mode=exchange_mode, launch=launch)
         progress("collective-path legs")
@@ -888,9 +1010,9 @@ def main():
             raise RuntimeError(f"{tag}: peer-window exchange disagrees with the collective path on some rank "
                                f"(this rank: status {st}, energy {l_got!r} vs {l_ref!r})")
 
-    if world > 1 and not a.no_peer and over_budget(0.6, "peer-window legs"):
+    if world > 1 and a.full and not a.no_peer and over_budget(0.6, "peer-window legs"):
         a.no_peer = True
-    if world > 1 and not a.no_peer:
+    if world > 1 and a.full and not a.no_peer:
         try:
             enable_peer(sh, "T1M x N")
             peer_on[0] = True
@@ -903,7 +1025,7 @@ def main():
                 train_step=leg(sh.owner_train_step, "Adam iteration: energy -> Adam on owned rows -> put -> get", ne),
                 train_step_overlap=leg(sh.owner_train_step_overlapped, "Adam iteration, the get of step k after the interior tiles of "
                                        "step k+1", ne, end_=sh.finish_overlapped))
-            if a.steps % 2 == 0:
+            if kl % 2 == 0:
                 peer_legs["train_step_fused"] = leg(sh.owner_train_step_fused, "Adam inside the energy launch -> put -> get", ne)
                 peer_legs["train_step_fused_overlap"] = leg(sh.owner_train_step_fused_overlapped, "Adam inside the two energy launches, "
                                                             "the get after the next step's interior tiles", ne, end_=sh.finish_overlapped)
@@ -920,6 +1042,7 @@ def main():
             if peer_legs[best]["value"] > value:
                 value, ms_per_step, launch = peer_legs[best]["value"], peer_legs[best]["ms_per_step"], peer_legs[best]["launch"]
                 regions = [r * a.steps * 1e-3 for r in peer_legs[best]["ms_per_step_replays"]]
+                timed_region = f"median of {len(regions)} replays of a hipGraph of {kl} steps (config.peer_exchange.{best})"
                 exchange_mode = ("peer windows" + (", the get under the next step's interior tiles" if best.endswith("overlap") else "")
                                  + ": interface rows stored by the pack launch into every rank's window over xGMI (faster than the "
                                  "all_gather steps on this topology; config.peer_exchange)")
@@ -930,14 +1053,14 @@ def main():
             sh.close_peer_exchange(check=False)
         peer_on[0] = False
 
-    if world > 1 and not a.no_peer:
+    if world > 1 and a.full and not a.no_peer:
         prov_state.update(value=value, ms_per_step=ms_per_step)
         prov_state["config"].update(exchange_mode=exchange_mode, launch=launch, peer_exchange=peer_state)
         progress("peer-window legs")
     # ---- N > 1: Example 4's own optimiser, node-sharded (weak: N x 10^6 elements, every rank keeps 2 x 10^6 parameters' history)
-    if world > 1 and not a.no_lbfgs and over_budget(0.6, "sharded L-BFGS legs"):
+    if world > 1 and a.full and not a.no_lbfgs and over_budget(0.6, "sharded L-BFGS legs"):
         a.no_lbfgs = True
-    if world > 1 and not a.no_lbfgs:
+    if world > 1 and a.full and not a.no_lbfgs:
         try:
             was_peer = sh.peer is not None
             if was_peer:
@@ -946,7 +1069,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             note(f"lbfgs_step leg failed: {type(e).__name__}: {str(e)[:160]}")
 
-    if world > 1 and not a.no_lbfgs:
+    if world > 1 and a.full and not a.no_lbfgs:
         progress("sharded L-BFGS leg (weak)")
     # ---- N > 1: BASELINE configs[3] / [4] as stated -- a FIXED mesh sharded over the N ranks (strong scaling)
     def strong_leg(name, mesh6_s):
@@ -957,7 +1080,7 @@ def main():
         sh_s.init_owner_adam(lr_x=1e-9, lr_u=1e-12, fused=True)
         ne_s, nn_s = mesh6_s[1].shape[0], mesh6_s[0].shape[0]
         ko = KernelOnly(m_s, lf_s, sh_s.plan, sh_s.lo, sh_s.hi)
-        us, _ = time_launches(lambda i: ko(), max(a.steps, 200))
+        us, _ = time_launches(lambda i: ko(), kreps)
         ne_r, nn_r, ab = range_work(sh_s.plan, sh_s.lo, sh_s.hi)
         t = torch.tensor([us, float(ab) / (us * 1e-6) / 1e9], dtype=f64, device=dev)
         tmax, tsum = t.clone(), t.clone()
@@ -977,7 +1100,7 @@ def main():
                    train_step=leg(sh_s.owner_train_step, "Adam iteration, exchange on the critical path", ne_s),
                    train_step_overlap=leg(sh_s.owner_train_step_overlapped, "Adam iteration, exchange under the next step's interior tiles",
                                           ne_s, end_=sh_s.finish_overlapped))
-        if a.steps % 2 == 0:
+        if kl % 2 == 0:
             res["train_step_fused"] = leg(sh_s.owner_train_step_fused, "Adam inside the energy launch, exchange on the critical path", ne_s)
             res["train_step_fused_overlap"] = leg(sh_s.owner_train_step_fused_overlapped, "Adam inside the energy launches, exchange "
                                                   "under the next step's interior tiles", ne_s, end_=sh_s.finish_overlapped)
@@ -992,7 +1115,7 @@ def main():
                     train_step=leg(sh_s.owner_train_step, "energy -> Adam -> put -> get", ne_s),
                     train_step_overlap=leg(sh_s.owner_train_step_overlapped, "the get after the next step's interior tiles", ne_s,
                                            end_=sh_s.finish_overlapped))
-                if a.steps % 2 == 0:
+                if kl % 2 == 0:
                     res["peer_exchange"]["train_step_fused"] = leg(sh_s.owner_train_step_fused, "energy+Adam -> put -> get", ne_s)
                     res["peer_exchange"]["train_step_fused_overlap"] = leg(sh_s.owner_train_step_fused_overlapped,
                                                                            "the get after the next step's interior tiles", ne_s,
@@ -1010,9 +1133,9 @@ def main():
         del sh_s, m_s, ko
         return res
 
-    if world > 1 and not a.no_strong and over_budget(0.7, "strong_scaling legs"):
+    if world > 1 and a.full and not a.no_strong and over_budget(0.7, "strong_scaling legs"):
         a.no_strong = True
-    if world > 1 and not a.no_strong:
+    if world > 1 and a.full and not a.no_strong:
         strong = [strong_leg("T1M FIXED (BASELINE configs[3] as stated): 10^6 TRI3 sharded over the ranks", t1m_mesh(1))]
         spent = torch.tensor([time.perf_counter() - t_start], dtype=f64, device=dev)
         dist.all_reduce(spent, op=dist.ReduceOp.MAX)          # one decision for all ranks (the legs contain collectives)
@@ -1023,7 +1146,7 @@ def main():
             strong.append(strong_leg("cfg5u FIXED (BASELINE configs[4]): ~4.1 x 10^6 TRI3 Delaunay mesh sharded over the ranks",
                                      unstructured_tri_mesh(2_050_000, seed=2, dtype=f64)))
 
-    if world > 1 and not a.no_strong:
+    if world > 1 and a.full and not a.no_strong:
         progress("strong-scaling legs")
     # ------------------------------------------------------------------------------------------------ roofline legs
     # (ko_main, k_us, samples: timed right after the headline step)
@@ -1035,7 +1158,7 @@ def main():
     #  rotating_sets:    R parameter / gradient sets (R x 32 MB > the 256 MB Infinity Cache) visited round-robin: every read of
     #                    x, u and every gradient line misses the Infinity Cache (plan arrays stay shared) -- the HBM regime
     regimes = {}
-    if world == 1 and not a.no_regimes and not a.only_extra:
+    if world == 1 and (a.full or only) and not a.no_regimes and not a.only_extra:
         xf, uf = ko_main.xf, ko_main.uf
 
         def rewrite(i):
@@ -1061,9 +1184,9 @@ def main():
                                             working_set_mb=round(R * 4 * xf.numel() * 8 / 2 ** 20 + plan.stats["device_bytes"] / 2 ** 20, 1))
             if not only and lagged:      # the WHOLE timed step (same K, same lagged loss sum, same bracketing) in this regime
                 rs = RotatingStep(ko_main, sets)
-                el_, regs_, ln_ = timed_steps(rs, a.steps, rs.begin, rs.end)
-                regimes["rotating_sets"]["step"] = dict(ms_per_step=el_ / a.steps * 1e3, value=ne / (el_ / a.steps), launch=ln_,
-                                                        ms_per_step_replays=[round(r_ / a.steps * 1e3, 6) for r_ in regs_])
+                el_, regs_, ln_ = timed_steps(rs, kl, rs.begin, rs.end)
+                regimes["rotating_sets"]["step"] = dict(ms_per_step=el_ / kl * 1e3, value=ne / (el_ / kl), launch=ln_,
+                                                        ms_per_step_replays=[round(r_ / kl * 1e3, 6) for r_ in regs_])
             # for information: the same leg on a plan created with "store_policy" = 2 (nt gradient stores) -- what plans of
             # >= 750 k nodes take by default and what a caller whose T1M-sized buffers are NOT cache-resident should set
             try:
@@ -1140,7 +1263,7 @@ def main():
     # MI355X_MICROARCH.md; gfx950: FETCH_SIZE x 2); else the committed passes of the same shape, labelled as such
     traffic_kind = ("committed: FETCH_SIZE x2 + WRITE_SIZE of the rocprofv3 --pmc passes under profiles/ (same workload shape), "
                     "not measured in this run") if traffic is not None else None
-    if world == 1 and not a.no_pmc and not a.no_regimes:
+    if world == 1 and a.full and not a.no_pmc and not a.no_regimes:
         got, why = pmc_traffic_in_run(kname)
         if got is not None:
             traffic, traffic_kind = got["traffic_bytes_per_launch"], (
@@ -1176,8 +1299,10 @@ def main():
                         regime="replayed: the same buffers every launch (cache-resident working set)" + ("" if world == 1 else
                                "; this rank's tile range of the weak-scaling mesh"),
                         alg_bytes_per_launch=alg_bytes, elems_per_launch=ne_launch, nodes_per_launch=nn_launch)
+    if not a.full:
+        roofline = None                 # its kernel-only legs run with --full only
 
-    if world == 1:
+    if world == 1 and a.full:
         progress("roofline legs (regimes, in-run PMC traffic)")
     # ---- config.extra (N = 1): the other readings of "1 M quad elements" and BASELINE config 5, kernel only, each with
     #      its own roofline figures (algorithmic bytes of ITS element type over ITS kernel's average launch time) in the HBM
@@ -1189,7 +1314,7 @@ def main():
     #        cfg5r    the same after mesh.reorder_for_locality (explicit renumbering by the caller)
     #        cfg5u    4.1 x 10^6 TRI3, genuinely unstructured: Delaunay of graded random points, plate with three holes
     extras = []
-    if world == 1 and (not a.no_extra or a.only_extra):
+    if world == 1 and ((a.full and not a.no_extra) or a.only_extra):
         from hidenn_fem_amd.mesh import reorder_for_locality, structured_quad_mesh, unstructured_tri_mesh
 
         def extra(key, name, mesh, quad=False, model_kw=None):
@@ -1262,13 +1387,13 @@ def main():
             print(json.dumps(dict(only_extra=a.only_extra, extras=extras)), flush=True)
         return None
 
-    if world == 1:
+    if world == 1 and a.full:
         progress("config.extra workloads")
     # ---- config.fp32_rows (N = 1): T1M as the reference would run it by default -- an fp32 model (src/loss.py:16,
     #      src/models.py:274): float rows widened on load, gradients rounded once on store, fp64 arithmetic and loss; kernel
     #      only, its own algorithmic bytes (12 Ne + 32 Nn + 8)
     fp32_leg = None
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         try:
             m32 = PiecewiseLinearShapeNN2D(coords.float(), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                            neumann_edges=edges, reorder=a.reorder).to(dev)
@@ -1325,7 +1450,7 @@ def main():
     #      sharded N ways by a plan prepared for N ranks (shard-aware tile policy), kernel only over the tile range of the
     #      first, a middle and the last rank; the max is what a strong-scaling step waits for
     strong_emu = None
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         strong_emu = []
         for n_ in (2, 4, 8):
             r_ = shard_kernel_leg(model, loss_fn, n_, sorted({0, n_ // 2, n_ - 1}), kreps)
@@ -1338,12 +1463,12 @@ def main():
     #      (the reference's `loss.backward(); optimizer.step()`), (ii) one launch: the tiles apply Adam to the rows they own
     #      (hfem_tri3_energy_adam_step).  K iterations in one hipGraph each; lr tiny so the mesh stays valid.
     train1 = None
-    if world == 1 and not a.no_extra:
+    if world == 1 and a.full and not a.no_extra:
         try:
             from hidenn_fem_amd.optim import FusedAdam, EnergyAdamStep
             from hidenn_fem_amd.graphed import GraphedTraining
             res = {}
-            K = max(2, (a.steps // 2) * 2)
+            K = max(2, (kl // 2) * 2)
             for mode in ("two_launch", "one_launch"):
                 m_ = build_model(mesh6)
                 lf_ = EnergyLoss2D(E=10e9, nu=0.3, gauss_order=4, device=dev, dtype=f64, tile_elems=a.tile_elems)
@@ -1376,13 +1501,13 @@ def main():
         except Exception as e:  # noqa: BLE001
             note(f"train_step_1gpu leg failed: {type(e).__name__}: {str(e)[:160]}")
 
-    if world == 1:
+    if world == 1 and a.full:
         progress("fp32 rows, training-step legs")
     # ---- N = 1: Example 4's optimiser at full size -- LBFGS as the reference drives it (examples/example4.py:68-78: lr 1, max_iter 20,
     #      history 100, no line search) on T1M.  With the history full an inner iteration streams the 2 x 100 history vectors twice
     #      (multidot + direction passes, csrc/lbfgs.hip): 4 h n 8 B = 6.4 GB -- the optimiser, not the 9 us energy launch, is the iteration.
     lbfgs1 = None
-    if world == 1 and not a.no_extra and not a.no_lbfgs and not only and not a.only_extra:
+    if world == 1 and a.full and not a.no_extra and not a.no_lbfgs and not only and not a.only_extra:
         try:
             from hidenn_fem_amd.optim import FusedLBFGS
 
@@ -1417,7 +1542,7 @@ def main():
     #      rank r of 8 -- its tile range's energy launch, its 1/8 of the history (emulate=True: no peers; the payload gather is a
     #      local copy) -- ms per inner iteration against lbfgs_step_1gpu (the whole optimiser on one GPU)
     lbfgs_emu = None
-    if world == 1 and not a.no_extra and not a.no_lbfgs and not only and not a.only_extra:
+    if world == 1 and a.full and not a.no_extra and not a.no_lbfgs and not only and not a.only_extra:
         try:
             lbfgs_emu = []
             for r_ in (0, 4, 7):
@@ -1433,13 +1558,13 @@ def main():
         except Exception as e:  # noqa: BLE001
             note(f"lbfgs_sharded_emulated leg failed: {type(e).__name__}: {str(e)[:160]}")
 
-    if world == 1:
+    if world == 1 and a.full:
         progress("L-BFGS legs")
     # ---- N = 1: what the owner-sharded step machinery costs on ONE rank (no peer to talk to: every microsecond above the
     #      plain iteration is overhead of the exchange path) -- all_gather stand-in on one stream, the side-stream overlap,
     #      and the peer-window put / get; plain and fused (Adam inside the energy launch); K iterations per hipGraph.
     shard1 = None
-    if world == 1 and not a.no_extra and not a.no_peer and not only and not a.only_extra:
+    if world == 1 and a.full and not a.no_extra and not a.no_peer and not only and not a.only_extra:
         try:
             m_ = build_model(mesh6)
             lf_ = EnergyLoss2D(E=10e9, nu=0.3, gauss_order=4, device=dev, dtype=f64, tile_elems=a.tile_elems)
@@ -1448,7 +1573,7 @@ def main():
             sh_.init_owner_adam(lr_x=1e-9, lr_u=1e-12, fused=True)
             n_t = sh_.hi - sh_.lo
             sh_.mid = sh_.lo + max(1, n_t // 20)            # 5 % of the tiles play the boundary part, as on a real shard
-            K1 = max(2, (max(a.steps, 100) // 2) * 2)
+            K1 = max(2, (max(kl, 100) // 2) * 2)
 
             def us(body, end_=None):
                 el, _, ln = timed_steps(body, K1, None, end_)
@@ -1471,12 +1596,12 @@ def main():
         except Exception as e:  # noqa: BLE001
             note(f"sharded_step_1gpu leg failed: {type(e).__name__}: {str(e)[:160]}")
 
-    if world == 1:
+    if world == 1 and a.full:
         progress("owner-sharded steps on one rank")
     out = None
     if rank == 0:
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cpu, loss_cpu = cpu_baseline(mesh6, model.to_caller_order(model.u_free.detach(), "u").cpu(), a.cpu_evals)
             rel = abs(loss_cpu - loss_gpu) / abs(loss_cpu)
             assert rel <= 1e-12, f"GPU loss {loss_gpu!r} != oracle loss {loss_cpu!r} (rel {rel:.2e})"
@@ -1496,17 +1621,19 @@ def main():
                         threads_per_tile=st["threads_per_tile"],
                         halo_elem_factor=sum(len(plan.tile_elements(t)[0]) for t in range(st["n_tiles"])) / max(ne, 1),
                         lds_bytes=st["lds_bytes"], launch=launch,
-                        timed_region=f"one hipGraph of {a.steps} steps; median of {len(regions)} replays",
-                        ms_per_step_replays=[round(r / a.steps * 1e3, 6) for r in regions],
+                        timed_region=timed_region, ms_per_step_replays=[round(r / a.steps * 1e3, 6) for r in regions],
                         loss_sum=("by an extra workgroup of the next launch (HFEM_FLAG_SUM_PREVIOUS) + one trailing "
                                   "1-block launch" if lagged else "1-block launch after every energy kernel"),
                         exchange="none" if world == 1 else
                         f"owner-sharded: gradient rows stay with the rank whose tiles own the node; one all_gather per "
                         f"step of interface parameter rows + partial energy ({sh.interface_stats['payload_bytes']} B "
                         f"per rank), {comm_state}",
-                        loss=loss_gpu),
-            roofline=roofline,
+                        loss=loss_gpu, full=a.full),
         )
+        if roofline is not None:
+            out["roofline"] = roofline
+        if dumped is not None:
+            out["config"]["dumped_outputs"] = dict(dir=a.dump_outputs, shapes=dumped)
         if world > 1:
             out["config"]["collectives"] = comm_state
             out["config"]["plan_cache"] = plan_cache_state

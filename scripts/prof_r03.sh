@@ -20,7 +20,7 @@ if [ "$PART" = regimes ] || [ "$PART" = all ]; then
     echo "regime $r done"
   done
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o p -- \
-      python3 $B --no-cpu-baseline --no-regimes --no-extra > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench.log"
+      python3 $B --full --no-cpu-baseline --no-regimes --no-extra > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench.log"
   cp "$OUT/bench/p_kernel_stats.csv" "$OUT/kernel_stats_bench_py.csv"; rm -rf "$OUT/bench"
   echo "bench under rocprof done"
 fi
