@@ -11,11 +11,17 @@ from src.mesh import generate_mesh
 from src.models import PiecewiseLinearShapeNN2D
 
 
-def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False):
+def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
-    the history and direction of the rows its tiles own; two small exchanges per inner iteration)."""
+    the history and direction of the rows its tiles own; two small exchanges per inner iteration).
+    ``solve_first=True``: before the loop, ``u_free`` is set to the displacement that minimises the energy on the initial mesh
+    (``hidenn_fem_amd.solve.solve_displacement_``: preconditioned CG at frozen coordinates) and that energy is printed -- the
+    fixed-mesh FEM reference an r-adapted energy is compared against.  The L-BFGS loop then starts from it; with the reference's
+    fixed step (lr 1, no line search) on coordinates and displacements together it does not stay there: at that point the
+    gradient is all coordinate gradient, and the coordinate steps invert elements (the energy turns NaN on this plate; the
+    reference's own op chain does the same on a smaller plate on the CPU)."""
     import os
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -36,6 +42,16 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype)
+    if solve_first:
+        import time
+        from hidenn_fem_amd.solve import solve_displacement_
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = solve_displacement_(model, loss_fn, rtol=1e-10)
+        torch.cuda.synchronize()
+        if rank0:
+            print(f"frozen-mesh solve: {info.iterations} CG iterations, |r|/|f| = {info.residual_norm / max(info.rhs_norm, 1e-300):.2e} "
+                  f"({info.reason}), {time.perf_counter() - t0:.3f} s, energy {loss_fn(model).item():.6e}")
     if sharded:
         import time
         from hidenn_fem_amd.optim import ShardedLBFGS
@@ -92,5 +108,7 @@ if __name__ == "__main__":
     ap.add_argument("--fp64", action="store_true")
     ap.add_argument("--fused-lbfgs", action="store_true")
     ap.add_argument("--sharded", action="store_true", help="owner-sharded energy + node-sharded L-BFGS (one process per GPU)")
+    ap.add_argument("--solve-first", action="store_true", help="start L-BFGS from the frozen-mesh displacement solve (CG)")
     a = ap.parse_args()
-    run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded)
+    run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
+        solve_first=a.solve_first)

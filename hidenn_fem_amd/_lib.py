@@ -140,6 +140,13 @@ PROTOTYPES = {
     "hfem_rectq4_eval_fwd": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "hfem_rectq4_eval_bwd": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_rectq4_mse": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "hfem_cg_create": (C.c_int, [_vp, _i64, _i32, C.POINTER(_vp)]),
+    "hfem_cg_destroy": (C.c_int, [_vp]),
+    "hfem_cg_setup": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp]),
+    "hfem_cg_start": (C.c_int, [_vp, _vp, _vp, _f64, _f64, _i64, _vp]),
+    "hfem_cg_iterate": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "hfem_cg_status": (C.c_int, [_vp, _vp, _vp]),
+    "hfem_cg_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured entry points (same argument lists; every array pointer is float* except the

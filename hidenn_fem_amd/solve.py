@@ -1,0 +1,242 @@
+"""Frozen-mesh displacement solve: the ``u_free`` that minimises the energy at the model's CURRENT coordinates.
+
+With the nodal coordinates held fixed the HiDeNN-FEM energy is classical P1 finite elements and exactly quadratic in the
+displacements, ``E(u) = 1/2 u^T K u - f^T u`` (K symmetric positive definite on the free rows once Dirichlet rows exist), so
+its minimum is the linear system ``K_ff u = f - K_fd u_d``.  ``FrozenMeshSolver`` solves it by matrix-free preconditioned
+conjugate gradients on the GPU (``csrc/tri3_cg.hip``): ``K p`` is the displacement half of the tuned energy kernel at
+``u = p`` with no forces, the residual ``r = -dE/du`` comes from the graded energy kernel itself (so every force table of
+``EnergyLoss2D`` -- default traction, a traction or body-force callable, nonzero ``u_fixed`` -- enters with no extra code),
+and each iteration is two launches whose scalars (alpha, beta, the stopping test) are reduced on the device.  Iterations run
+``iters_per_graph`` at a time as one replayed graph; the host reads one status record per replay.
+
+This is the exact "Step 1" of the alternating scheme of the reference's example 4 (frozen coordinates, optimise ``u_free``),
+the fixed-mesh FEM solution to compare an r-adapted energy against, and a warm start for L-BFGS.  Not deterministic: the LDS
+atomics of the matrix-vector product make iterates differ in the last bits from run to run (the scalars are reduced in a
+fixed order; the deterministic energy path has no solver counterpart).  TRI3 models only; the kernels run on a paired-slot
+tile plan (the model's own, or one built for the solver when the planner chose one element per slot for this mesh).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream_ptr
+
+F64 = torch.float64
+HFEM_FLAG_NO_GX = 1
+HFEM_FLAG_NO_EDGES = 4
+HFEM_FLAG_PHYSICAL_GRAD = 64
+_REASONS = {1: "rtol", 2: "atol", 3: "max_iter", 4: "breakdown"}
+
+
+@dataclass
+class SolveInfo:
+    """Outcome of ``FrozenMeshSolver.solve()``.  ``residual_norm``: ||r||_2 over the free u rows of the CG recursion
+    (r is updated, not recomputed); ``rhs_norm``: ||f||_2 = ||dE/du|| at ``u_free = 0`` (it includes the ``u_fixed`` term);
+    ``reason``: ``"rtol"``, ``"atol"`` (whichever tolerance was the larger one when ||r|| <= max(rtol ||f||, atol)),
+    ``"max_iter"`` or ``"breakdown"`` (p^T K p <= 0 or a non-finite scalar: ``u_free`` keeps the last good iterate)."""
+    iterations: int
+    residual_norm: float
+    rhs_norm: float
+    converged: bool
+    reason: str
+
+
+class FrozenMeshSolver:
+    """Preconditioned CG for ``model.u_free`` at frozen coordinates (see the module docstring).
+
+    ``b_force`` / ``t_force``: the callables ``loss_fn(model, b_force, t_force)`` would take (default forces when None);
+    ``precond``: ``"block_jacobi"`` (2x2 diagonal blocks of K) or ``"none"``; stopping test
+    ``||r||_2 <= max(rtol ||f||_2, atol)``; ``max_iter`` None = ``max(1000, 2 x free dofs)``; ``iters_per_graph``: CG
+    iterations per graph replay (iterations behind the one that stopped do nothing on the device).
+
+    ``solve()`` starts from the current ``model.u_free`` (a warm start works), writes the result into it in place and
+    returns a ``SolveInfo``.  Nothing else of the model changes: coordinates, ``.grad`` of both parameters, Dirichlet rows.
+    ``refresh()`` rebuilds the right-hand side inputs and the preconditioner; ``solve()`` calls it by itself when the
+    coordinate rows, ``u_fixed`` or the force inputs changed since the last one (tensor ``_version``).  fp32 models solve
+    in fp64 (coordinates widened once per refresh, ``u_free`` rounded once on write-back).  The gradient convention
+    follows ``loss_fn`` / ``model`` as the energy does; works in the model's storage row order (``reorder`` any)."""
+
+    def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None,
+                 precond: str = "block_jacobi", rtol: float = 1e-10, atol: float = 0.0, max_iter: Optional[int] = None,
+                 iters_per_graph: int = 16):
+        if getattr(model, "nodes_per_element", 3) != 3:
+            raise NotImplementedError("FrozenMeshSolver: TRI3 models only (QUAD4 has no CG kernels)")
+        if getattr(loss_fn, "deterministic", False):
+            raise NotImplementedError("FrozenMeshSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
+                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+        if precond not in ("block_jacobi", "none"):
+            raise ValueError("precond must be 'block_jacobi' or 'none'")
+        if int(iters_per_graph) < 1:
+            raise ValueError("iters_per_graph must be >= 1")
+        if rtol < 0 or atol < 0:
+            raise ValueError("rtol and atol must be >= 0")
+        for name, t in (("node_coords_free", model.node_coords_free), ("u_free", model.u_free)):
+            _lib.require_gpu_tensor(t, name, dtype=None)
+        self.model, self.loss_fn = model, loss_fn
+        self.b_force, self.t_force = b_force, t_force
+        self.precond, self.rtol, self.atol = precond, float(rtol), float(atol)
+        self.iters_per_graph = int(iters_per_graph)
+        self.phys = bool(loss_fn._mode_flags(model) & HFEM_FLAG_PHYSICAL_GRAD)
+        self.plan = _paired_plan(model, loss_fn.tile_elems)
+        if not self.plan.stats["paired"]:
+            raise NotImplementedError("FrozenMeshSolver: the CG kernels need a paired-slot tile plan (plan_elem_order 5)")
+        dev = model.u_free.device
+        self.device = dev
+        self.n_u = int(model.u_free.shape[0])
+        self.max_iter = max(1000, 4 * self.n_u) if max_iter is None else int(max_iter)
+        h = C.c_void_p()
+        check(_lib.lib().hfem_cg_create(self.plan.handle, self.n_u, HFEM_FLAG_PHYSICAL_GRAD if self.phys else 0, C.byref(h)),
+              "hfem_cg_create")
+        self._h = h
+        # solver-owned fp64 working set (the captured graph only ever sees these addresses)
+        z = dict(dtype=F64, device=dev)
+        self._xf = torch.empty(model.node_coords_free.shape, **z)
+        self._xfix = torch.empty(model.node_coords_fixed.shape, **z)
+        self._ufix = torch.empty((int(model._idx_udir.shape[0]), 2), **z)
+        self._u = torch.zeros((self.n_u, 2), **z)
+        self._zero = torch.zeros((self.n_u, 2), **z)
+        self._g0 = torch.empty((self.n_u, 2), **z)
+        self._gz = torch.empty((self.n_u, 2), **z)
+        self._loss = torch.empty((), **z)
+        self.diag = torch.empty((self.n_u, 3), **z)        # the 2x2 diagonal blocks {K_xx, K_xy, K_yy} of the last refresh
+        self._status = (C.c_double * 16)()
+        self._graph = None
+        self._key = None
+        self._tables = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib().hfem_cg_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    # ---- what the right-hand side and K depend on
+    def _state_key(self):
+        m = self.model
+        ts = [m.node_coords_free, m.node_coords_fixed, m.u_fixed]
+        return tuple((None if t is None else (t.data_ptr(), t._version, tuple(t.shape), t.dtype)) for t in ts)
+
+    def refresh(self):
+        """Coordinates, ``u_fixed`` or the forces changed: re-widen the coordinate rows, re-tabulate the forces and rebuild
+        the preconditioner (one setup launch)."""
+        m, lf = self.model, self.loss_fn
+        dev = self.device
+        with torch.no_grad():
+            self._xf.copy_(m.node_coords_free.detach())
+            self._xfix.copy_(m.node_coords_fixed.detach())
+            self._ufix.copy_(m.u_fixed_rows().detach())
+        mat = (C.c_double * 4)(*lf._mat)
+        check(_lib.lib().hfem_cg_setup(self._h, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, mat,
+                                       float(lf._W), 1 if self.precond == "block_jacobi" else 0, ptr(self.diag),
+                                       stream_ptr(dev)), "hfem_cg_setup")
+        # force tables exactly as EnergyLoss2D builds them (the coordinates are frozen: a position-dependent traction is a
+        # constant table here)
+        bk = lf._body_table(self.b_force)
+        flags = HFEM_FLAG_NO_GX | (HFEM_FLAG_PHYSICAL_GRAD if self.phys else 0)
+        if m.neumann_edges is None or m.N_edges == 0:
+            te, tc, flags = None, [0.0] * 4, flags | HFEM_FLAG_NO_EDGES
+        else:
+            te, tc = lf._traction(_Frozen(m, self._xf, self._xfix), self.t_force)
+            te = None if te is None else te.to(device=dev, dtype=F64).contiguous()
+        self._tables = (mat, (C.c_double * 6)(*bk), te, None if tc is None else (C.c_double * 4)(*tc), flags)
+        self._key = self._state_key()
+
+    def _gradient(self, u, out):
+        """out = dE/du_free at u (fp64 rows), one launch of the graded energy kernel."""
+        mat, bk, te, tc, flags = self._tables
+        check(_lib.lib().hfem_tri3_energy_plan(
+            self.plan.handle, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
+            ptr(self._ufix) if self._ufix.numel() else None, mat, float(self.loss_fn._W), bk, ptr(te), tc, 0, -1,
+            ptr(self._loss), None, ptr(out), flags, stream_ptr(self.device)), "hfem_tri3_energy_plan")
+
+    def _read_status(self):
+        check(_lib.lib().hfem_cg_status(self._h, self._status, stream_ptr(self.device)), "hfem_cg_status")
+        return list(self._status)
+
+    def solve(self) -> SolveInfo:
+        m = self.model
+        if self._key is None or self._key != self._state_key():
+            self.refresh()
+        dev = self.device
+        L = _lib.lib()
+        with torch.no_grad():
+            self._u.copy_(m.u_free.detach())
+            self._gradient(self._u, self._g0)
+            self._gradient(self._zero, self._gz)
+            check(L.hfem_cg_start(self._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol, self.max_iter, stream_ptr(dev)),
+                  "hfem_cg_start")
+            st = self._read_status()
+            while not st[10] and st[0] < self.max_iter:
+                self._replay()
+                st = self._read_status()
+            m.u_free.copy_(self._u)                          # rounds once for fp32 models
+        reason = _REASONS.get(int(st[4]), "max_iter")
+        return SolveInfo(iterations=int(st[0]), residual_norm=float(st[1]), rhs_norm=float(st[2]),
+                         converged=reason in ("rtol", "atol"), reason=reason)
+
+    def _replay(self):
+        dev = self.device
+        if self._graph is None:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):                        # captured, not executed
+                check(_lib.lib().hfem_cg_iterate(self._h, ptr(self._u), self.iters_per_graph, stream_ptr(dev)),
+                      "hfem_cg_iterate")
+            self._graph = g
+        self._graph.replay()
+
+    def apply(self, p: torch.Tensor):
+        """Standalone ``q = K p`` over the free u rows (fixed rows read as 0) and ``p^T q`` (0-d device tensor); ``p`` is fp64
+        ``[n_u, 2]`` in storage order.  For tests and measurements."""
+        if self._key is None or self._key != self._state_key():
+            self.refresh()
+        p = _lib.require_gpu_tensor(p.detach(), "p", F64)
+        q = torch.empty_like(p)
+        pq = torch.empty((), dtype=F64, device=self.device)
+        check(_lib.lib().hfem_cg_apply(self._h, ptr(p), ptr(q), ptr(pq), stream_ptr(self.device)), "hfem_cg_apply")
+        return q, pq
+
+
+def _paired_plan(model, tile_elems):
+    """The model's tile plan when it has paired slots, else a paired plan of the same mesh and row maps (cached on the model
+    beside its own plans).  The planner's auto policy gives meshes with few fan-adjacent partners -- zigzag splits such as
+    example 4's plate, Delaunay meshes -- the one-element-per-slot order; the CG kernels exist for paired plans only, where an
+    element without a partner is simply a slot with one element."""
+    from .plan import TilePlan
+    plan = model.tile_plan(tile_elems)
+    if plan.stats["paired"]:
+        return plan
+    key = (str(model.device), int(tile_elems), "paired")
+    if key not in model._plans:
+        model._plans[key] = TilePlan(model.connectivity, model.Nnodes, coords_hint=model.initial_node_coords,
+                                     x_src=model._x_src, u_src=model._u_src, edges=model.neumann_edges, tile_elems=tile_elems,
+                                     device=model.device, elem_order=5, nodes_per_elem=3)
+    return model._plans[key]
+
+
+class _Frozen:
+    """What ``EnergyLoss2D._traction`` reads of a model (``nm_edges``), over the solver's fp64 coordinate rows."""
+
+    def __init__(self, model, xf, xfix):
+        self._m, self._xf, self._xfix = model, xf, xfix
+
+    @property
+    def nm_edges(self):
+        from . import ops
+        m = self._m
+        coords = ops.AssembleRowsFn.apply(self._xf, self._xfix, m._idx_free, m._idx_fixed, m.Nnodes)
+        from .models import NeumannEdgesWrapper
+        return NeumannEdgesWrapper(coords, m.neumann_edges)
+
+
+def solve_displacement_(model, loss_fn, **kw) -> SolveInfo:
+    """One-shot ``FrozenMeshSolver(model, loss_fn, **kw).solve()``: ``model.u_free`` minimises the energy at the current
+    coordinates (in place)."""
+    return FrozenMeshSolver(model, loss_fn, **kw).solve()

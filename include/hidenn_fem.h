@@ -642,6 +642,36 @@ int hfem_rectq4_mse_f32(int device, const float *gx, int64_t nx, const float *gy
                         const float *x_eval, const float *target, int64_t m, float *loss_acc, float *ggx, float *ggy,
                         float *gu, void *stream);
 
+/* ------------------------------------------------------------------ frozen-mesh displacement solve (TRI3)
+ * Matrix-free preconditioned conjugate gradients for u_free at FIXED coordinates (hidenn_fem_amd/solve.py; no reference
+ * counterpart -- the reference reaches this minimum only by iterating Adam / L-BFGS on the energy).  The energy is exactly
+ * quadratic in u there, E(u) = 1/2 u^T K u - f^T u, so K p = dE/du(p) with no forces and r = -dE/du(u): the caller
+ * forms g0 = dE/du(u0) and g_zero = dE/du(u_free = 0) with hfem_tri3_energy_plan (fp64 rows, the forces of its loss) and
+ * the solver never sees the forces.  Paired-slot TRI3 plans only (the default); all vectors are fp64 free u rows [n_u][2]
+ * in the plan's storage order.  Two launches per iteration (csrc/tri3_cg.hip): q = K p with p = z + beta p_old formed in
+ * the gather, then u += alpha p, r -= alpha q, z = D^-1 r; alpha, beta and the stopping test |r|_2 <= max(rtol |f|_2, atol)
+ * are reduced on the device in a fixed order.  Once halted (converged, max_iter, breakdown: p^T K p <= 0 or a non-finite
+ * scalar) later iterations do nothing on the device: u keeps the last good iterate.
+ *   create   flags: HFEM_FLAG_PHYSICAL_GRAD or 0 (the gradient convention of K).  The plan must outlive the solver.
+ *   setup    binds the coordinate rows (fp64; they must stay allocated and unchanged while iterating) and the material, and
+ *            builds the preconditioner: precond 1 = block Jacobi (2x2 diagonal blocks of K), 0 = none.  diag_out [n_u][3]
+ *            (may be NULL): the blocks {K_xx, K_xy, K_yy}.
+ *   start    r = -g0, z = D^-1 r, |f| = |g_zero|; resets the status record.
+ *   iterate  n_iter iterations on u_free (launch only: capturable in a hipGraph).
+ *   status   synchronises the stream; status_host[16] = {iterations, |r|, |f|, rho = r^T z, reason (0 running, 1 rtol,
+ *            2 atol, 3 max_iter, 4 breakdown), alpha, beta, p^T K p, tolerance, max_iter, halted, ...}.
+ *   apply    standalone q = K p (fixed rows read as 0) and pq_out[0] = p^T q on the device; not during iterate.   */
+typedef struct hfem_cg hfem_cg;
+int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_cg **out);
+int hfem_cg_destroy(hfem_cg *cg);
+int hfem_cg_setup(hfem_cg *cg, const double *x_free, const double *x_fixed, const double mat[4], double W, int32_t precond,
+                  double *diag_out, void *stream);
+int hfem_cg_start(hfem_cg *cg, const double *g0, const double *g_zero, double rtol, double atol, int64_t max_iter,
+                  void *stream);
+int hfem_cg_iterate(hfem_cg *cg, double *u_free, int32_t n_iter, void *stream);
+int hfem_cg_status(hfem_cg *cg, double *status_host, void *stream);
+int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
