@@ -11,7 +11,8 @@ from src.mesh import generate_mesh
 from src.models import PiecewiseLinearShapeNN2D
 
 
-def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False):
+def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
+        r_adapt=False, outer=20):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -21,7 +22,11 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     fixed-mesh FEM reference an r-adapted energy is compared against.  The L-BFGS loop then starts from it; with the reference's
     fixed step (lr 1, no line search) on coordinates and displacements together it does not stay there: at that point the
     gradient is all coordinate gradient, and the coordinate steps invert elements (the energy turns NaN on this plate; the
-    reference's own op chain does the same on a smaller plate on the CPU)."""
+    reference's own op chain does the same on a smaller plate on the CPU).
+    ``r_adapt=True``: the alternating scheme the reference sketches in comments (example4.py:83-110) instead of the L-BFGS loop:
+    the frozen-mesh solve, then ``outer`` iterations of ``hidenn_fem_amd.radapt.RAdaptiveSolver`` (re-solve ``u``, an L-BFGS step
+    on the coordinates bounded so that no element inverts, Armijo on the energy); prints the energy history, the smallest
+    element quality and the stopping reason, and returns the r-adapted energy ``Pi*``."""
     import os
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -42,6 +47,8 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype)
+    if r_adapt:
+        return _r_adapt(model, loss_fn, outer)
     if solve_first:
         import time
         from hidenn_fem_amd.solve import solve_displacement_
@@ -100,6 +107,24 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     return model, value.item()
 
 
+def _r_adapt(model, loss_fn, outer):
+    import time
+    from hidenn_fem_amd.radapt import RAdaptiveSolver, mesh_quality
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    solver = RAdaptiveSolver(model, loss_fn, max_outer=outer)
+    info = solver.run()
+    torch.cuda.synchronize()
+    print(f"frozen-mesh energy {info.energy[0]:.9e} ({info.cg_iterations[0]} CG iterations)")
+    for k in range(1, info.iterations + 1):
+        print(f"outer {k:3d}: energy {info.energy[k]:.9e} |g_x|inf {info.grad_inf[k]:.3e} alpha {info.alpha[k]:.3e} "
+              f"(max {info.alpha_max[k]:.3e}) CG {info.cg_iterations[k]} min q {info.min_q[k]:.4f}")
+    mq = mesh_quality(model)
+    print(f"r-adapted energy {info.energy[-1]:.9e} after {info.iterations} outer iterations ({info.reason}), "
+          f"min q {mq.min_q:.4f}, inverted elements {mq.n_inverted}, {time.perf_counter() - t0:.3f} s")
+    return model, info.energy[-1]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=200)
@@ -109,6 +134,9 @@ if __name__ == "__main__":
     ap.add_argument("--fused-lbfgs", action="store_true")
     ap.add_argument("--sharded", action="store_true", help="owner-sharded energy + node-sharded L-BFGS (one process per GPU)")
     ap.add_argument("--solve-first", action="store_true", help="start L-BFGS from the frozen-mesh displacement solve (CG)")
+    ap.add_argument("--r-adapt", action="store_true",
+                    help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS")
+    ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
     a = ap.parse_args()
     run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
-        solve_first=a.solve_first)
+        solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer)

@@ -1,0 +1,371 @@
+"""r-adaptive TRI3 solve: alternate the frozen-mesh displacement solve with inversion-safe coordinate steps.
+
+HiDeNN-FEM treats the nodal coordinates as trainable: the FE energy is lowered by moving the interior nodes.  With the reduced
+energy ``Pi*(x) = min_u E(u, x)`` (evaluated by ``solve.FrozenMeshSolver``), the envelope theorem gives
+``grad Pi*(x) = dE/dx`` at ``u = u*(x)`` -- the coordinate gradient the graded energy kernel already returns.  A step on ``x``
+at fixed ``u_k`` that passes an Armijo test gives ``Pi*(x_k+1) <= E(u_k, x_k+1) < E(u_k, x_k) = Pi*(x_k)``: re-solving ``u`` (CG
+from ``u_k``, whose energy only decreases) can only lower it further, so every outer iteration lowers the reduced energy.
+What keeps each step valid is device code (``csrc/tri3_mesh.hip``): the step bound (the largest step before some element
+keeps less than ``eta`` of its signed area -- ``detJ(x + a d)`` is an exact quadratic in ``a``), the element measure (signed
+mean-ratio quality ``q``, the ``detJ`` ratio to the initial mesh, the inverted count) and the opt-in quality barrier
+``Q(x) = (w / Ne) sum (1/q - 1)``: the ``mesh_quality_loss`` the reference's example 4 sketches (examples/example4.py:83-110)
+and never defines.
+
+TRI3 models only; coordinate rows fp64 or fp32 (fp64 inside the kernels), any storage row order (``reorder``).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional
+
+import torch
+
+from . import _lib
+from ._lib import check, dev_index, ptr, stream_ptr
+
+F64 = torch.float64
+
+
+def _require_tri3(model, what):
+    if getattr(model, "nodes_per_element", 3) != 3:
+        raise NotImplementedError(f"{what}: TRI3 models only (QUAD4 has no mesh-validity kernels)")
+
+
+def _check_eta(eta):
+    if not (0.0 < float(eta) < 1.0):
+        raise ValueError(f"eta must be in (0, 1), got {eta!r}")
+
+
+class _Mesh:
+    """What the mesh kernels read of a model: the int32 connectivity, the x row map, the fixed and the reference rows (all on
+    the model's device, in its coordinate dtype)."""
+
+    def __init__(self, model):
+        _require_tri3(model, "hidenn_fem_amd.radapt")
+        xf = _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
+        if xf.dtype not in (F64, torch.float32):
+            raise RuntimeError(f"hidenn_fem_amd.radapt: coordinate rows must be fp64 or fp32, got {xf.dtype}")
+        self.model, self.dtype, self.device = model, xf.dtype, xf.device
+        self.f32 = xf.dtype == torch.float32
+        self.ne = int(model.Nelems)
+        self.conn = model._conn32.to(self.device).contiguous()
+        self.x_src = torch.from_numpy(model._x_src).to(self.device)
+        self.x_ref = model.initial_node_coords.to(device=self.device, dtype=self.dtype).contiguous()
+        self.n_x = int(xf.shape[0])
+
+    def fixed(self):
+        t = self.model.node_coords_fixed.to(device=self.device, dtype=self.dtype).contiguous()
+        return t if t.numel() else None
+
+    def fn(self, name):
+        L = _lib.lib()
+        return getattr(L, name + "_f32") if self.f32 else getattr(L, name)
+
+    def measure(self, x_ref=None, per_element=True):
+        """(q [Ne] or None, ratio [Ne] or None, summary [3] fp64 device) against ``x_ref`` (default: initial coordinates)."""
+        dev = self.device
+        q = torch.empty(self.ne, dtype=F64, device=dev) if per_element else None
+        r = torch.empty(self.ne, dtype=F64, device=dev) if per_element else None
+        summary = torch.empty(3, dtype=F64, device=dev)
+        xr = self.x_ref if x_ref is None else x_ref.to(dtype=self.dtype).contiguous()
+        xf = self.model.node_coords_free.detach()
+        xfix = self.fixed()
+        check(self.fn("hfem_tri3_mesh_measure")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
+                                                 ptr(xr), ptr(q), ptr(r), ptr(summary), stream_ptr(dev)),
+              "hfem_tri3_mesh_measure")
+        return q, r, summary
+
+    def step_bound(self, d, eta, out=None):
+        """0-d fp64 device tensor: the largest step along ``d`` (fp64 [n_x, 2], storage order) that keeps every element's
+        ``detJ`` at or above ``eta`` times its current value."""
+        dev = self.device
+        out = torch.empty((), dtype=F64, device=dev) if out is None else out
+        xf = self.model.node_coords_free.detach()
+        xfix = self.fixed()
+        check(self.fn("hfem_tri3_step_bound")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
+                                               ptr(d), float(eta), ptr(out), stream_ptr(dev)), "hfem_tri3_step_bound")
+        return out
+
+    def barrier(self, weight, grad=True):
+        """(Q 0-d fp64, dQ/dx_free fp64 [n_x, 2] or None) at the current coordinates."""
+        dev = self.device
+        val = torch.zeros((), dtype=F64, device=dev)
+        g = torch.zeros((self.n_x, 2), dtype=F64, device=dev) if grad else None
+        xf = self.model.node_coords_free.detach()
+        xfix = self.fixed()
+        check(self.fn("hfem_tri3_quality_barrier")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf),
+                                                    ptr(xfix), ptr(self.x_ref), float(weight), ptr(val), ptr(g),
+                                                    stream_ptr(dev)), "hfem_tri3_quality_barrier")
+        return val, g
+
+
+@dataclass
+class MeshQuality:
+    """Element measure against the model's ``initial_node_coords``.  ``q`` [Ne]: signed mean-ratio quality (1 = equilateral,
+    <= 0 = inverted); ``det_ratio`` [Ne]: ``detJ / detJ_initial``; both fp64 on the device, elements in the caller's order."""
+    q: torch.Tensor
+    det_ratio: torch.Tensor
+    min_q: float
+    min_det_ratio: float
+    n_inverted: int
+
+
+def mesh_quality(model) -> MeshQuality:
+    """Per-element quality and ``detJ`` ratio of the current coordinates, with the minimum of each and the number of inverted
+    elements (one measure launch; the summary is reduced on the device, deterministically)."""
+    q, r, s = _Mesh(model).measure()
+    s = s.tolist()
+    return MeshQuality(q=q, det_ratio=r, min_q=s[0], min_det_ratio=s[1], n_inverted=int(s[2]))
+
+
+def max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool = False):
+    """The largest ``alpha`` such that moving the free coordinate rows by ``alpha * d`` keeps every element's signed ``detJ``
+    at or above ``eta`` times its current value (``+inf`` if no step along ``d`` gets there).  ``d``: ``[n_x, 2]`` in the
+    storage order of ``node_coords_free`` (any float dtype; used in fp64).  For any caller's optimiser: a trial step below it
+    cannot invert an element.  ``as_tensor=True`` returns the 0-d fp64 device tensor without a host sync."""
+    _require_tri3(model, "max_feasible_step")
+    _check_eta(eta)
+    mesh = _Mesh(model)
+    if tuple(d.shape) != (mesh.n_x, 2):
+        raise ValueError(f"d must have the shape of node_coords_free {(mesh.n_x, 2)}, got {tuple(d.shape)}")
+    d64 = d.detach().to(device=mesh.device, dtype=F64).contiguous()
+    a = mesh.step_bound(d64, eta)
+    return a if as_tensor else a.item()
+
+
+def quality_barrier(model, weight: float = 1.0):
+    """``Q = (weight / Ne) sum_e (1/q_e - 1)`` at the current coordinates and its gradient with respect to the free coordinate
+    rows (fp64 ``[n_x, 2]``, storage order).  Accumulated with fp64 atomics: not bit-reproducible run to run."""
+    _require_tri3(model, "quality_barrier")
+    return _Mesh(model).barrier(weight)
+
+
+@dataclass
+class RAdaptInfo:
+    """Outcome of ``RAdaptiveSolver.run()``, one entry per outer iteration (entry 0: the frozen-mesh solve at the start).
+    ``energy``: ``Pi*`` (the energy at the solved ``u``); ``objective``: ``Pi* + Q`` (what the line search lowers; equal to
+    ``energy`` without the barrier); ``grad_inf``: ``|g_x|_inf`` of the objective; ``alpha`` / ``alpha_max``: the accepted step
+    and the step bound (0 / nan at entry 0); ``cg_iterations``; ``min_q`` against the initial mesh; ``step_ratio``: the smallest
+    ``detJ(x_k) / detJ(x_k-1)`` over the elements (>= ``eta`` by construction); ``trials``: line-search evaluations.
+    ``reason``: ``"gtol"``, ``"ftol"``, ``"max_outer"``, ``"line_search"`` (no trial passed the Armijo test, not even along the
+    steepest descent: the coordinates are left at the last accepted point) or ``"stalled"`` (the accepted step rounded away)."""
+    energy: List[float] = field(default_factory=list)
+    objective: List[float] = field(default_factory=list)
+    grad_inf: List[float] = field(default_factory=list)
+    alpha: List[float] = field(default_factory=list)
+    alpha_max: List[float] = field(default_factory=list)
+    cg_iterations: List[int] = field(default_factory=list)
+    min_q: List[float] = field(default_factory=list)
+    step_ratio: List[float] = field(default_factory=list)
+    trials: List[int] = field(default_factory=list)
+    reason: str = ""
+
+    @property
+    def iterations(self) -> int:
+        return len(self.energy) - 1
+
+
+class RAdaptiveSolver:
+    """Alternating r-adaptive minimisation of the TRI3 energy over ``u_free`` and ``node_coords_free`` (module docstring).
+
+    One outer iteration: (1) ``u <- FrozenMeshSolver.solve()``, warm-started (one solver instance; it refreshes itself when the
+    coordinates moved; fp64 models restart it from the true residual when that drifted, ``solve_and_grad``); (2) ``g_x = dE/dx_free`` at that ``u`` through ``loss_fn(model, b_force, t_force)`` and
+    ``torch.autograd.grad`` on ``node_coords_free`` alone (every force table enters as in training), plus ``dQ/dx`` when
+    ``quality_weight > 0``; (3) an L-BFGS direction over the x rows (``history`` pairs, a pair with ``s^T y <= 0`` skipped;
+    ``history=0``: steepest descent with a Barzilai-Borwein initial step); (4) ``alpha_max`` from the step-bound kernel, trial
+    ``min(alpha_init, 0.9 alpha_max)`` (``alpha_init`` = 1 with curvature pairs, the BB step without, ``0.9 alpha_max`` at the
+    very first step), halved until ``E(u_k, x + a d) + Q(x + a d)`` passes the Armijo test with ``c1`` -- one loss-only
+    evaluation per trial, ``x + a d`` written into ``node_coords_free`` in place.  A failed search retries once along the
+    steepest descent, then restores ``x`` and stops.
+
+    Stopping: ``gtol`` -- ``|g_x|_inf <= gtol * |Pi*_0 + Q_0| / L`` (``L``: diagonal of the initial mesh's bounding box, so the
+    test is free of units); ``ftol`` -- the objective fell by no more than ``ftol * max(|f_k|, |f_k+1|, 1)``; ``max_outer``
+    coordinate steps.  Only ``node_coords_free`` and ``u_free`` change: ``.grad`` of both, the Dirichlet rows and the fixed
+    coordinate rows are untouched.  fp32 models: fp64 inside the kernels, coordinates rounded once per trial on write-back (the
+    0.9 margin and ``eta`` absorb the rounding).  QUAD4 models and ``EnergyLoss2D(deterministic=True)`` are refused."""
+
+    def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None, *,
+                 history: int = 10, eta: float = 0.25, quality_weight: float = 0.0, cg_rtol: float = 1e-10,
+                 gtol: float = 1e-9, ftol: float = 1e-12, max_outer: int = 50, max_ls: int = 20, c1: float = 1e-4,
+                 max_restarts: int = 5):
+        _require_tri3(model, "RAdaptiveSolver")
+        if getattr(loss_fn, "deterministic", False):
+            raise NotImplementedError("RAdaptiveSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
+                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+        _check_eta(eta)
+        if int(history) < 0 or int(max_outer) < 0 or int(max_ls) < 1 or int(max_restarts) < 0:
+            raise ValueError("history, max_outer and max_restarts must be >= 0, max_ls >= 1")
+        if not (0.0 < c1 < 1.0):
+            raise ValueError("c1 must be in (0, 1)")
+        if not (quality_weight >= 0.0 and math.isfinite(quality_weight)):
+            raise ValueError("quality_weight must be finite and >= 0")
+        if gtol < 0 or ftol < 0:
+            raise ValueError("gtol and ftol must be >= 0")
+        from .solve import FrozenMeshSolver
+        self.mesh = _Mesh(model)
+        self.model, self.loss_fn, self.b_force, self.t_force = model, loss_fn, b_force, t_force
+        self.history, self.eta, self.quality_weight = int(history), float(eta), float(quality_weight)
+        self.gtol, self.ftol, self.max_outer, self.max_ls, self.c1 = float(gtol), float(ftol), int(max_outer), int(max_ls), float(c1)
+        self.max_restarts = int(max_restarts)
+        self.solver = FrozenMeshSolver(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol)
+        self.last_solve = None                                 # SolveInfo of the latest displacement solve
+        x0 = model.initial_node_coords.detach().double()
+        self.length = float((x0.max(dim=0).values - x0.min(dim=0).values).norm()) if x0.numel() else 1.0
+
+    # ---- pieces of an outer iteration (also timed one by one by scripts/radapt_timing.py)
+    def objective_and_grad(self):
+        """(``E``, ``E + Q``, flat fp64 ``d(E + Q)/dx_free``, ``||dE/du_free||``) at the current ``u`` and coordinates (one
+        launch yields both gradients); ``.grad`` untouched."""
+        m = self.model
+        with torch.enable_grad():
+            e = self.loss_fn(m, self.b_force, self.t_force)
+            gx, gu = torch.autograd.grad(e, [m.node_coords_free, m.u_free])
+        self._gu_norm = float(gu.detach().double().norm().item())
+        g = gx.detach().to(F64).reshape(-1)
+        e = float(e.detach().double().item())
+        f = e
+        if self.quality_weight > 0.0:
+            q, gq = self.mesh.barrier(self.quality_weight)
+            g = g + gq.reshape(-1)
+            f = e + float(q.item())
+        return e, f, g
+
+    def solve_and_grad(self):
+        """Displacement solve at the current coordinates, then ``objective_and_grad()``.  fp64 models: while the true residual
+        ``||dE/du||`` exceeds twice the CG tolerance, CG restarts from the current ``u`` (at most ``max_restarts`` times).  The
+        solver's own test reads the recurrence residual, which drifts from the true one by about eps x cond(K) -- and cond(K)
+        grows as r-adaptation thins elements (1/min q).  Returns (E, E + Q, g, CG iterations)."""
+        sol = self.last_solve = self.solver.solve()
+        iters = sol.iterations
+        e, f, g = self.objective_and_grad()
+        if self.model.node_coords_free.dtype == F64:                # fp32 rows: rounding u on write-back sets the floor
+            for _ in range(self.max_restarts):
+                before = self._gu_norm
+                if not before > 2.0 * self.solver.rtol * sol.rhs_norm:
+                    break
+                sol = self.last_solve = self.solver.solve()
+                iters += sol.iterations
+                e, f, g = self.objective_and_grad()
+                if not self._gu_norm < 0.5 * before:                   # at the rounding floor: restarts no longer help
+                    break
+        return e, f, g, iters
+
+    def objective(self) -> float:
+        """``E + Q`` at the current ``u`` and coordinates, loss only."""
+        with torch.no_grad():
+            f = float(self.loss_fn(self.model, self.b_force, self.t_force).double().item())
+            if self.quality_weight > 0.0:
+                f += float(self.mesh.barrier(self.quality_weight, grad=False)[0].item())
+        return f
+
+    def _direction(self, g, pairs):
+        """L-BFGS two-loop recursion over the flat x rows: ``d = -H g``."""
+        q = -g
+        if not pairs:
+            return q
+        alphas = []
+        for s, y, rho in reversed(pairs):
+            a = rho * torch.dot(s, q)
+            q = q - a * y
+            alphas.append(a)
+        s, y, _ = pairs[-1]
+        q = q * (torch.dot(s, y) / torch.dot(y, y))
+        for (s, y, rho), a in zip(pairs, reversed(alphas)):
+            b = rho * torch.dot(y, q)
+            q = q + (a - b) * s
+        return q
+
+    def _line_search(self, x0, d, f0, gd, alpha_init):
+        """Backtracking Armijo along ``d`` from the rows ``x0`` (fp64 flat).  Returns (accepted alpha or None, alpha_max, f, trials);
+        on failure ``node_coords_free`` holds ``x0`` again."""
+        xf = self.model.node_coords_free
+        d2 = d.reshape(xf.shape).contiguous()
+        amax = float(self.mesh.step_bound(d2, self.eta).item())
+        alpha = min(alpha_init, 0.9 * amax)
+        if not math.isfinite(alpha):                          # no element shrinks along d and no curvature yet
+            alpha = 1.0
+        for t in range(self.max_ls):
+            with torch.no_grad():
+                xf.copy_((x0 + alpha * d).reshape(xf.shape))   # rounds once for fp32 rows
+            f = self.objective()
+            if math.isfinite(f) and f <= f0 + self.c1 * alpha * gd:
+                return alpha, amax, f, t + 1
+            alpha *= 0.5
+        with torch.no_grad():
+            xf.copy_(x0.reshape(xf.shape))
+        return None, amax, f0, self.max_ls
+
+    def run(self) -> RAdaptInfo:
+        m, info = self.model, RAdaptInfo()
+        xf = m.node_coords_free
+        e, f, g, cg_iters = self.solve_and_grad()
+        gscale = max(abs(f), 1e-300) / self.length
+
+        def record(e, f, g, alpha, amax, cg_iters, step_ratio, trials):
+            _, _, s = self.mesh.measure(per_element=False)
+            info.energy.append(e)
+            info.objective.append(f)
+            info.grad_inf.append(float(g.abs().max().item()) if g.numel() else 0.0)
+            info.alpha.append(alpha)
+            info.alpha_max.append(amax)
+            info.cg_iterations.append(cg_iters)
+            info.min_q.append(float(s[0].item()))
+            info.step_ratio.append(step_ratio)
+            info.trials.append(trials)
+
+        record(e, f, g, 0.0, math.nan, cg_iters, math.nan, 0)
+        pairs, last = [], None                                 # curvature pairs (s, y, 1 / s^T y); the latest pair for BB
+        while True:
+            if info.grad_inf[-1] <= self.gtol * gscale:
+                info.reason = "gtol"
+                break
+            if info.iterations >= self.max_outer:
+                info.reason = "max_outer"
+                break
+            x0 = xf.detach().to(F64).reshape(-1).clone()
+            with torch.no_grad():
+                coords0 = m.coords.to(self.mesh.dtype).contiguous()     # x_k by node id: the reference of the step ratio
+            step = None
+            for use_pairs in ([True, False] if pairs else [False]):   # L-BFGS direction, then once the steepest descent
+                d = self._direction(g, pairs if use_pairs else [])
+                gd = float(torch.dot(g, d).item())
+                if not gd < 0.0:                                    # not a descent direction: steepest descent instead
+                    d, gd, use_pairs = -g, -float(torch.dot(g, g).item()), False
+                if use_pairs:
+                    alpha_init = 1.0
+                elif last is not None:
+                    sy = float(torch.dot(last[0], last[1]).item())
+                    alpha_init = float(torch.dot(last[0], last[0]).item()) / sy if sy > 0.0 else math.inf
+                else:
+                    alpha_init = math.inf
+                alpha, amax, _, trials = self._line_search(x0, d, f, gd, alpha_init)
+                if alpha is not None:
+                    step = (alpha, amax, trials)
+                    break
+                pairs = []                                          # the curvature history did not help: drop it
+                if not use_pairs:
+                    break
+            if step is None:
+                info.reason = "line_search"
+                break
+            x1 = xf.detach().to(F64).reshape(-1)
+            if torch.equal(x1, x0):
+                info.reason = "stalled"
+                break
+            _, ratio, _ = self.mesh.measure(x_ref=coords0)
+            step_ratio = float(ratio.min().item()) if ratio.numel() else math.nan
+            e1, f1, g1, cg_iters = self.solve_and_grad()
+            s, y = x1 - x0, g1 - g
+            sy = float(torch.dot(s, y).item())
+            if sy > 0.0:
+                last = (s, y)
+                if self.history > 0:
+                    pairs.append((s, y, 1.0 / sy))
+                    pairs = pairs[-self.history:]
+            record(e1, f1, g1, step[0], step[1], cg_iters, step_ratio, step[2])
+            f_old, f, g = f, f1, g1
+            if f_old - f1 <= self.ftol * max(abs(f_old), abs(f1), 1.0):
+                info.reason = "ftol"
+                break
+        return info

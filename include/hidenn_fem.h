@@ -672,6 +672,40 @@ int hfem_cg_iterate(hfem_cg *cg, double *u_free, int32_t n_iter, void *stream);
 int hfem_cg_status(hfem_cg *cg, double *status_host, void *stream);
 int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void *stream);
 
+/* ------------------------------------------------------------------ mesh validity for r-adaptivity (TRI3)
+ * What keeps a coordinate update valid (hidenn_fem_amd/radapt.py; no reference counterpart -- the reference's example 4
+ * moves the nodes with L-BFGS unguarded and calls a mesh_quality_loss it never defines).  One thread per element over the
+ * int32 connectivity conn [ne][3] (caller numbering); corner rows through the x row map x_src [nn] (>= 0: x_free row,
+ * < 0: x_fixed row -1 - x_src), so any storage row order works.  x_free / x_fixed / x_ref rows are fp64 (plain) or fp32
+ * (_f32); the arithmetic is fp64.  detJ = (x0-x2)(y1-y2) - (x1-x2)(y0-y2); the signed mean-ratio quality is
+ * q = 4 sqrt(3) s A / (|e1|^2 + |e2|^2 + |e3|^2), s = sign of detJ on x_ref (the model's initial coordinates, [nn][2] by node
+ * id): q in (0, 1] for a valid element, <= 0 for an inverted one, whatever the mesh's orientation.
+ *   mesh_measure     q_out [ne], ratio_out [ne] = detJ / detJ_ref (both may be NULL); summary_out [3] (device) = {min q,
+ *                    min ratio, number of inverted elements (s detJ <= 0)}.  Deterministic (order-independent reductions).
+ *   step_bound       d [n_x][2] fp64 over the free rows (fixed rows move by 0), eta in (0, 1): alpha_out [1] (device) = the
+ *                    smallest alpha > 0 with detJ(x + alpha d) = eta detJ(x) over all elements, +inf if there is none
+ *                    (0 for an element with detJ(x) = 0).  detJ(x + alpha d) is an exact quadratic in alpha; stable roots.
+ *                    Deterministic; launch-only (capturable in a hipGraph).
+ *   quality_barrier  ACCUMULATES value_acc[0] += Q = (weight / ne) sum_e (1/q_e - 1) and grad_acc [n_x][2] += dQ/dx_free
+ *                    (either may be NULL; fixed rows get nothing).  fp64 atomics: not deterministic in the last bits.
+ *                    Finite for valid elements only.                                                                   */
+int hfem_tri3_mesh_measure(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                           const double *x_fixed, const double *x_ref, double *q_out, double *ratio_out, double *summary_out,
+                           void *stream);
+int hfem_tri3_mesh_measure_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                               const float *x_fixed, const float *x_ref, double *q_out, double *ratio_out,
+                               double *summary_out, void *stream);
+int hfem_tri3_step_bound(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                         const double *x_fixed, const double *d, double eta, double *alpha_out, void *stream);
+int hfem_tri3_step_bound_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                             const float *x_fixed, const double *d, double eta, double *alpha_out, void *stream);
+int hfem_tri3_quality_barrier(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                              const double *x_fixed, const double *x_ref, double weight, double *value_acc, double *grad_acc,
+                              void *stream);
+int hfem_tri3_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                  const float *x_fixed, const float *x_ref, double weight, double *value_acc,
+                                  double *grad_acc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""r-adaptive solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/radapt.py, csrc/tri3_mesh.hip).
+
+Records, as one JSON object:
+  * the step-bound launch (init + element kernel), the measure launch (init + element kernel + finish), the barrier launch
+    (zero fill of the value and the [n_x, 2] gradient + element kernel): device events around graph replays of 16 calls;
+  * the graded energy evaluation on the same mesh (value_and_grad_), for scale;
+  * one line-search trial (write x + a d, loss-only energy, host read of the value) and the coordinate gradient
+    (loss_fn + autograd.grad on node_coords_free): host clock, synchronised, median of repeats;
+  * three outer iterations of RAdaptiveSolver: per iteration the warm-started CG solve and everything else (host clock);
+  * the 36 k-element example-4 plate (200 x 100, fp64), without and with the quality barrier (weight 0.05): outer iterations,
+    Pi* before and after, reason, min q, wall time.
+Cache regime: the working sets stay in the 256 MB Infinity Cache.
+
+    python scripts/radapt_timing.py [--grid 1001x501] [--reps 200] [--out profiles/radapt/radapt_timing_T1M.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from hidenn_fem_amd.loss import EnergyLoss2D
+from hidenn_fem_amd.mesh import generate_mesh, structured_tri_mesh
+from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+from hidenn_fem_amd.radapt import RAdaptiveSolver, mesh_quality
+
+F64 = torch.float64
+
+
+def events_us(fn, reps):
+    """Mean device time per call of `fn` over `reps` back-to-back calls (after a warm-up), median of 5 such runs."""
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1e3 / reps)
+    return sorted(out)[len(out) // 2]
+
+
+def graphed_us(fn, reps, k=16):
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(k):
+            fn()
+    return events_us(g.replay, max(reps // k, 4)) / k
+
+
+def host_us(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e6)
+    return sorted(out)[len(out) // 2]
+
+
+class Clock:
+    """Wraps a callable; accumulates its synchronised host time."""
+
+    def __init__(self, fn):
+        self.fn, self.total = fn, 0.0
+
+    def __call__(self, *a, **k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = self.fn(*a, **k)
+        torch.cuda.synchronize()
+        self.total += time.perf_counter() - t0
+        return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", default="1001x501")
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    nx, ny = (int(v) for v in a.grid.split("x"))
+    coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    torch.manual_seed(0)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
+    lf = EnergyLoss2D(device=dev, dtype=F64)
+    ne, nn = m.Nelems, m.Nnodes
+    rec = dict(mesh=f"{nx}x{ny} structured, jitter 0.2", n_elems=ne, n_nodes=nn, n_x_rows=int(m.node_coords_free.shape[0]),
+               regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
+
+    s = RAdaptiveSolver(m, lf, max_outer=3)
+    mesh = s.mesh
+    d = torch.randn(m.node_coords_free.shape, dtype=F64, device=dev) * 1e-3
+    alpha = torch.empty((), dtype=F64, device=dev)
+    bound_us = graphed_us(lambda: mesh.step_bound(d, 0.25, out=alpha), a.reps)
+    alg = 12 * ne + (4 + 16 + 16) * nn
+    rec["step_bound"] = dict(us=bound_us, launches=2, algorithmic_bytes=alg, tb_per_s=alg / bound_us * 1e-6,
+                             note="12 B/element of connectivity + per node: x_src 4 B, x row 16 B, d row 16 B")
+    rec["measure"] = dict(us=graphed_us(lambda: mesh.measure(per_element=False), a.reps), launches=3)
+    rec["measure_per_element_outputs"] = dict(us=graphed_us(lambda: mesh.measure(per_element=True), a.reps))
+    rec["barrier"] = dict(us=graphed_us(lambda: mesh.barrier(1.0), a.reps), launches="2 fills + 1")
+    energy_us = graphed_us(lambda: lf.value_and_grad_(m), a.reps)
+    rec["energy_value_and_grad"] = dict(us=energy_us, note="pair kernel + tile-energy sum launch")
+    rec["step_bound_over_energy"] = bound_us / energy_us
+    m.node_coords_free.grad = None
+    m.u_free.grad = None
+
+    s.solver.solve()
+    x0 = m.node_coords_free.detach().clone()
+
+    def trial():
+        with torch.no_grad():
+            m.node_coords_free.copy_(x0 + 1e-3 * d)
+        return s.objective()
+
+    rec["line_search_trial_host_us"] = host_us(trial, 20)
+    with torch.no_grad():
+        m.node_coords_free.copy_(x0)
+    rec["gradient_host_us"] = host_us(s.objective_and_grad, 20)
+
+    # ---- outer iterations: CG vs everything else
+    solve_clock = Clock(s.solver.solve)
+    s.solver.solve = solve_clock
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = s.run()
+    torch.cuda.synchronize()
+    total = time.perf_counter() - t0
+    rec["outer_T1M"] = dict(iterations=info.iterations, reason=info.reason, cg_iterations=info.cg_iterations,
+                            energy=info.energy, alpha=info.alpha, alpha_max=info.alpha_max, trials=info.trials,
+                            min_q=info.min_q, seconds_total=total, seconds_cg=solve_clock.total,
+                            seconds_other=total - solve_clock.total,
+                            other_over_cg=(total - solve_clock.total) / solve_clock.total)
+
+    # ---- the example-4 plate (36 k elements)
+    nodes, conn4, geom4, bc4, mn4, edges4 = generate_mesh(2.0, 1.0, [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)],
+                                                          {"up": 0, "down": 0, "right": 2, "left": 1}, 200, 100)
+    for key, w in (("example4_plate", 0.0), ("example4_plate_barrier_0.05", 0.05)):
+        torch.manual_seed(0)
+        p = PiecewiseLinearShapeNN2D(nodes.double(), conn4, boundary_mask=geom4, dirichlet_mask=bc4, u_fixed=0.0,
+                                     neumann_edges=edges4).to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pi = RAdaptiveSolver(p, lf, max_outer=50, quality_weight=w).run()
+        torch.cuda.synchronize()
+        mq = mesh_quality(p)
+        rec[key] = dict(n_elems=p.Nelems, quality_weight=w, iterations=pi.iterations, reason=pi.reason,
+                        energy_frozen=pi.energy[0], energy_final=pi.energy[-1], decrease=pi.energy[0] - pi.energy[-1],
+                        cg_iterations=pi.cg_iterations, min_q_initial=pi.min_q[0], min_q_final=mq.min_q,
+                        n_inverted=mq.n_inverted, seconds=time.perf_counter() - t0, energy=pi.energy)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
