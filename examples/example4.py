@@ -12,7 +12,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
-        r_adapt=False, outer=20):
+        r_adapt=False, outer=20, precond="block_jacobi"):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -26,7 +26,8 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     ``r_adapt=True``: the alternating scheme the reference sketches in comments (example4.py:83-110) instead of the L-BFGS loop:
     the frozen-mesh solve, then ``outer`` iterations of ``hidenn_fem_amd.radapt.RAdaptiveSolver`` (re-solve ``u``, an L-BFGS step
     on the coordinates bounded so that no element inverts, Armijo on the energy); prints the energy history, the smallest
-    element quality and the stopping reason, and returns the r-adapted energy ``Pi*``."""
+    element quality and the stopping reason, and returns the r-adapted energy ``Pi*``.
+    ``precond``: the CG preconditioner of ``solve_first`` and ``r_adapt`` (``"block_jacobi"`` or ``"amg"``)."""
     import os
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -48,13 +49,13 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype)
     if r_adapt:
-        return _r_adapt(model, loss_fn, outer)
+        return _r_adapt(model, loss_fn, outer, precond)
     if solve_first:
         import time
         from hidenn_fem_amd.solve import solve_displacement_
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        info = solve_displacement_(model, loss_fn, rtol=1e-10)
+        info = solve_displacement_(model, loss_fn, rtol=1e-10, precond=precond)
         torch.cuda.synchronize()
         if rank0:
             print(f"frozen-mesh solve: {info.iterations} CG iterations, |r|/|f| = {info.residual_norm / max(info.rhs_norm, 1e-300):.2e} "
@@ -107,12 +108,12 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     return model, value.item()
 
 
-def _r_adapt(model, loss_fn, outer):
+def _r_adapt(model, loss_fn, outer, precond="block_jacobi"):
     import time
     from hidenn_fem_amd.radapt import RAdaptiveSolver, mesh_quality
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    solver = RAdaptiveSolver(model, loss_fn, max_outer=outer)
+    solver = RAdaptiveSolver(model, loss_fn, max_outer=outer, cg_precond=precond)
     info = solver.run()
     torch.cuda.synchronize()
     print(f"frozen-mesh energy {info.energy[0]:.9e} ({info.cg_iterations[0]} CG iterations)")
@@ -137,6 +138,9 @@ if __name__ == "__main__":
     ap.add_argument("--r-adapt", action="store_true",
                     help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS")
     ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
+    ap.add_argument("--precond", choices=["block_jacobi", "amg"], default="block_jacobi",
+                    help="CG preconditioner of --solve-first and --r-adapt")
     a = ap.parse_args()
     run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
-        solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer)
+        solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,
+        precond=a.precond)

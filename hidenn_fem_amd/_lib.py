@@ -150,6 +150,19 @@ PROTOTYPES = {
     "hfem_tri3_mesh_measure": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_tri3_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_tri3_quality_barrier": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp]),
+    "hfem_amg_host_create": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_vp)]),
+    "hfem_amg_host_destroy": (C.c_int, [_vp]),
+    "hfem_amg_host_info": (C.c_int, [_vp, _i32, _vp]),
+    "hfem_amg_host_copy": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "hfem_amg_create": (C.c_int, [C.c_int, _vp, _i32, C.POINTER(_vp)]),
+    "hfem_amg_destroy": (C.c_int, [_vp]),
+    "hfem_amg_assemble": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp]),
+    "hfem_amg_setup": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_amg_set_coarse": (C.c_int, [_vp, _vp]),
+    "hfem_amg_vcycle": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "hfem_amg_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "hfem_cg_start_amg": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _f64, _i64, _vp]),
+    "hfem_cg_iterate_amg": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 mesh-validity entry points (same argument lists; every array pointer

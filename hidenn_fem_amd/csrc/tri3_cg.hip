@@ -18,6 +18,8 @@
 // Two launches per iteration; every scalar is reduced on the device in a fixed order (bit-reproducible given q; q itself
 // carries the LDS atomics' run-to-run last bits).  Once the status record says halted (converged, max_iter, breakdown) every
 // later launch returns at once: iterations replayed behind the last one do nothing.
+// precond = AMG (hfem_cg_start_amg / hfem_cg_iterate_amg): tri3_cg_vec_amg_kernel (the update without z), the V-cycle of
+// tri3_amg.hip (z = M r) and tri3_cg_rz_kernel (rho = r^T z, beta) replace the vector kernel: four launch groups per iteration.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +27,7 @@
 #include <memory>
 #include <string>
 
+#include "hfem_amg.h"
 #include "hfem_device.h"
 #include "hfem_plan_dev.h"
 
@@ -35,6 +38,7 @@ namespace {
 enum { kIter = 0, kRnorm, kFnorm, kRho, kReason, kAlpha, kBeta, kPq, kTol, kMaxIter, kHalted, kRtolWins, kStatusN = 16 };
 enum { kRunning = 0, kRtol = 1, kAtol = 2, kMaxIterHit = 3, kBreakdown = 4 };
 constexpr int kVecBlock = 256, kVecMaxBlocks = 1024;
+static_assert(kHalted == kAmgHaltedIndex, "the AMG cycle kernels test the status record's halted slot");
 
 __device__ __forceinline__ void publish(const double *st, double *host) {
     if (host)
@@ -357,6 +361,104 @@ __global__ __launch_bounds__(kVecBlock) void tri3_cg_vec_kernel(
     publish(st, host);
 }
 
+// ---------------------------------------------------------------- AMG-preconditioned iteration (tri3_amg.hip cycle)
+// Vector update without the preconditioner: u += alpha p, r -= alpha q, |r|, the stopping test (START: r = -g0, |f|).
+// z = M r comes from the V-cycle after this launch, rho = r^T z and beta from tri3_cg_rz_kernel after that.
+template <bool START>
+__global__ __launch_bounds__(kVecBlock) void tri3_cg_vec_amg_kernel(
+    int64_t n, double2 *__restrict__ u, double2 *__restrict__ r, const double2 *pbuf0, const double2 *pbuf1,
+    const double2 *__restrict__ q, const double2 *__restrict__ g0, const double2 *__restrict__ gzero, double *__restrict__ part,
+    unsigned *ticket, double *st, double *host, double rtol, double atol, double max_iter) {
+    __shared__ double red[kVecBlock / 64 + 1];
+    const int tid = threadIdx.x;
+    const int nb = (int)gridDim.x;
+    if (!START && st[kHalted] != 0.0) return;
+    double alpha = 0.0;
+    const double2 *p = nullptr;
+    if (!START) {
+        alpha = st[kAlpha];
+        p = (((long long)st[kIter]) & 1) ? pbuf0 : pbuf1;
+    }
+    double rr = 0.0, ff = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVecBlock + tid; i < n; i += (int64_t)nb * kVecBlock) {
+        double2 ri;
+        if (START) {
+            const double2 g = g0[i], h = gzero[i];
+            ri = make_double2(-g.x, -g.y);
+            ff += h.x * h.x + h.y * h.y;
+        } else {
+            const double2 pi = p[i], qi = q[i];
+            double2 ui = u[i];
+            ri = r[i];
+            ui.x = __builtin_fma(alpha, pi.x, ui.x); ui.y = __builtin_fma(alpha, pi.y, ui.y);
+            ri.x = __builtin_fma(-alpha, qi.x, ri.x); ri.y = __builtin_fma(-alpha, qi.y, ri.y);
+            u[i] = ui;
+        }
+        r[i] = ri;
+        rr += ri.x * ri.x + ri.y * ri.y;
+    }
+    const double s_rr = block_sum(rr, red);
+    __syncthreads();
+    const double s_ff = START ? block_sum(ff, red) : 0.0;
+    if (tid == 0) {
+        put_partial(part + nb + blockIdx.x, s_rr);
+        put_partial(part + 2 * nb + blockIdx.x, s_ff);
+    }
+    if (!last_block(ticket, (unsigned)nb, reinterpret_cast<int *>(red + kVecBlock / 64))) return;
+    const double r2 = ordered_sum<kVecBlock>(part + nb, nb, red);
+    __syncthreads();
+    const double f2 = START ? ordered_sum<kVecBlock>(part + 2 * nb, nb, red) : 0.0;
+    if (tid != 0) return;
+    const double rnorm = sqrt(r2);
+    int reason = kRunning;
+    if (START) {
+        for (int i = 0; i < kStatusN; ++i) st[i] = 0.0;
+        st[kFnorm] = sqrt(f2);
+        st[kTol] = fmax(rtol * st[kFnorm], atol);
+        st[kMaxIter] = max_iter;
+        st[kRtolWins] = rtol * st[kFnorm] >= atol ? 1.0 : 0.0;
+    } else {
+        st[kIter] += 1.0;
+    }
+    st[kRnorm] = rnorm;
+    if (!isfinite(rnorm)) reason = kBreakdown;
+    else if (rnorm <= st[kTol]) reason = st[kRtolWins] != 0.0 ? kRtol : kAtol;
+    else if (st[kIter] >= st[kMaxIter]) reason = kMaxIterHit;
+    if (reason != kRunning) {
+        st[kHalted] = 1.0;
+        st[kReason] = reason;
+    }
+    publish(st, host);
+}
+
+// rho = r^T z in block order, beta = rho / rho_old (0 on the first direction)
+__global__ __launch_bounds__(kVecBlock) void tri3_cg_rz_kernel(int64_t n, const double2 *__restrict__ r,
+                                                               const double2 *__restrict__ z, double *__restrict__ part,
+                                                               unsigned *ticket, double *st, double *host) {
+    __shared__ double red[kVecBlock / 64 + 1];
+    const int tid = threadIdx.x;
+    const int nb = (int)gridDim.x;
+    if (st[kHalted] != 0.0) return;
+    double rz = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kVecBlock + tid; i < n; i += (int64_t)nb * kVecBlock) {
+        const double2 ri = r[i], zi = z[i];
+        rz += ri.x * zi.x + ri.y * zi.y;
+    }
+    const double s_rz = block_sum(rz, red);
+    if (tid == 0) put_partial(part + blockIdx.x, s_rz);
+    if (!last_block(ticket, (unsigned)nb, reinterpret_cast<int *>(red + kVecBlock / 64))) return;
+    const double rho = ordered_sum<kVecBlock>(part, nb, red);
+    if (tid != 0) return;
+    const double beta = st[kIter] == 0.0 ? 0.0 : rho / st[kRho];
+    st[kBeta] = beta;
+    st[kRho] = rho;
+    if (!isfinite(rho) || !isfinite(beta)) {
+        st[kHalted] = 1.0;
+        st[kReason] = kBreakdown;
+    }
+    publish(st, host);
+}
+
 }  // namespace
 }  // namespace hfem
 
@@ -555,4 +657,56 @@ extern "C" int hfem_cg_apply(hfem_cg *c, const double *p, double *q, double *pq_
     if (int rc = hfem::use_device(c->device)) return rc;
     cg_apply(c, (const double2 *)p, (double2 *)q, c->tickets + 2, nullptr, nullptr, pq_out, (hipStream_t)stream);
     return hfem::launch_status("hfem_cg_apply");
+}
+
+// ---------------------------------------------------------------- AMG-preconditioned PCG
+namespace {
+template <bool START>
+void cg_vec_amg(const hfem_cg *c, double2 *u, const double2 *g0, const double2 *gzero, double rtol, double atol, double max_iter,
+                hipStream_t s) {
+    hipLaunchKernelGGL((hfem::tri3_cg_vec_amg_kernel<START>), dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, u, c->r,
+                       c->p[0], c->p[1], c->q, g0, gzero, c->vec_part, c->tickets + 1, c->st, c->host, rtol, atol, max_iter);
+}
+
+void cg_rz(const hfem_cg *c, hipStream_t s) {
+    hipLaunchKernelGGL(hfem::tri3_cg_rz_kernel, dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, c->r, c->z,
+                       c->vec_part, c->tickets + 1, c->st, c->host);
+}
+
+int check_amg(const hfem_cg *c, const hfem_amg *a) {
+    HFEM_ARG_CHECK(c->ready, "hfem_cg_setup has not run");
+    HFEM_ARG_CHECK(hfem::amg_ready(a), "hfem_amg_setup / hfem_amg_set_coarse have not run");
+    HFEM_ARG_CHECK(hfem::amg_rows(a) == c->n_u, "the AMG hierarchy and the CG solve have different free rows");
+    HFEM_ARG_CHECK(hfem::amg_device(a) == c->device, "the AMG hierarchy lives on another device");
+    return 0;
+}
+}  // namespace
+
+extern "C" int hfem_cg_start_amg(hfem_cg *c, hfem_amg *amg, const double *g0, const double *g_zero, double rtol, double atol,
+                                 int64_t max_iter, void *stream) {
+    HFEM_ARG_CHECK(c && amg && g0 && g_zero, "null pointer");
+    if (int rc = check_amg(c, amg)) return rc;
+    HFEM_ARG_CHECK(rtol >= 0.0 && atol >= 0.0 && max_iter >= 0, "rtol, atol and max_iter must be >= 0");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HFEM_HIP_CHECK(hipMemsetAsync(c->p[0], 0, 2 * (size_t)std::max<int64_t>(c->n_u, 1) * 16, s));
+    cg_vec_amg<true>(c, nullptr, (const double2 *)g0, (const double2 *)g_zero, rtol, atol, (double)max_iter, s);
+    hfem::amg_cycle(amg, (const double *)c->r, (double *)c->z, c->st, s);
+    cg_rz(c, s);
+    return hfem::launch_status("hfem_cg_start_amg");
+}
+
+extern "C" int hfem_cg_iterate_amg(hfem_cg *c, hfem_amg *amg, double *u_free, int32_t n_iter, void *stream) {
+    HFEM_ARG_CHECK(c && amg && (u_free || c->n_u == 0), "null pointer");
+    if (int rc = check_amg(c, amg)) return rc;
+    HFEM_ARG_CHECK(n_iter >= 0, "n_iter must be >= 0");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for (int it = 0; it < n_iter; ++it) {                    // launch-only: capturable in one graph
+        cg_apply(c, c->z, c->q, c->tickets, c->st, c->host, nullptr, s);
+        cg_vec_amg<false>(c, (double2 *)u_free, nullptr, nullptr, 0.0, 0.0, 0.0, s);
+        hfem::amg_cycle(amg, (const double *)c->r, (double *)c->z, c->st, s);
+        cg_rz(c, s);
+    }
+    return hfem::launch_status("hfem_cg_iterate_amg");
 }

@@ -183,12 +183,14 @@ class RAdaptiveSolver:
     test is free of units); ``ftol`` -- the objective fell by no more than ``ftol * max(|f_k|, |f_k+1|, 1)``; ``max_outer``
     coordinate steps.  Only ``node_coords_free`` and ``u_free`` change: ``.grad`` of both, the Dirichlet rows and the fixed
     coordinate rows are untouched.  fp32 models: fp64 inside the kernels, coordinates rounded once per trial on write-back (the
-    0.9 margin and ``eta`` absorb the rounding).  QUAD4 models and ``EnergyLoss2D(deterministic=True)`` are refused."""
+    0.9 margin and ``eta`` absorb the rounding).  QUAD4 models and ``EnergyLoss2D(deterministic=True)`` are refused.
+    ``cg_precond`` is the ``precond`` of the inner ``FrozenMeshSolver`` (``"amg"``: the AMG host setup is done once, every
+    coordinate step redoes only its numeric setup)."""
 
     def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None, *,
                  history: int = 10, eta: float = 0.25, quality_weight: float = 0.0, cg_rtol: float = 1e-10,
                  gtol: float = 1e-9, ftol: float = 1e-12, max_outer: int = 50, max_ls: int = 20, c1: float = 1e-4,
-                 max_restarts: int = 5):
+                 max_restarts: int = 5, cg_precond: str = "block_jacobi"):
         _require_tri3(model, "RAdaptiveSolver")
         if getattr(loss_fn, "deterministic", False):
             raise NotImplementedError("RAdaptiveSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
@@ -208,7 +210,8 @@ class RAdaptiveSolver:
         self.history, self.eta, self.quality_weight = int(history), float(eta), float(quality_weight)
         self.gtol, self.ftol, self.max_outer, self.max_ls, self.c1 = float(gtol), float(ftol), int(max_outer), int(max_ls), float(c1)
         self.max_restarts = int(max_restarts)
-        self.solver = FrozenMeshSolver(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol)
+        self.solver = FrozenMeshSolver(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol,
+                                       precond=cg_precond)
         self.last_solve = None                                 # SolveInfo of the latest displacement solve
         x0 = model.initial_node_coords.detach().double()
         self.length = float((x0.max(dim=0).values - x0.min(dim=0).values).norm()) if x0.numel() else 1.0

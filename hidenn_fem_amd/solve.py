@@ -21,6 +21,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -50,7 +51,9 @@ class FrozenMeshSolver:
     """Preconditioned CG for ``model.u_free`` at frozen coordinates (see the module docstring).
 
     ``b_force`` / ``t_force``: the callables ``loss_fn(model, b_force, t_force)`` would take (default forces when None);
-    ``precond``: ``"block_jacobi"`` (2x2 diagonal blocks of K) or ``"none"``; stopping test
+    ``precond``: ``"block_jacobi"`` (2x2 diagonal blocks of K), ``"none"`` or ``"amg"`` (one symmetric V-cycle of smoothed
+    aggregation per iteration, ``csrc/tri3_amg.hip``; its host setup is cached on the model, a refresh redoes only the numeric
+    setup; needs Dirichlet rows; ``solver.amg`` reports the hierarchy); stopping test
     ``||r||_2 <= max(rtol ||f||_2, atol)``; ``max_iter`` None = ``max(1000, 2 x free dofs)``; ``iters_per_graph``: CG
     iterations per graph replay (iterations behind the one that stopped do nothing on the device).
 
@@ -69,8 +72,10 @@ class FrozenMeshSolver:
         if getattr(loss_fn, "deterministic", False):
             raise NotImplementedError("FrozenMeshSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
                                       "(the CG matrix-vector product accumulates with LDS atomics)")
-        if precond not in ("block_jacobi", "none"):
-            raise ValueError("precond must be 'block_jacobi' or 'none'")
+        if precond not in ("block_jacobi", "none", "amg"):
+            raise ValueError("precond must be 'block_jacobi', 'none' or 'amg'")
+        if precond == "amg" and int(model._idx_udir.shape[0]) == 0:
+            raise ValueError("precond='amg' needs Dirichlet rows: without them K_ff and the coarse operator are singular")
         if int(iters_per_graph) < 1:
             raise ValueError("iters_per_graph must be >= 1")
         if rtol < 0 or atol < 0:
@@ -108,6 +113,9 @@ class FrozenMeshSolver:
         self._graph = None
         self._key = None
         self._tables = None
+        self._amg = None
+        if precond == "amg":
+            self._amg = _AmgDevice(amg_host(model), dev, self.phys)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -137,6 +145,8 @@ class FrozenMeshSolver:
         check(_lib.lib().hfem_cg_setup(self._h, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, mat,
                                        float(lf._W), 1 if self.precond == "block_jacobi" else 0, ptr(self.diag),
                                        stream_ptr(dev)), "hfem_cg_setup")
+        if self._amg is not None:
+            self._amg.setup(self._xf, self._xfix, mat, float(lf._W))
         # force tables exactly as EnergyLoss2D builds them (the coordinates are frozen: a position-dependent traction is a
         # constant table here)
         bk = lf._body_table(self.b_force)
@@ -171,8 +181,12 @@ class FrozenMeshSolver:
             self._u.copy_(m.u_free.detach())
             self._gradient(self._u, self._g0)
             self._gradient(self._zero, self._gz)
-            check(L.hfem_cg_start(self._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol, self.max_iter, stream_ptr(dev)),
-                  "hfem_cg_start")
+            if self._amg is None:
+                check(L.hfem_cg_start(self._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol, self.max_iter,
+                                      stream_ptr(dev)), "hfem_cg_start")
+            else:
+                check(L.hfem_cg_start_amg(self._h, self._amg._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol,
+                                          self.max_iter, stream_ptr(dev)), "hfem_cg_start_amg")
             st = self._read_status()
             while not st[10] and st[0] < self.max_iter:
                 self._replay()
@@ -187,8 +201,12 @@ class FrozenMeshSolver:
         if self._graph is None:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):                        # captured, not executed
-                check(_lib.lib().hfem_cg_iterate(self._h, ptr(self._u), self.iters_per_graph, stream_ptr(dev)),
-                      "hfem_cg_iterate")
+                if self._amg is None:
+                    check(_lib.lib().hfem_cg_iterate(self._h, ptr(self._u), self.iters_per_graph, stream_ptr(dev)),
+                          "hfem_cg_iterate")
+                else:
+                    check(_lib.lib().hfem_cg_iterate_amg(self._h, self._amg._h, ptr(self._u), self.iters_per_graph,
+                                                         stream_ptr(dev)), "hfem_cg_iterate_amg")
             self._graph = g
         self._graph.replay()
 
@@ -202,6 +220,157 @@ class FrozenMeshSolver:
         pq = torch.empty((), dtype=F64, device=self.device)
         check(_lib.lib().hfem_cg_apply(self._h, ptr(p), ptr(q), ptr(pq), stream_ptr(self.device)), "hfem_cg_apply")
         return q, pq
+
+
+    @property
+    def amg(self):
+        """The AMG hierarchy (``precond="amg"``; None otherwise): level count, rows and block nnz per level, operator
+        complexity (scalar nnz of all levels over the fine level's), host setup seconds (once per mesh) and the last numeric
+        setup seconds (every refresh; device-synchronised)."""
+        if self._amg is None:
+            return None
+        return self._amg.report()
+
+    def precondition(self, r: torch.Tensor):
+        """``z = M r`` (one V-cycle, ``precond="amg"`` only) over the free u rows; fp64 ``[n_u, 2]`` in storage order.  For
+        tests and measurements."""
+        if self._amg is None:
+            raise ValueError("precondition(): precond='amg' only")
+        if self._key is None or self._key != self._state_key():
+            self.refresh()
+        r = _lib.require_gpu_tensor(r.detach().contiguous(), "r", F64)
+        z = torch.empty_like(r)
+        check(_lib.lib().hfem_amg_vcycle(self._amg._h, ptr(r), ptr(z), stream_ptr(self.device)), "hfem_amg_vcycle")
+        return z
+
+
+class AmgHost:
+    """Host setup of the AMG hierarchy of one mesh (``csrc/amg.cpp``): block pattern, element fan, aggregation and symbolic
+    products of every level.  Depends on the connectivity, the Dirichlet mask and the u row order only (``amg_host``)."""
+
+    def __init__(self, model):
+        conn = np.ascontiguousarray(model.connectivity.detach().cpu().numpy(), dtype=np.int32)
+        xs = np.ascontiguousarray(model._x_src, dtype=np.int32)
+        us = np.ascontiguousarray(model._u_src, dtype=np.int32)
+        h = C.c_void_p()
+        check(_lib.lib().hfem_amg_host_create(conn.ctypes.data, conn.shape[0], xs.shape[0], xs.ctypes.data, us.ctypes.data,
+                                              C.byref(h)), "hfem_amg_host_create")
+        self._h = h
+        top = self.info(-1)
+        self.seconds = top[4] * 1e-9
+        self.levels = [self.info(lvl) for lvl in range(top[0])]
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib().hfem_amg_host_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def info(self, level):
+        out = (C.c_int64 * 8)()
+        check(_lib.lib().hfem_amg_host_info(self._h, level, out), "hfem_amg_host_info")
+        return list(out)
+
+    def array(self, level, which):
+        n = C.c_int64()
+        check(_lib.lib().hfem_amg_host_copy(self._h, level, which, None, C.byref(n)), "hfem_amg_host_copy")
+        out = np.empty(n.value, dtype=np.int32)
+        check(_lib.lib().hfem_amg_host_copy(self._h, level, which, out.ctypes.data, C.byref(n)), "hfem_amg_host_copy")
+        return out
+
+
+def amg_host(model) -> AmgHost:
+    """The model's AMG host setup, built on first use and cached beside its tile plans (topology, Dirichlet mask and row order
+    never change for a model)."""
+    key = ("amg_host",)
+    if key not in model._plans:
+        model._plans[key] = AmgHost(model)
+    return model._plans[key]
+
+
+class _AmgDevice:
+    """Device hierarchy of an ``AmgHost`` (``csrc/tri3_amg.hip``) with the dense coarsest matrix and its inverse (formed by
+    ``torch.linalg`` at setup: not on the cycle's path)."""
+
+    def __init__(self, host, device, phys):
+        self.host, self.device = host, device
+        h = C.c_void_p()
+        check(_lib.lib().hfem_amg_create(_lib.dev_index(device), host._h, HFEM_FLAG_PHYSICAL_GRAD if phys else 0, C.byref(h)),
+              "hfem_amg_create")
+        self._h = h
+        n, bs = host.levels[-1][:2]
+        self.coarse = torch.empty((n * bs, n * bs), dtype=F64, device=device)
+        self.coarse_inv = torch.empty_like(self.coarse)
+        self.setups, self.seconds = 0, 0.0
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.lib().hfem_amg_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def assemble(self, xf, xfix, mat, W):
+        check(_lib.lib().hfem_amg_assemble(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W,
+                                           stream_ptr(self.device)), "hfem_amg_assemble")
+
+    def setup(self, xf, xfix, mat, W):
+        import time
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        check(_lib.lib().hfem_amg_setup(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W, ptr(self.coarse),
+                                        stream_ptr(self.device)), "hfem_amg_setup")
+        inv = torch.linalg.inv(self.coarse)
+        self.coarse_inv.copy_(0.5 * (inv + inv.T))
+        check(_lib.lib().hfem_amg_set_coarse(self._h, ptr(self.coarse_inv)), "hfem_amg_set_coarse")
+        torch.cuda.synchronize(self.device)
+        self.seconds = time.perf_counter() - t0
+        self.setups += 1
+
+    def values(self, level, which):
+        """Device fp64 array ``which`` of a level (hfem_amg_values: 0 A blocks, 1 D^-1, 2 coefficients, 3 near-null space,
+        4 P_tent, 5 P blocks)."""
+        n = C.c_int64()
+        check(_lib.lib().hfem_amg_values(self._h, level, which, None, C.byref(n), None), "hfem_amg_values")
+        out = torch.empty(n.value, dtype=F64, device=self.device)
+        check(_lib.lib().hfem_amg_values(self._h, level, which, ptr(out), C.byref(n), stream_ptr(self.device)),
+              "hfem_amg_values")
+        return out
+
+    def report(self):
+        lv = self.host.levels
+        nnz = [L[2] * L[1] * L[1] for L in lv]
+        return dict(levels=len(lv), rows=[L[0] * L[1] for L in lv], block_rows=[L[0] for L in lv],
+                    block_nnz=[L[2] for L in lv], block_size=[L[1] for L in lv],
+                    operator_complexity=sum(nnz) / nnz[0], host_setup_seconds=self.host.seconds,
+                    numeric_setup_seconds=self.seconds, numeric_setups=self.setups)
+
+
+def assemble_stiffness(model, loss_fn) -> torch.Tensor:
+    """K_ff of the model at its current coordinates: fp64 ``torch.sparse_bsr_tensor`` with 2x2 blocks over the free u rows in
+    storage order (Dirichlet columns dropped), from the AMG assembly kernel (one thread per row, deterministic).  The gradient
+    convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 models only."""
+    if getattr(model, "nodes_per_element", 3) != 3:
+        raise NotImplementedError("assemble_stiffness: TRI3 models only")
+    _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
+    dev = model.u_free.device
+    phys = bool(loss_fn._mode_flags(model) & HFEM_FLAG_PHYSICAL_GRAD)
+    host = amg_host(model)
+    a = _AmgDevice(host, dev, phys)
+    xf = model.node_coords_free.detach().to(F64).contiguous()
+    xfix = model.node_coords_fixed.detach().to(F64).contiguous()
+    a.assemble(xf, xfix, (C.c_double * 4)(*loss_fn._mat), float(loss_fn._W))
+    vals = a.values(0, 0).view(-1, 2, 2).clone()
+    n = host.levels[0][0]
+    i64 = dict(dtype=torch.int64, device=dev)
+    crow = torch.as_tensor(host.array(0, 0), **i64)
+    col = torch.as_tensor(host.array(0, 1), **i64)
+    return torch.sparse_bsr_tensor(crow, col, vals, size=(2 * n, 2 * n))
 
 
 def _paired_plan(model, tile_elems):

@@ -706,6 +706,52 @@ int hfem_tri3_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, c
                                   const float *x_fixed, const float *x_ref, double weight, double *value_acc,
                                   double *grad_acc, void *stream);
 
+/* ------------------------------------------------------------------ smoothed-aggregation AMG for the frozen-mesh solve (TRI3)
+ * A symmetric V-cycle of smoothed aggregation over K_ff in 2x2 node blocks (hidenn_fem_amd/solve.py, precond="amg").
+ * Host setup (amg.cpp, no GPU), once per mesh topology: conn [ne][3] int32, x_src / u_src [nn] the model's row maps (u_src < 0:
+ * a Dirichlet node).  Builds the fine block pattern (diagonal + free neighbours through shared elements, sorted columns), the
+ * node -> element fan with the block slots each corner writes to, the aggregation of every level (SA phases 1-3, no strength
+ * filter, singletons merged into a neighbour's aggregate; until a level has <= 1500 dofs or stops shrinking) and the
+ * symbolic products P = pattern(A) pattern(P_tent), R = P^T, A P and A_c = R A P.  Never reads coordinates.
+ *   host_info   level -1: {levels, n_u, ne, fan entries, host setup ns, 0, 0, 0}; level l: {block rows, block size, A block
+ *               nnz, aggregates (0 on the coarsest), P block nnz, AP block nnz, 0, 0}
+ *   host_copy   *n_out = length of an int32 array, copied into out when out != NULL.  level -1: which 0 fan_ptr, 1 fan
+ *               element, 2 fan corner, 3 fan slots [.][3]; level l: 0 A row_ptr, 1 A columns, 2 A diagonal slot, 3 aggregate
+ *               of each row, 4 P row_ptr, 5 P columns, 6 R row_ptr, 7 R columns (fine rows), 8 R -> P block index,
+ *               9 AP row_ptr, 10 AP columns
+ * Device hierarchy (tri3_amg.hip, fp64), from a host setup (which may be destroyed afterwards):
+ *   assemble    level-0 A values (K_ff, 2x2 blocks, row-major, in the host pattern) at the coordinates x_free / x_fixed (fp64
+ *               rows; mat, W as hfem_cg_setup).  One thread per row, no atomics: bit-deterministic.
+ *   setup       assemble + the numeric hierarchy (block-diagonal inverses, lambda_max(D^-1 A) by power iteration, tentative
+ *               and smoothed prolongators, Galerkin products); writes the coarsest level as a dense row-major N x N matrix
+ *               into coarse_out (an all-zero row gets a 1 on the diagonal).  The caller inverts it and hands the inverse
+ *               over with set_coarse (the pointer must stay valid; it is read by every later cycle).
+ *   vcycle      z = M r over the free u rows (fp64 [n_u][2]); launch-only.
+ *   values      *n_out = length of a device fp64 array of level `level`, copied (device to device) into out when out != NULL:
+ *               which 0 A blocks, 1 D^-1 blocks, 2 coefficients {lambda_hat, 1/theta, c1, c2, omega, ., ., .}, 3 near-null
+ *               space [rows][bs][3], 4 P_tent [rows][bs][3], 5 P blocks [bs][3]
+ * PCG with the V-cycle: cg_start_amg / cg_iterate_amg replace hfem_cg_start / hfem_cg_iterate (same status record, same
+ * halting; hfem_cg_setup still binds the coordinates).  Four launch groups per iteration: apply, vector update, V-cycle,
+ * r^T z.                                                                                                                */
+typedef struct hfem_amg_host hfem_amg_host;
+typedef struct hfem_amg hfem_amg;
+int hfem_amg_host_create(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, const int32_t *u_src,
+                         hfem_amg_host **out);
+int hfem_amg_host_destroy(hfem_amg_host *host);
+int hfem_amg_host_info(const hfem_amg_host *host, int32_t level, int64_t info[8]);
+int hfem_amg_host_copy(const hfem_amg_host *host, int32_t level, int32_t which, int32_t *out, int64_t *n_out);
+int hfem_amg_create(int device, const hfem_amg_host *host, int32_t flags, hfem_amg **out);
+int hfem_amg_destroy(hfem_amg *amg);
+int hfem_amg_assemble(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W, void *stream);
+int hfem_amg_setup(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                   double *coarse_out, void *stream);
+int hfem_amg_set_coarse(hfem_amg *amg, const double *coarse_inv);
+int hfem_amg_vcycle(hfem_amg *amg, const double *r, double *z, void *stream);
+int hfem_amg_values(hfem_amg *amg, int32_t level, int32_t which, double *out, int64_t *n_out, void *stream);
+int hfem_cg_start_amg(hfem_cg *cg, hfem_amg *amg, const double *g0, const double *g_zero, double rtol, double atol,
+                      int64_t max_iter, void *stream);
+int hfem_cg_iterate_amg(hfem_cg *cg, hfem_amg *amg, double *u_free, int32_t n_iter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""AMG-preconditioned frozen-mesh solve at T1M (dev tool): 10^6 TRI3, fp64, default traction, the 1001 x 501 mesh of
+scripts/cg_timing.py (hidenn_fem_amd/solve.py precond="amg", csrc/amg.cpp, csrc/tri3_amg.hip).
+
+Records, as one JSON object: the hierarchy (rows and block nnz per level, operator complexity), the host setup, the numeric
+setup of a refresh (device-synchronised host clock, the coarse inverse included), iterations and wall time to rtol 1e-8
+for AMG (numeric setup included and not) and block Jacobi, one V-cycle and one captured AMG iteration (device events around
+graph replays of the same buffers: cache regime), and iteration counts in both gradient conventions.
+
+    python scripts/amg_timing.py [--grid 1001x501] [--out profiles/amg/amg_timing_T1M.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from hidenn_fem_amd.loss import EnergyLoss2D
+from hidenn_fem_amd.mesh import structured_tri_mesh
+from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+from hidenn_fem_amd.solve import FrozenMeshSolver
+
+F64 = torch.float64
+
+
+def events_us(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1e3 / reps)
+    return sorted(out)[len(out) // 2]
+
+
+def solve_timed(m, lf, precond, refresh_inside):
+    with torch.no_grad():
+        m.u_free.zero_()
+    s = FrozenMeshSolver(m, lf, precond=precond, rtol=1e-8)
+    if not refresh_inside:
+        s.refresh()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if refresh_inside:
+        s.refresh()
+    info = s.solve()
+    torch.cuda.synchronize()
+    return s, dict(iterations=info.iterations, seconds=time.perf_counter() - t0, reason=info.reason,
+                   residual_over_rhs=info.residual_norm / info.rhs_norm)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", default="1001x501")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    nx, ny = (int(v) for v in a.grid.split("x"))
+    coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    torch.manual_seed(0)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
+    lf = EnergyLoss2D(device=dev, dtype=F64)
+    rec = dict(mesh=f"{nx}x{ny} structured, jitter 0.2", n_elems=m.Nelems, n_u_rows=int(m.u_free.shape[0]),
+               regime="cache (back-to-back launches of the same buffers)")
+    solve_timed(m, lf, "amg", True)                       # warm-up: code objects, the host setup, torch.linalg
+    s, rec["amg_with_numeric_setup"] = solve_timed(m, lf, "amg", True)
+    _, rec["amg_setup_done"] = solve_timed(m, lf, "amg", False)
+    _, rec["block_jacobi"] = solve_timed(m, lf, "block_jacobi", False)
+    rec["hierarchy"] = s.amg
+    setups = []
+    for _ in range(5):
+        s.refresh()
+        setups.append(s.amg["numeric_setup_seconds"])
+    rec["numeric_setup_seconds_median"] = sorted(setups)[2]
+    r = torch.randn(m.u_free.shape, dtype=F64, device=dev)
+    rec["vcycle_us"] = events_us(lambda: s.precondition(r), 50)
+    # one captured AMG iteration (rtol 0: never halts while timed)
+    s0 = FrozenMeshSolver(m, lf, precond="amg", rtol=0.0, atol=0.0, max_iter=10 ** 9, iters_per_graph=16)
+    with torch.no_grad():
+        m.u_free.zero_()
+    s0.refresh()
+    from hidenn_fem_amd import _lib
+    with torch.no_grad():
+        s0._u.zero_()
+        s0._gradient(s0._u, s0._g0)
+        s0._gradient(s0._zero, s0._gz)
+    _lib.check(_lib.lib().hfem_cg_start_amg(s0._h, s0._amg._h, s0._g0.data_ptr(), s0._gz.data_ptr(), 0.0, 0.0, 10 ** 9,
+                                            _lib.stream_ptr(dev)), "hfem_cg_start_amg")
+    rec["iteration_graphed_us"] = events_us(s0._replay, 8) / 16
+    conv = {}
+    for c in ("reference", "physical"):
+        m.grad_convention = c
+        conv[c] = solve_timed(m, lf, "amg", True)[1]["iterations"]
+    m.grad_convention = "reference"
+    rec["amg_iterations_by_convention"] = conv
+    bj, am = rec["block_jacobi"]["seconds"], rec["amg_with_numeric_setup"]["seconds"]
+    rec["speedup_over_block_jacobi"] = bj / am
+    rec["bars"] = dict(iterations_le_100=rec["amg_with_numeric_setup"]["iterations"] <= 100, time_le_66ms=am <= 0.066,
+                       speedup_ge_5=bj / am >= 5.0, numeric_setup_le_30ms=rec["numeric_setup_seconds_median"] <= 0.030,
+                       host_setup_le_10s=rec["hierarchy"]["host_setup_seconds"] <= 10.0)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
