@@ -199,6 +199,17 @@ def check(rc: int, what: str = ""):
         raise RuntimeError(f"libhidenn_hip {what} failed (rc={rc}): {msg.decode() if msg else '?'}")
 
 
+def destroy_handle(obj, destroy: str):
+    """``__del__`` of an object that owns a library handle in ``_h``: call ``destroy`` on it if it is still set."""
+    h = getattr(obj, "_h", None)
+    if h is not None and h.value:
+        try:
+            getattr(lib(), destroy)(h)
+        except Exception:       # interpreter shutdown: the library may already be gone
+            pass
+        obj._h = None
+
+
 def require_gpu_tensor(t: torch.Tensor, name: str, dtype=torch.float64):
     """The kernels only run on ROCm device memory; anything else is an error, not a fallback."""
     if not t.is_cuda:

@@ -42,8 +42,10 @@ struct hfem_amg_host {
 struct hfem_amg;   // device hierarchy (tri3_amg.hip)
 
 namespace hfem {
-constexpr int kAmgHaltedIndex = 10;   // status record slot the cycle kernels test (tri3_cg.hip: kHalted)
-// Enqueue z = M r (one V-cycle) on `s`; every launch returns at once when st != nullptr and st[kAmgHaltedIndex] != 0.
+// CG status record (device, and its pinned host mirror; hfem_cg_status): doubles
+enum { kIter = 0, kRnorm, kFnorm, kRho, kReason, kAlpha, kBeta, kPq, kTol, kMaxIter, kHalted, kRtolWins, kStatusN = 16 };
+enum { kRunning = 0, kRtol = 1, kAtol = 2, kMaxIterHit = 3, kBreakdown = 4 };   // st[kReason]
+// Enqueue z = M r (one V-cycle) on `s`; every launch returns at once when st != nullptr and st[kHalted] != 0.
 void amg_cycle(const hfem_amg *a, const double *r, double *z, const double *st, void *s);
 int64_t amg_rows(const hfem_amg *a);
 int amg_device(const hfem_amg *a);

@@ -28,6 +28,9 @@ constexpr int kMaxLocal = 1 << kLocalBits;
 constexpr uint32_t kLocalMask = kMaxLocal - 1;
 constexpr uint32_t kHomeBit = 1u << 30;   // element/edge energy is counted by this tile
 constexpr uint32_t kSkipBit = 1u << 31;   // padding record: the lane has no element
+constexpr uint32_t kHasBBit = 1u << 10;   // elem_pack_hi of a paired slot: a second element B = (n, c, d)
+constexpr uint32_t kHomeBBit = 1u << 11;  // elem_pack_hi: B's energy is counted by this tile
+constexpr uint32_t kChainedBit = 1u << 12;  // elem_pack_hi: the slot's rows of b and c are carried into the next row's slot
 constexpr int32_t kNodeTailPad = 2048;    // records after the last tile's stride (unguarded loads of up to NPT x BLOCK lanes from a tile's start)
 constexpr int32_t kElemTailPad = 4096;    // slot records after the last tile's stride (EPT x BLOCK lanes)
 constexpr int32_t kMaxQuadSlots = 1024;   // element slots per tile the tiled QUAD4 kernel can hold in registers

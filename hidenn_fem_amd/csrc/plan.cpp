@@ -924,7 +924,7 @@ int try_build(const int64_t *conn, int npe, int64_t ne, int64_t nn, const double
                 const std::array<int32_t, 4> &L = items[si];
                 P.elem_pack.push_back((uint32_t)L[0] | ((uint32_t)L[1] << kLocalBits) | ((uint32_t)L[2] << (2 * kLocalBits)) |
                                       (home[ea] == t ? kHomeBit : 0u));
-                P.elem_pack_hi.push_back(eb >= 0 ? ((uint32_t)L[3] | (1u << 10) | (home[eb] == t ? (1u << 11) : 0u) | (chain[si] ? (1u << 12) : 0u)) : 0u);
+                P.elem_pack_hi.push_back(eb >= 0 ? ((uint32_t)L[3] | kHasBBit | (home[eb] == t ? kHomeBBit : 0u) | (chain[si] ? kChainedBit : 0u)) : 0u);
                 P.elem_gid.push_back(ea);
                 P.elem_gid_b.push_back(eb);
                 P.n_pairs += eb >= 0;

@@ -36,7 +36,7 @@ constexpr int kBlock = 256, kRedBlocks = 256;
 // per-level coefficient record (device doubles)
 enum { kLam = 0, kInvTheta, kC1, kC2, kOmega, kScale, kNorm, kCoefN = 8 };
 
-__device__ __forceinline__ bool halted(const double *st) { return st && st[kAmgHaltedIndex] != 0.0; }
+__device__ __forceinline__ bool halted(const double *st) { return st && st[kHalted] != 0.0; }
 
 __device__ __forceinline__ int32_t find_slot(const int32_t *__restrict__ col, int32_t lo, int32_t hi, int32_t key) {
     while (lo < hi) {

@@ -18,8 +18,8 @@
 // Two launches per iteration; every scalar is reduced on the device in a fixed order (bit-reproducible given q; q itself
 // carries the LDS atomics' run-to-run last bits).  Once the status record says halted (converged, max_iter, breakdown) every
 // later launch returns at once: iterations replayed behind the last one do nothing.
-// precond = AMG (hfem_cg_start_amg / hfem_cg_iterate_amg): tri3_cg_vec_amg_kernel (the update without z), the V-cycle of
-// tri3_amg.hip (z = M r) and tri3_cg_rz_kernel (rho = r^T z, beta) replace the vector kernel: four launch groups per iteration.
+// precond = AMG (hfem_cg_start_amg / hfem_cg_iterate_amg): the vector kernel's JACOBI = false instance (the update without z),
+// the V-cycle of tri3_amg.hip (z = M r) and tri3_cg_rz_kernel (rho = r^T z, beta) replace it: four launch groups per iteration.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,11 +34,7 @@
 namespace hfem {
 namespace {
 
-// status record (device, and its pinned host mirror): doubles
-enum { kIter = 0, kRnorm, kFnorm, kRho, kReason, kAlpha, kBeta, kPq, kTol, kMaxIter, kHalted, kRtolWins, kStatusN = 16 };
-enum { kRunning = 0, kRtol = 1, kAtol = 2, kMaxIterHit = 3, kBreakdown = 4 };
 constexpr int kVecBlock = 256, kVecMaxBlocks = 1024;
-static_assert(kHalted == kAmgHaltedIndex, "the AMG cycle kernels test the status record's halted slot");
 
 __device__ __forceinline__ void publish(const double *st, double *host) {
     if (host)
@@ -161,11 +157,11 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_apply_kernel(
                 if (lb < n_owned) add_row(lb, gu[1]);
                 sn = gu[0]; sc = gu[2];
             }
-            if (b & (1u << 10)) {                           // B = (n, c, d)
+            if (b & kHasBBit) {                             // B = (n, c, d)
                 const int ld = (int)(b & kLocalMask);
                 double2 gx[3], gu[3];
                 const double e = tri3_element<true, false, PHYS>(Xn, Xc, nd_xy[ld], Pn, Pc, nd_p[ld], k, gx, gu);
-                if (b & (1u << 11)) e_loc += e;
+                if (b & kHomeBBit) e_loc += e;
                 if (ld < n_owned) add_row(ld, gu[2]);
                 sn.x += gu[0].x; sn.y += gu[0].y; sc.x += gu[1].x; sc.y += gu[1].y;
             }
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_diag_kernel(PlanDev pd, const d
         const int ln = (int)(a & kLocalMask), lb = (int)((a >> kLocalBits) & kLocalMask),
                   lc = (int)((a >> (2 * kLocalBits)) & kLocalMask);
         element(ln, lb, lc);
-        if (b & (1u << 10)) element(ln, lc, (int)(b & kLocalMask));
+        if (b & kHasBBit) element(ln, lc, (int)(b & kLocalMask));
     }
     __syncthreads();
 #pragma unroll
@@ -281,7 +277,45 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_diag_kernel(PlanDev pd, const d
 }
 
 // ---------------------------------------------------------------- vector update + scalars
-template <bool START>
+// Thread 0 of the last workgroup, rho step: beta = rho / rho_old (0 on the first direction), rho; true on a non-finite one.
+__device__ __forceinline__ bool rho_step(double *st, double rho) {
+    const double beta = st[kIter] == 0.0 ? 0.0 : rho / st[kRho];
+    st[kBeta] = beta;
+    st[kRho] = rho;
+    return !isfinite(rho) || !isfinite(beta);
+}
+
+// Residual step: the START reset of the record (|f|, tolerance, max_iter, rtol-wins) or one more iteration, the rho step when
+// this launch also formed rho (JACOBI), |r|, and the halt decision: breakdown before a met tolerance before max_iter.
+template <bool START, bool JACOBI>
+__device__ __forceinline__ void residual_step(double *st, double *host, double rho, double r2, double f2, double rtol,
+                                              double atol, double max_iter) {
+    const double rnorm = sqrt(r2);
+    int reason = kRunning;
+    if (START) {
+        for (int i = 0; i < kStatusN; ++i) st[i] = 0.0;
+        st[kFnorm] = sqrt(f2);
+        st[kTol] = fmax(rtol * st[kFnorm], atol);
+        st[kMaxIter] = max_iter;
+        st[kRtolWins] = rtol * st[kFnorm] >= atol ? 1.0 : 0.0;
+    } else {
+        st[kIter] += 1.0;
+    }
+    const bool bad = JACOBI && rho_step(st, rho);
+    st[kRnorm] = rnorm;
+    if (bad || !isfinite(rnorm)) reason = kBreakdown;
+    else if (rnorm <= st[kTol]) reason = st[kRtolWins] != 0.0 ? kRtol : kAtol;
+    else if (st[kIter] >= st[kMaxIter]) reason = kMaxIterHit;
+    if (reason != kRunning) {
+        st[kHalted] = 1.0;
+        st[kReason] = reason;
+    }
+    publish(st, host);
+}
+
+// JACOBI: the whole update with z = D^-1 r and rho fused.  Otherwise (precond = AMG) the update without z: z = M r comes from
+// the V-cycle after this launch, rho = r^T z and beta from tri3_cg_rz_kernel after that.
+template <bool START, bool JACOBI>
 __global__ __launch_bounds__(kVecBlock) void tri3_cg_vec_kernel(
     int64_t n, double2 *__restrict__ u, double2 *__restrict__ r, double2 *__restrict__ z, const double2 *pbuf0,
     const double2 *pbuf1, const double2 *__restrict__ q, const double *__restrict__ dinv, const double2 *__restrict__ g0,
@@ -312,126 +346,35 @@ __global__ __launch_bounds__(kVecBlock) void tri3_cg_vec_kernel(
             ri.x = __builtin_fma(-alpha, qi.x, ri.x); ri.y = __builtin_fma(-alpha, qi.y, ri.y);
             u[i] = ui;
         }
-        const double d0 = dinv[3 * i], d1 = dinv[3 * i + 1], d2 = dinv[3 * i + 2];
-        const double2 zi = make_double2(d0 * ri.x + d1 * ri.y, d1 * ri.x + d2 * ri.y);
         r[i] = ri;
-        z[i] = zi;
-        rz += ri.x * zi.x + ri.y * zi.y;
-        rr += ri.x * ri.x + ri.y * ri.y;
-    }
-    const double s_rz = block_sum(rz, red);
-    __syncthreads();
-    const double s_rr = block_sum(rr, red);
-    __syncthreads();
-    const double s_ff = START ? block_sum(ff, red) : 0.0;
-    if (tid == 0) {
-        put_partial(part + blockIdx.x, s_rz);
-        put_partial(part + nb + blockIdx.x, s_rr);
-        put_partial(part + 2 * nb + blockIdx.x, s_ff);
-    }
-    if (!last_block(ticket, (unsigned)nb, reinterpret_cast<int *>(red + kVecBlock / 64))) return;
-    const double rho = ordered_sum<kVecBlock>(part, nb, red);
-    __syncthreads();
-    const double r2 = ordered_sum<kVecBlock>(part + nb, nb, red);
-    __syncthreads();
-    const double f2 = START ? ordered_sum<kVecBlock>(part + 2 * nb, nb, red) : 0.0;
-    if (tid != 0) return;
-    const double rnorm = sqrt(r2);
-    int reason = kRunning;
-    if (START) {
-        for (int i = 0; i < kStatusN; ++i) st[i] = 0.0;
-        st[kFnorm] = sqrt(f2);
-        st[kTol] = fmax(rtol * st[kFnorm], atol);
-        st[kMaxIter] = max_iter;
-        st[kRtolWins] = rtol * st[kFnorm] >= atol ? 1.0 : 0.0;
-        st[kBeta] = 0.0;
-    } else {
-        st[kIter] += 1.0;
-        st[kBeta] = rho / st[kRho];
-    }
-    st[kRho] = rho;
-    st[kRnorm] = rnorm;
-    if (!isfinite(rho) || !isfinite(rnorm) || !isfinite(st[kBeta])) reason = kBreakdown;
-    else if (rnorm <= st[kTol]) reason = st[kRtolWins] != 0.0 ? kRtol : kAtol;
-    else if (st[kIter] >= st[kMaxIter]) reason = kMaxIterHit;
-    if (reason != kRunning) {
-        st[kHalted] = 1.0;
-        st[kReason] = reason;
-    }
-    publish(st, host);
-}
-
-// ---------------------------------------------------------------- AMG-preconditioned iteration (tri3_amg.hip cycle)
-// Vector update without the preconditioner: u += alpha p, r -= alpha q, |r|, the stopping test (START: r = -g0, |f|).
-// z = M r comes from the V-cycle after this launch, rho = r^T z and beta from tri3_cg_rz_kernel after that.
-template <bool START>
-__global__ __launch_bounds__(kVecBlock) void tri3_cg_vec_amg_kernel(
-    int64_t n, double2 *__restrict__ u, double2 *__restrict__ r, const double2 *pbuf0, const double2 *pbuf1,
-    const double2 *__restrict__ q, const double2 *__restrict__ g0, const double2 *__restrict__ gzero, double *__restrict__ part,
-    unsigned *ticket, double *st, double *host, double rtol, double atol, double max_iter) {
-    __shared__ double red[kVecBlock / 64 + 1];
-    const int tid = threadIdx.x;
-    const int nb = (int)gridDim.x;
-    if (!START && st[kHalted] != 0.0) return;
-    double alpha = 0.0;
-    const double2 *p = nullptr;
-    if (!START) {
-        alpha = st[kAlpha];
-        p = (((long long)st[kIter]) & 1) ? pbuf0 : pbuf1;
-    }
-    double rr = 0.0, ff = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kVecBlock + tid; i < n; i += (int64_t)nb * kVecBlock) {
-        double2 ri;
-        if (START) {
-            const double2 g = g0[i], h = gzero[i];
-            ri = make_double2(-g.x, -g.y);
-            ff += h.x * h.x + h.y * h.y;
-        } else {
-            const double2 pi = p[i], qi = q[i];
-            double2 ui = u[i];
-            ri = r[i];
-            ui.x = __builtin_fma(alpha, pi.x, ui.x); ui.y = __builtin_fma(alpha, pi.y, ui.y);
-            ri.x = __builtin_fma(-alpha, qi.x, ri.x); ri.y = __builtin_fma(-alpha, qi.y, ri.y);
-            u[i] = ui;
+        if constexpr (JACOBI) {
+            const double d0 = dinv[3 * i], d1 = dinv[3 * i + 1], d2 = dinv[3 * i + 2];
+            const double2 zi = make_double2(d0 * ri.x + d1 * ri.y, d1 * ri.x + d2 * ri.y);
+            z[i] = zi;
+            rz += ri.x * zi.x + ri.y * zi.y;
         }
-        r[i] = ri;
         rr += ri.x * ri.x + ri.y * ri.y;
     }
+    const double s_rz = JACOBI ? block_sum(rz, red) : 0.0;
+    if (JACOBI) __syncthreads();
     const double s_rr = block_sum(rr, red);
     __syncthreads();
     const double s_ff = START ? block_sum(ff, red) : 0.0;
     if (tid == 0) {
+        if constexpr (JACOBI) put_partial(part + blockIdx.x, s_rz);
         put_partial(part + nb + blockIdx.x, s_rr);
         put_partial(part + 2 * nb + blockIdx.x, s_ff);
     }
     if (!last_block(ticket, (unsigned)nb, reinterpret_cast<int *>(red + kVecBlock / 64))) return;
+    const double rho = JACOBI ? ordered_sum<kVecBlock>(part, nb, red) : 0.0;
+    if (JACOBI) __syncthreads();
     const double r2 = ordered_sum<kVecBlock>(part + nb, nb, red);
     __syncthreads();
     const double f2 = START ? ordered_sum<kVecBlock>(part + 2 * nb, nb, red) : 0.0;
-    if (tid != 0) return;
-    const double rnorm = sqrt(r2);
-    int reason = kRunning;
-    if (START) {
-        for (int i = 0; i < kStatusN; ++i) st[i] = 0.0;
-        st[kFnorm] = sqrt(f2);
-        st[kTol] = fmax(rtol * st[kFnorm], atol);
-        st[kMaxIter] = max_iter;
-        st[kRtolWins] = rtol * st[kFnorm] >= atol ? 1.0 : 0.0;
-    } else {
-        st[kIter] += 1.0;
-    }
-    st[kRnorm] = rnorm;
-    if (!isfinite(rnorm)) reason = kBreakdown;
-    else if (rnorm <= st[kTol]) reason = st[kRtolWins] != 0.0 ? kRtol : kAtol;
-    else if (st[kIter] >= st[kMaxIter]) reason = kMaxIterHit;
-    if (reason != kRunning) {
-        st[kHalted] = 1.0;
-        st[kReason] = reason;
-    }
-    publish(st, host);
+    if (tid == 0) residual_step<START, JACOBI>(st, host, rho, r2, f2, rtol, atol, max_iter);
 }
 
-// rho = r^T z in block order, beta = rho / rho_old (0 on the first direction)
+// rho = r^T z in block order, then the rho step
 __global__ __launch_bounds__(kVecBlock) void tri3_cg_rz_kernel(int64_t n, const double2 *__restrict__ r,
                                                                const double2 *__restrict__ z, double *__restrict__ part,
                                                                unsigned *ticket, double *st, double *host) {
@@ -449,10 +392,7 @@ __global__ __launch_bounds__(kVecBlock) void tri3_cg_rz_kernel(int64_t n, const 
     if (!last_block(ticket, (unsigned)nb, reinterpret_cast<int *>(red + kVecBlock / 64))) return;
     const double rho = ordered_sum<kVecBlock>(part, nb, red);
     if (tid != 0) return;
-    const double beta = st[kIter] == 0.0 ? 0.0 : rho / st[kRho];
-    st[kBeta] = beta;
-    st[kRho] = rho;
-    if (!isfinite(rho) || !isfinite(beta)) {
+    if (rho_step(st, rho)) {
         st[kHalted] = 1.0;
         st[kReason] = kBreakdown;
     }
@@ -531,12 +471,52 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
 #undef HFEM_CG_A
 }
 
+void cg_rz(const hfem_cg *c, hipStream_t s) {
+    hipLaunchKernelGGL(hfem::tri3_cg_rz_kernel, dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, c->r, c->z,
+                       c->vec_part, c->tickets + 1, c->st, c->host);
+}
+
+// amg == nullptr: block Jacobi, z and rho fused into the vector launch; otherwise z = M r (the V-cycle) and rho follow it
 template <bool START>
-void cg_vec(const hfem_cg *c, double2 *u, const double2 *g0, const double2 *gzero, double rtol, double atol, double max_iter,
-            hipStream_t s) {
-    hipLaunchKernelGGL((hfem::tri3_cg_vec_kernel<START>), dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, u, c->r,
-                       c->z, c->p[0], c->p[1], c->q, c->dinv, g0, gzero, c->vec_part, c->tickets + 1, c->st, c->host, rtol,
-                       atol, max_iter);
+void cg_vec(const hfem_cg *c, const hfem_amg *amg, double2 *u, const double2 *g0, const double2 *gzero, double rtol, double atol,
+            double max_iter, hipStream_t s) {
+#define HFEM_CG_VEC(J)                                                                                                       \
+    hipLaunchKernelGGL((hfem::tri3_cg_vec_kernel<START, J>), dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, u, c->r, \
+                       c->z, c->p[0], c->p[1], c->q, c->dinv, g0, gzero, c->vec_part, c->tickets + 1, c->st, c->host, rtol,  \
+                       atol, max_iter)
+    if (!amg) HFEM_CG_VEC(true);
+    else {
+        HFEM_CG_VEC(false);
+        hfem::amg_cycle(amg, (const double *)c->r, (double *)c->z, c->st, s);
+        cg_rz(c, s);
+    }
+#undef HFEM_CG_VEC
+}
+
+// The PCG driver behind both pairs of entry points, which check the arguments.
+int cg_start(hfem_cg *c, const hfem_amg *amg, const double *g0, const double *g_zero, double rtol, double atol, int64_t max_iter,
+             hipStream_t s, const char *what) {
+    if (int rc = hfem::use_device(c->device)) return rc;
+    HFEM_HIP_CHECK(hipMemsetAsync(c->p[0], 0, 2 * (size_t)std::max<int64_t>(c->n_u, 1) * 16, s));   // p_old of iteration 0
+    cg_vec<true>(c, amg, nullptr, (const double2 *)g0, (const double2 *)g_zero, rtol, atol, (double)max_iter, s);
+    return hfem::launch_status(what);
+}
+
+int cg_iterate(hfem_cg *c, const hfem_amg *amg, double *u_free, int32_t n_iter, hipStream_t s, const char *what) {
+    if (int rc = hfem::use_device(c->device)) return rc;
+    for (int it = 0; it < n_iter; ++it) {                    // launch-only: capturable in one graph
+        cg_apply(c, c->z, c->q, c->tickets, c->st, c->host, nullptr, s);
+        cg_vec<false>(c, amg, (double2 *)u_free, nullptr, nullptr, 0.0, 0.0, 0.0, s);
+    }
+    return hfem::launch_status(what);
+}
+
+int check_amg(const hfem_cg *c, const hfem_amg *a) {
+    HFEM_ARG_CHECK(c->ready, "hfem_cg_setup has not run");
+    HFEM_ARG_CHECK(hfem::amg_ready(a), "hfem_amg_setup / hfem_amg_set_coarse have not run");
+    HFEM_ARG_CHECK(hfem::amg_rows(a) == c->n_u, "the AMG hierarchy and the CG solve have different free rows");
+    HFEM_ARG_CHECK(hfem::amg_device(a) == c->device, "the AMG hierarchy lives on another device");
+    return 0;
 }
 }  // namespace
 
@@ -623,24 +603,14 @@ extern "C" int hfem_cg_start(hfem_cg *c, const double *g0, const double *g_zero,
     HFEM_ARG_CHECK(c && g0 && g_zero, "null pointer");
     HFEM_ARG_CHECK(c->ready, "hfem_cg_setup has not run");
     HFEM_ARG_CHECK(rtol >= 0.0 && atol >= 0.0 && max_iter >= 0, "rtol, atol and max_iter must be >= 0");
-    if (int rc = hfem::use_device(c->device)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HFEM_HIP_CHECK(hipMemsetAsync(c->p[0], 0, 2 * (size_t)std::max<int64_t>(c->n_u, 1) * 16, s));   // p_old of iteration 0
-    cg_vec<true>(c, nullptr, (const double2 *)g0, (const double2 *)g_zero, rtol, atol, (double)max_iter, s);
-    return hfem::launch_status("hfem_cg_start");
+    return cg_start(c, nullptr, g0, g_zero, rtol, atol, max_iter, (hipStream_t)stream, __func__);
 }
 
 extern "C" int hfem_cg_iterate(hfem_cg *c, double *u_free, int32_t n_iter, void *stream) {
     HFEM_ARG_CHECK(c && (u_free || c->n_u == 0), "null pointer");
     HFEM_ARG_CHECK(c->ready, "hfem_cg_setup has not run");
     HFEM_ARG_CHECK(n_iter >= 0, "n_iter must be >= 0");
-    if (int rc = hfem::use_device(c->device)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    for (int it = 0; it < n_iter; ++it) {                    // launch-only: capturable in one graph
-        cg_apply(c, c->z, c->q, c->tickets, c->st, c->host, nullptr, s);
-        cg_vec<false>(c, (double2 *)u_free, nullptr, nullptr, 0.0, 0.0, 0.0, s);
-    }
-    return hfem::launch_status("hfem_cg_iterate");
+    return cg_iterate(c, nullptr, u_free, n_iter, (hipStream_t)stream, __func__);
 }
 
 extern "C" int hfem_cg_status(hfem_cg *c, double *status_host, void *stream) {
@@ -660,53 +630,17 @@ extern "C" int hfem_cg_apply(hfem_cg *c, const double *p, double *q, double *pq_
 }
 
 // ---------------------------------------------------------------- AMG-preconditioned PCG
-namespace {
-template <bool START>
-void cg_vec_amg(const hfem_cg *c, double2 *u, const double2 *g0, const double2 *gzero, double rtol, double atol, double max_iter,
-                hipStream_t s) {
-    hipLaunchKernelGGL((hfem::tri3_cg_vec_amg_kernel<START>), dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, u, c->r,
-                       c->p[0], c->p[1], c->q, g0, gzero, c->vec_part, c->tickets + 1, c->st, c->host, rtol, atol, max_iter);
-}
-
-void cg_rz(const hfem_cg *c, hipStream_t s) {
-    hipLaunchKernelGGL(hfem::tri3_cg_rz_kernel, dim3(c->vec_blocks), dim3(hfem::kVecBlock), 0, s, c->n_u, c->r, c->z,
-                       c->vec_part, c->tickets + 1, c->st, c->host);
-}
-
-int check_amg(const hfem_cg *c, const hfem_amg *a) {
-    HFEM_ARG_CHECK(c->ready, "hfem_cg_setup has not run");
-    HFEM_ARG_CHECK(hfem::amg_ready(a), "hfem_amg_setup / hfem_amg_set_coarse have not run");
-    HFEM_ARG_CHECK(hfem::amg_rows(a) == c->n_u, "the AMG hierarchy and the CG solve have different free rows");
-    HFEM_ARG_CHECK(hfem::amg_device(a) == c->device, "the AMG hierarchy lives on another device");
-    return 0;
-}
-}  // namespace
-
 extern "C" int hfem_cg_start_amg(hfem_cg *c, hfem_amg *amg, const double *g0, const double *g_zero, double rtol, double atol,
                                  int64_t max_iter, void *stream) {
     HFEM_ARG_CHECK(c && amg && g0 && g_zero, "null pointer");
     if (int rc = check_amg(c, amg)) return rc;
     HFEM_ARG_CHECK(rtol >= 0.0 && atol >= 0.0 && max_iter >= 0, "rtol, atol and max_iter must be >= 0");
-    if (int rc = hfem::use_device(c->device)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HFEM_HIP_CHECK(hipMemsetAsync(c->p[0], 0, 2 * (size_t)std::max<int64_t>(c->n_u, 1) * 16, s));
-    cg_vec_amg<true>(c, nullptr, (const double2 *)g0, (const double2 *)g_zero, rtol, atol, (double)max_iter, s);
-    hfem::amg_cycle(amg, (const double *)c->r, (double *)c->z, c->st, s);
-    cg_rz(c, s);
-    return hfem::launch_status("hfem_cg_start_amg");
+    return cg_start(c, amg, g0, g_zero, rtol, atol, max_iter, (hipStream_t)stream, __func__);
 }
 
 extern "C" int hfem_cg_iterate_amg(hfem_cg *c, hfem_amg *amg, double *u_free, int32_t n_iter, void *stream) {
     HFEM_ARG_CHECK(c && amg && (u_free || c->n_u == 0), "null pointer");
     if (int rc = check_amg(c, amg)) return rc;
     HFEM_ARG_CHECK(n_iter >= 0, "n_iter must be >= 0");
-    if (int rc = hfem::use_device(c->device)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    for (int it = 0; it < n_iter; ++it) {                    // launch-only: capturable in one graph
-        cg_apply(c, c->z, c->q, c->tickets, c->st, c->host, nullptr, s);
-        cg_vec_amg<false>(c, (double2 *)u_free, nullptr, nullptr, 0.0, 0.0, 0.0, s);
-        hfem::amg_cycle(amg, (const double *)c->r, (double *)c->z, c->st, s);
-        cg_rz(c, s);
-    }
-    return hfem::launch_status("hfem_cg_iterate_amg");
+    return cg_iterate(c, amg, u_free, n_iter, (hipStream_t)stream, __func__);
 }

@@ -162,11 +162,11 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
                 if (lb < n_owned) add_row(lb, gx[1], gu[1]);
                 sxn = gx[0]; sun = gu[0]; sxc = gx[2]; suc = gu[2];
             }
-            if (q & (1u << 10)) {                       // B = (n, c, d)
+            if (q & kHasBBit) {                         // B = (n, c, d)
                 const int ld = (int)(q & kLocalMask);
                 double2 gx[3], gu[3];
                 const double e = tri3_element<true, HASB, PHYS>(Xn, Xc, nd_xy[ld], Un, Uc, nd_uv[ld], k, gx, gu);
-                if (q & (1u << 11)) e_loc += e;
+                if (q & kHomeBBit) e_loc += e;
                 if (ld < n_owned) add_row(ld, gx[2], gu[2]);
                 sxn.x += gx[0].x; sxn.y += gx[0].y; sun.x += gu[0].x; sun.y += gu[0].y;
                 sxc.x += gx[1].x; sxc.y += gx[1].y; suc.x += gu[1].x; suc.y += gu[1].y;
@@ -192,13 +192,13 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
             if (kCarryVals && j > 0 && chained) { Xn = pXb; Un = pUb; } else { Xn = nd_xy[ln]; Un = nd_uv[ln]; }
             const double2 Xc = nd_xy[lc], Uc = nd_uv[lc];
             double2 sxn = make_double2(0.0, 0.0), sun = sxn, sxc = sxn, suc = sxn;   // running rows of the shared nodes n and c
-            if (q & (1u << 10)) {                       // B = (n, c, d) first: the carried rows and node values die here
+            if (q & kHasBBit) {                         // B = (n, c, d) first: the carried rows and node values die here
                 const int ld = (int)(q & kLocalMask);
                 double2 Xd, Ud;
                 if (kCarryVals && j > 0 && chained) { Xd = pXc; Ud = pUc; } else { Xd = nd_xy[ld]; Ud = nd_uv[ld]; }
                 double2 gx[3], gu[3];
                 const double e = tri3_element<true, HASB, PHYS>(Xn, Xc, Xd, Un, Uc, Ud, k, gx, gu);
-                if (q & (1u << 11)) e_loc += e;
+                if (q & kHomeBBit) e_loc += e;
                 if (j > 0 && chained) {
                     gx[0].x += kxb.x; gx[0].y += kxb.y; gu[0].x += kub.x; gu[0].y += kub.y;
                     gx[2].x += kxc.x; gx[2].y += kxc.y; gu[2].x += kuc.x; gu[2].y += kuc.y;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
                 sxn.x += gx[0].x; sxn.y += gx[0].y; sun.x += gu[0].x; sun.y += gu[0].y;
                 sxc.x += gx[2].x; sxc.y += gx[2].y; suc.x += gu[2].x; suc.y += gu[2].y;
                 if (ln < n_owned) add_row(ln, sxn, sun);
-                chained = (q & (1u << 12)) != 0;
+                chained = (q & kChainedBit) != 0;
                 if (j + 1 < EPT && chained) {
                     kxb = gx[1]; kub = gu[1]; kxc = sxc; kuc = suc;
                     if (kCarryVals) { pXb = Xb; pUb = Ub; pXc = Xc; pUc = Uc; }

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 3 : (ADAM && EPT > 4 ? 4 : 5)
         if (!(p & kSkipBit)) {
             const int ln = (int)(p & kLocalMask), lb = (int)((p >> kLocalBits) & kLocalMask),
                       lc = (int)((p >> (2 * kLocalBits)) & kLocalMask);
-            const bool hasB = (q & (1u << 10)) != 0;
+            const bool hasB = (q & kHasBBit) != 0;
             const int ld = hasB ? (int)(q & kLocalMask) : lb;      // no partner: the B half re-evaluates (n, c, b) -- finite, unused
             const float4 Nn = nd[ln], Nb = nd[lb], Nc = nd[lc], Nd = nd[ld];
             f2 gxx[3], gxy[3], gux[3], guy[3];
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 3 : (ADAM && EPT > 4 ? 4 : 5)
                 k, gxx, gxy, gux, guy);
             const float mB = hasB ? 1.0f : 0.0f;                   // B's half is finite either way: a multiply masks it
             if (p & kHomeBit) e_loc += (double)e.x;
-            if (q & (1u << 11)) e_loc += (double)e.y;
+            if (q & kHomeBBit) e_loc += (double)e.y;
             if (lb < n_owned) add_row(lb, gxx[1].x, gxy[1].x, gux[1].x, guy[1].x);
             if (hasB && ld < n_owned) add_row(ld, gxx[2].y, gxy[2].y, gux[2].y, guy[2].y);
             if (ln < n_owned)

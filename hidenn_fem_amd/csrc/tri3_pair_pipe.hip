@@ -155,11 +155,11 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_pipe_kernel(
                     if (lb < n_owned) add_row(lb, gx[1], gu[1]);
                     sxn = gx[0]; sun = gu[0]; sxc = gx[2]; suc = gu[2];
                 }
-                if (q & (1u << 10)) {                   // B = (n, c, d)
+                if (q & kHasBBit) {                     // B = (n, c, d)
                     const int ld = (int)(q & kLocalMask);
                     double2 gx[3], gu[3];
                     const double e = tri3_element<true, false, false>(Xn, Xc, nd_xy[ld], Un, Uc, nd_uv[ld], k, gx, gu);
-                    if (q & (1u << 11)) e_loc += e;
+                    if (q & kHomeBBit) e_loc += e;
                     if (ld < n_owned) add_row(ld, gx[2], gu[2]);
                     sxn.x += gx[0].x; sxn.y += gx[0].y; sun.x += gu[0].x; sun.y += gu[0].y;
                     sxc.x += gx[1].x; sxc.y += gx[1].y; suc.x += gu[1].x; suc.y += gu[1].y;

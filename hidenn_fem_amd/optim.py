@@ -332,12 +332,7 @@ class FusedLBFGS(torch.optim.Optimizer):
         caller_order_hooks(self)
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                _lib.lib().hfem_lbfgs_destroy(self._h)
-                self._h = None
-        except Exception:       # interpreter shutdown: the library may already be gone
-            pass
+        _lib.destroy_handle(self, "hfem_lbfgs_destroy")
 
     def _handle(self):
         if self._h is None:
@@ -484,12 +479,7 @@ class ShardedLBFGS:
         self.state = dict(func_evals=0, n_iter=0)
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.lib().hfem_lbfgs_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        _lib.destroy_handle(self, "hfem_lbfgs_destroy")
 
     def _evaluate(self):
         """Interface rows of the parameters in, then the energy over this rank's tiles: the gradient of the owned rows into the

@@ -32,6 +32,7 @@ HFEM_FLAG_NO_GX = 1
 HFEM_FLAG_NO_EDGES = 4
 HFEM_FLAG_PHYSICAL_GRAD = 64
 _REASONS = {1: "rtol", 2: "atol", 3: "max_iter", 4: "breakdown"}
+ST_ITER, ST_RNORM, ST_FNORM, ST_REASON, ST_HALTED = 0, 1, 2, 4, 10     # hfem_cg_status slots (csrc/hfem_amg.h: kIter ...)
 
 
 @dataclass
@@ -118,13 +119,7 @@ class FrozenMeshSolver:
             self._amg = _AmgDevice(amg_host(model), dev, self.phys)
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().hfem_cg_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        _lib.destroy_handle(self, "hfem_cg_destroy")
 
     # ---- what the right-hand side and K depend on
     def _state_key(self):
@@ -171,42 +166,45 @@ class FrozenMeshSolver:
         check(_lib.lib().hfem_cg_status(self._h, self._status, stream_ptr(self.device)), "hfem_cg_status")
         return list(self._status)
 
+    def _start(self, rtol, atol, max_iter):
+        """r = -g0, z = M r, rho, |f| and the stopping rule from ``self._g0`` / ``self._gz``: the record of iteration 0."""
+        args = (ptr(self._g0), ptr(self._gz), rtol, atol, max_iter, stream_ptr(self.device))
+        if self._amg is None:
+            check(_lib.lib().hfem_cg_start(self._h, *args), "hfem_cg_start")
+        else:
+            check(_lib.lib().hfem_cg_start_amg(self._h, self._amg._h, *args), "hfem_cg_start_amg")
+
+    def _iterate(self):
+        """Enqueue ``iters_per_graph`` iterations on ``self._u`` (launches only: capturable)."""
+        args = (ptr(self._u), self.iters_per_graph, stream_ptr(self.device))
+        if self._amg is None:
+            check(_lib.lib().hfem_cg_iterate(self._h, *args), "hfem_cg_iterate")
+        else:
+            check(_lib.lib().hfem_cg_iterate_amg(self._h, self._amg._h, *args), "hfem_cg_iterate_amg")
+
     def solve(self) -> SolveInfo:
         m = self.model
         if self._key is None or self._key != self._state_key():
             self.refresh()
-        dev = self.device
-        L = _lib.lib()
         with torch.no_grad():
             self._u.copy_(m.u_free.detach())
             self._gradient(self._u, self._g0)
             self._gradient(self._zero, self._gz)
-            if self._amg is None:
-                check(L.hfem_cg_start(self._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol, self.max_iter,
-                                      stream_ptr(dev)), "hfem_cg_start")
-            else:
-                check(L.hfem_cg_start_amg(self._h, self._amg._h, ptr(self._g0), ptr(self._gz), self.rtol, self.atol,
-                                          self.max_iter, stream_ptr(dev)), "hfem_cg_start_amg")
+            self._start(self.rtol, self.atol, self.max_iter)
             st = self._read_status()
-            while not st[10] and st[0] < self.max_iter:
+            while not st[ST_HALTED] and st[ST_ITER] < self.max_iter:
                 self._replay()
                 st = self._read_status()
             m.u_free.copy_(self._u)                          # rounds once for fp32 models
-        reason = _REASONS.get(int(st[4]), "max_iter")
-        return SolveInfo(iterations=int(st[0]), residual_norm=float(st[1]), rhs_norm=float(st[2]),
+        reason = _REASONS.get(int(st[ST_REASON]), "max_iter")
+        return SolveInfo(iterations=int(st[ST_ITER]), residual_norm=float(st[ST_RNORM]), rhs_norm=float(st[ST_FNORM]),
                          converged=reason in ("rtol", "atol"), reason=reason)
 
     def _replay(self):
-        dev = self.device
         if self._graph is None:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):                        # captured, not executed
-                if self._amg is None:
-                    check(_lib.lib().hfem_cg_iterate(self._h, ptr(self._u), self.iters_per_graph, stream_ptr(dev)),
-                          "hfem_cg_iterate")
-                else:
-                    check(_lib.lib().hfem_cg_iterate_amg(self._h, self._amg._h, ptr(self._u), self.iters_per_graph,
-                                                         stream_ptr(dev)), "hfem_cg_iterate_amg")
+                self._iterate()
             self._graph = g
         self._graph.replay()
 
@@ -261,13 +259,7 @@ class AmgHost:
         self.levels = [self.info(lvl) for lvl in range(top[0])]
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().hfem_amg_host_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        _lib.destroy_handle(self, "hfem_amg_host_destroy")
 
     def info(self, level):
         out = (C.c_int64 * 8)()
@@ -307,13 +299,7 @@ class _AmgDevice:
         self.setups, self.seconds = 0, 0.0
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                _lib.lib().hfem_amg_destroy(h)
-            except Exception:
-                pass
-            self._h = None
+        _lib.destroy_handle(self, "hfem_amg_destroy")
 
     def assemble(self, xf, xfix, mat, W):
         check(_lib.lib().hfem_amg_assemble(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W,

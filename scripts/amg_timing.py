@@ -88,13 +88,11 @@ def main():
     with torch.no_grad():
         m.u_free.zero_()
     s0.refresh()
-    from hidenn_fem_amd import _lib
     with torch.no_grad():
         s0._u.zero_()
         s0._gradient(s0._u, s0._g0)
         s0._gradient(s0._zero, s0._gz)
-    _lib.check(_lib.lib().hfem_cg_start_amg(s0._h, s0._amg._h, s0._g0.data_ptr(), s0._gz.data_ptr(), 0.0, 0.0, 10 ** 9,
-                                            _lib.stream_ptr(dev)), "hfem_cg_start_amg")
+    s0._start(0.0, 0.0, 10 ** 9)
     rec["iteration_graphed_us"] = events_us(s0._replay, 8) / 16
     conv = {}
     for c in ("reference", "physical"):

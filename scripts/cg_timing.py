@@ -84,7 +84,6 @@ def main():
     p = torch.randn(m.u_free.shape, dtype=F64, device=dev) * 1e-4
     q, pq = torch.empty_like(p), torch.empty((), dtype=F64, device=dev)
     L = _lib.lib()
-    st = _lib.stream_ptr(dev)
     apply_one = lambda: L.hfem_cg_apply(s._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), _lib.stream_ptr(dev))
     apply_host_us = events_us(apply_one, a.reps)
     apply_us = graphed_us(apply_one, a.reps)
@@ -103,7 +102,7 @@ def main():
         s0._u.copy_(u_init)
         s0._gradient(s0._u, s0._g0)
         s0._gradient(s0._zero, s0._gz)
-    _lib.check(L.hfem_cg_start(s0._h, s0._g0.data_ptr(), s0._gz.data_ptr(), 0.0, 0.0, 10 ** 9, st), "hfem_cg_start")
+    s0._start(0.0, 0.0, 10 ** 9)
     it_us = events_us(s0._replay, max(a.reps // 16, 4)) / 16
     rec["iteration_graphed"] = dict(us=it_us, iters_per_graph=16, launches_per_iteration=2)
 
