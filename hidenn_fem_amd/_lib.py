@@ -151,6 +151,7 @@ PROTOTYPES = {
     "hfem_tri3_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_tri3_quality_barrier": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp]),
     "hfem_amg_host_create": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_vp)]),
+    "hfem_amg_host_create_ex": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_vp)]),
     "hfem_amg_host_destroy": (C.c_int, [_vp]),
     "hfem_amg_host_info": (C.c_int, [_vp, _i32, _vp]),
     "hfem_amg_host_copy": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),

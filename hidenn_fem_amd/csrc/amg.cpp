@@ -1,5 +1,5 @@
 // Smoothed-aggregation AMG, host setup (no GPU): the fine 2x2 block pattern of K_ff with the node -> element fan that the
-// assembly kernel walks, the aggregation of every level (SA phases 1-3, no strength filter, singletons merged), and the
+// assembly kernel walks (npe corners per element: 3 for TRI3, 4 for QUAD4, whose diagonal partners are neighbours too), the aggregation of every level (SA phases 1-3, no strength filter, singletons merged), and the
 // symbolic products P = pattern(A) pattern(P_tent), R = P^T (explicit transpose map), A P and A_c = R (A P).  Everything here
 // depends on the connectivity, the Dirichlet mask and the u row map only; the numeric setup (tri3_amg.hip) redoes the values
 // whenever the coordinates move.  Rows of every pattern are sorted, so a numeric kernel finds its output slot by binary search.
@@ -129,8 +129,8 @@ void diag_slots(AmgLevel &L) {
     }
 }
 
-int build(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, const int32_t *u_src, hfem_amg_host &h) {
-    h.ne = ne; h.nn = nn;
+int build(const int32_t *conn, int64_t ne, int npe, int64_t nn, const int32_t *x_src, const int32_t *u_src, hfem_amg_host &h) {
+    h.ne = ne; h.nn = nn; h.npe = npe;
     int64_t n_u = 0;
     for (int64_t v = 0; v < nn; ++v) n_u += u_src[v] >= 0;
     if (n_u >= ((int64_t)1 << 30)) { hfem::set_error("hfem_amg_host_create: too many free rows"); return -1; }
@@ -144,26 +144,26 @@ int build(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, con
     }
     h.row_x.resize((size_t)n_u);
     for (int32_t r = 0; r < n_u; ++r) h.row_x[r] = x_src[row_node[r]];
-    h.conn_x.resize((size_t)ne * 3);
+    h.conn_x.resize((size_t)ne * npe);
     for (int64_t e = 0; e < ne; ++e)
-        for (int a = 0; a < 3; ++a) {
-            const int32_t v = conn[3 * e + a];
+        for (int a = 0; a < npe; ++a) {
+            const int32_t v = conn[npe * e + a];
             if (v < 0 || v >= nn) { hfem::set_error("hfem_amg_host_create: connectivity out of range"); return -1; }
-            h.conn_x[3 * e + a] = x_src[v];
+            h.conn_x[npe * e + a] = x_src[v];
         }
     // node -> element fan of every free row (element ascending)
     h.fan_ptr.assign((size_t)n_u + 1, 0);
     for (int64_t e = 0; e < ne; ++e)
-        for (int a = 0; a < 3; ++a)
-            if (u_src[conn[3 * e + a]] >= 0) ++h.fan_ptr[u_src[conn[3 * e + a]] + 1];
+        for (int a = 0; a < npe; ++a)
+            if (u_src[conn[npe * e + a]] >= 0) ++h.fan_ptr[u_src[conn[npe * e + a]] + 1];
     for (int32_t r = 0; r < n_u; ++r) h.fan_ptr[r + 1] += h.fan_ptr[r];
     const size_t nf = (size_t)h.fan_ptr[n_u];
-    h.fan_elem.resize(nf); h.fan_corner.resize(nf); h.fan_slot.resize(3 * nf);
+    h.fan_elem.resize(nf); h.fan_corner.resize(nf); h.fan_slot.resize((size_t)npe * nf);
     {
         std::vector<int32_t> fill(h.fan_ptr.begin(), h.fan_ptr.end() - 1);
         for (int64_t e = 0; e < ne; ++e)
-            for (int a = 0; a < 3; ++a) {
-                const int32_t r = u_src[conn[3 * e + a]];
+            for (int a = 0; a < npe; ++a) {
+                const int32_t r = u_src[conn[npe * e + a]];
                 if (r < 0) continue;
                 const int32_t f = fill[r]++;
                 h.fan_elem[f] = (int32_t)e;
@@ -180,8 +180,8 @@ int build(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, con
     for (int32_t r = 0; r < n_u; ++r) {
         row.assign(1, r);
         for (int32_t f = h.fan_ptr[r]; f < h.fan_ptr[r + 1]; ++f)
-            for (int b = 0; b < 3; ++b) {
-                const int32_t c = u_src[conn[3 * (int64_t)h.fan_elem[f] + b]];
+            for (int b = 0; b < npe; ++b) {
+                const int32_t c = u_src[conn[npe * (int64_t)h.fan_elem[f] + b]];
                 if (c >= 0) row.push_back(c);
             }
         std::sort(row.begin(), row.end());
@@ -189,9 +189,9 @@ int build(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, con
         L0.a_col.insert(L0.a_col.end(), row.begin(), row.end());
         L0.a_ptr[r + 1] = (int32_t)L0.a_col.size();
         for (int32_t f = h.fan_ptr[r]; f < h.fan_ptr[r + 1]; ++f)
-            for (int b = 0; b < 3; ++b) {
-                const int32_t c = u_src[conn[3 * (int64_t)h.fan_elem[f] + b]];
-                h.fan_slot[3 * (size_t)f + b] =
+            for (int b = 0; b < npe; ++b) {
+                const int32_t c = u_src[conn[npe * (int64_t)h.fan_elem[f] + b]];
+                h.fan_slot[(size_t)npe * f + b] =
                     c < 0 ? -1 : (int32_t)(std::lower_bound(L0.a_col.begin() + L0.a_ptr[r], L0.a_col.end(), c) - L0.a_col.begin());
             }
     }
@@ -243,15 +243,21 @@ const std::vector<int32_t> *array_of(const hfem_amg_host *h, int32_t level, int3
 
 extern "C" int hfem_amg_host_create(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, const int32_t *u_src,
                                     hfem_amg_host **out) {
+    return hfem_amg_host_create_ex(conn, ne, 3, nn, x_src, u_src, out);
+}
+
+extern "C" int hfem_amg_host_create_ex(const int32_t *conn, int64_t ne, int32_t npe, int64_t nn, const int32_t *x_src,
+                                       const int32_t *u_src, hfem_amg_host **out) {
     HFEM_ARG_CHECK(out, "null pointer");
     *out = nullptr;
     HFEM_ARG_CHECK(x_src && u_src && (conn || ne == 0), "null pointer");
+    HFEM_ARG_CHECK(npe == 3 || npe == 4, "npe: 3 (TRI3) or 4 (QUAD4)");
     HFEM_ARG_CHECK(ne >= 0 && nn > 0 && ne < ((int64_t)1 << 31) && nn < ((int64_t)1 << 31), "ne / nn out of range");
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<hfem_amg_host> h(new (std::nothrow) hfem_amg_host);
     HFEM_ARG_CHECK(h != nullptr, "out of memory");
     try {
-        if (build(conn, ne, nn, x_src, u_src, *h)) return -1;
+        if (build(conn, ne, npe, nn, x_src, u_src, *h)) return -1;
     } catch (const std::exception &e) {
         hfem::set_error(std::string("hfem_amg_host_create: ") + e.what());
         return -1;
@@ -277,6 +283,7 @@ extern "C" int hfem_amg_host_info(const hfem_amg_host *h, int32_t level, int64_t
         info[2] = h->ne;
         info[3] = h->fan_ptr.back();
         info[4] = (int64_t)(h->seconds * 1e9);
+        info[5] = h->npe;
         return 0;
     }
     const AmgLevel &L = h->levels[level];

@@ -26,6 +26,7 @@
 #include <string>
 
 #include "hfem_amg.h"
+#include "hfem_cg_dev.h"
 #include "hfem_device.h"
 #include "hfem_plan_dev.h"
 
@@ -559,7 +560,7 @@ struct DevLevel {
 struct hfem_amg {
     int device = -1;
     bool phys = false;
-    int32_t n_u = 0;
+    int32_t n_u = 0, npe = 3;              // npe: corners per element of the fine level's fan (3 TRI3, 4 QUAD4)
     int32_t *fan_ptr = nullptr, *fan_elem = nullptr, *fan_corner = nullptr, *fan_slot = nullptr, *conn_x = nullptr,
             *row_x = nullptr;
     std::vector<DevLevel> lv;
@@ -661,6 +662,11 @@ hfem::Tri3Consts consts(const double mat[4], double W) { return hfem::make_const
 
 void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, hipStream_t s) {
     const DevLevel &L = a->lv[0];
+    if (a->npe == 4) {                                       // QUAD4 fan (quad4_cg.hip); the 2x2 rule's weights are 1: W is not read
+        hfem::launch_quad4_amg_assemble(L.n, a->fan_ptr, a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free,
+                                        (const double2 *)x_fixed, L.a_ptr, L.a_val, consts(mat, 1.0), a->phys, s);
+        return;
+    }
     const hfem::Tri3Consts k = consts(mat, W);
 #define HFEM_AMG_ASM(PH)                                                                                                      \
     hipLaunchKernelGGL(hfem::amg_assemble_kernel<PH>, grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr, a->fan_elem,         \
@@ -719,7 +725,7 @@ extern "C" int hfem_amg_create(int device, const hfem_amg_host *host, int32_t fl
                    "the coarsest level is too large for a dense solve (the mesh graph does not coarsen)");
     if (int rc = hfem::use_device(device)) return rc;
     std::unique_ptr<hfem_amg> a(new hfem_amg);
-    a->device = device; a->phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0; a->n_u = host->n_u;
+    a->device = device; a->phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0; a->n_u = host->n_u; a->npe = host->npe;
     if (create(a.get(), host)) {
         release(a.get());
         return -1;

@@ -1,5 +1,7 @@
 // Frozen-mesh displacement solve on TRI3, gfx950 (MI355X): matrix-free preconditioned conjugate gradients over the paired
-// owner-computes tile plan (hidenn_fem_amd/solve.py).
+// owner-computes tile plan (hidenn_fem_amd/solve.py).  The PCG driver at the end of this file also runs QUAD4 plans: the
+// vector kernels, the status record and the halt logic know nothing of the element, and the two element kernels of a QUAD4
+// solve (apply, block diagonal) are quad4_cg.hip's, reached through hfem_cg_dev.h.
 //
 // At fixed coordinates the total potential is exactly quadratic in u: E(u) = 1/2 u^T K u - f^T u.  So K p is the u-half of
 // the energy gradient at u = p with no forces (tri3_element<GRAD, HASB = false>: the same closed forms, both gradient
@@ -28,6 +30,7 @@
 #include <string>
 
 #include "hfem_amg.h"
+#include "hfem_cg_dev.h"
 #include "hfem_device.h"
 #include "hfem_plan_dev.h"
 
@@ -35,43 +38,6 @@ namespace hfem {
 namespace {
 
 constexpr int kVecBlock = 256, kVecMaxBlocks = 1024;
-
-__device__ __forceinline__ void publish(const double *st, double *host) {
-    if (host)
-        for (int i = 0; i < kStatusN; ++i) host[i] = st[i];
-}
-
-// The last-workgroup hand-off (cdna_hip_programming.md section 6, Guideline 16, write-through form): every partial is stored
-// with put_partial (agent-scope relaxed store: write-through, no release fence -- a release in every workgroup writes back its
-// XCD's L2 under the running tiles), every wave drains its stores, lane 0 takes a relaxed agent-scope ticket; the workgroup
-// that draws n - 1 is the reducer and reads the partials with agent-scope loads (get_partial).  `flag` is one word of the
-// block's own LDS array.  Returns true in every thread of the last block.
-__device__ __forceinline__ void put_partial(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double get_partial(const double *p) {
-    return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool last_block(unsigned *ticket, unsigned n, int *flag) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0): this wave's stores have been acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = t == n - 1;
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-        *flag = last;
-    }
-    __syncthreads();
-    return *flag != 0;
-}
-
-// Fixed-order sum of the n partials by one block (strided lanes, then block_sum's wave order).  Result in thread 0.
-template <int BLOCK>
-__device__ __forceinline__ double ordered_sum(const double *v, int n, double *red) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += BLOCK) a += get_partial(v + i);
-    __syncthreads();                                        // red[] may still be read by the caller's earlier reduction
-    return block_sum(a, red);
-}
 
 // ---------------------------------------------------------------- q = K p
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
@@ -408,7 +374,7 @@ struct hfem_cg {
     int device = -1;
     int64_t n_u = 0;
     int n_tiles = 0, block = 256, vec_blocks = 1;
-    bool phys = false;
+    bool phys = false, quad = false;   // quad: a QUAD4 plan (one element per slot; kernels of quad4_cg.hip)
     size_t lds_apply = 0, lds_diag = 0;
     // device memory, one allocation: p[2], r, z, q (double2 rows), dinv (3 doubles per row), tile partials, vector partials,
     // status record, tickets
@@ -452,11 +418,22 @@ void launch_diag(const hfem_cg *c, double *diag, int precond, hipStream_t s) {
 #undef HFEM_CG_DIAG
 }
 
+hfem::Quad4CgArgs quad4_args(const hfem_cg *c, size_t lds, hipStream_t s) {
+    hfem::Quad4CgArgs A;
+    A.plan = c->plan; A.n_tiles = c->n_tiles; A.phys = c->phys; A.x_free = c->x_free; A.x_fixed = c->x_fixed; A.k = c->k;
+    A.lds = lds; A.s = s;
+    return A;
+}
+
 // the tile shapes of a paired plan: 512 threads (2 nodes and 2 slot rows per thread), or 256 threads with 3 | 4 nodes and
 // 3 | 4 | 6 slot rows per thread (the pair kernel's matrix: a masked row or node costs a full pass of the slot loop)
 void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, double *st, double *host, double *pq_out,
               hipStream_t s) {
     const hfem::HostPlan &h = c->plan->host;
+    if (c->quad) {
+        hfem::launch_quad4_cg_apply(quad4_args(c, c->lds_apply, s), z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+        return;
+    }
 #define HFEM_CG_A(NPT, EPT) launch_apply<256, NPT, EPT>(c, z, q, ticket, st, host, pq_out, s)
     if (c->block == 512) launch_apply<512, 2, 2>(c, z, q, ticket, st, host, pq_out, s);
     else if (h.max_nodes <= 3 * 256) {
@@ -525,18 +502,24 @@ extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_
     *out = nullptr;
     HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
     const hfem::HostPlan &h = plan->host;
-    HFEM_ARG_CHECK(h.npe == 3, "QUAD4 plan: the CG solve is TRI3 only");
-    HFEM_ARG_CHECK(h.paired && plan->d_elem_pack_hi && h.n_chained == 0, "the CG solve needs a paired-slot plan (plan_elem_order 5)");
+    const bool quad = h.npe == 4;                            // QUAD4: the model's own plan, one element per slot, no pairing
+    HFEM_ARG_CHECK(quad || (h.paired && plan->d_elem_pack_hi && h.n_chained == 0),
+                   "the CG solve needs a paired-slot plan (plan_elem_order 5)");
+    HFEM_ARG_CHECK(!quad || plan->d_elem_pack_hi, "QUAD4 plan without its fourth-corner records");
     HFEM_ARG_CHECK((flags & ~HFEM_FLAG_PHYSICAL_GRAD) == 0, "flags: only HFEM_FLAG_PHYSICAL_GRAD");
-    const bool b512 = h.pair_block == 512;
-    HFEM_ARG_CHECK(b512 ? (h.max_nodes <= 2 * 512 && h.max_rows <= 2) : (h.max_nodes <= 4 * 256 && h.max_rows <= 6),
+    const bool b512 = !quad && h.pair_block == 512;
+    HFEM_ARG_CHECK(quad    ? (h.max_nodes <= 4 * 256 && h.max_elems <= 4 * 256)
+                   : b512 ? (h.max_nodes <= 2 * 512 && h.max_rows <= 2)
+                          : (h.max_nodes <= 4 * 256 && h.max_rows <= 6),
                    "tile shape outside the CG kernels' instances");
+    HFEM_ARG_CHECK(!quad || h.max_owned <= h.max_nodes, "QUAD4 plan owns more rows than a tile holds");
     int64_t rows = 0;                                        // free u rows the plan's row maps address
     for (size_t i = 1; i < h.node_src.size(); i += 2) rows = std::max<int64_t>(rows, (int64_t)h.node_src[i] + 1);
     HFEM_ARG_CHECK(n_u >= rows, "n_u is smaller than the plan's free u rows");
     HFEM_ARG_CHECK(n_u < ((int64_t)1 << 31), "n_u too large");
     std::unique_ptr<hfem_cg> c(new hfem_cg);
     c->plan = plan; c->device = plan->device; c->n_u = n_u; c->phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0;
+    c->quad = quad;
     c->n_tiles = (int)h.tiles.size(); c->block = b512 ? 512 : 256;
     c->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(hfem::kVecMaxBlocks, (n_u + hfem::kVecBlock - 1) / hfem::kVecBlock));
     c->lds_apply = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 16 + (c->block / 64 + 2) * 8;
@@ -590,8 +573,9 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
     if (int rc = hfem::use_device(c->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
-    c->k = hfem::make_consts(mat, W, nullptr);
-    if (c->block == 512) launch_diag<512, 2, 2>(c, diag_out, precond, s);
+    c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);   // QUAD4: the 2x2 rule's weights are 1 (hfem_quad4_energy_plan_ex)
+    if (c->quad) hfem::launch_quad4_cg_diag(quad4_args(c, c->lds_diag, s), diag_out, c->dinv, precond);
+    else if (c->block == 512) launch_diag<512, 2, 2>(c, diag_out, precond, s);
     else launch_diag<256, 4, 6>(c, diag_out, precond, s);
     if (int rc = hfem::launch_status("hfem_cg_setup")) return rc;
     c->ready = true;

@@ -134,7 +134,11 @@ class EnergyLoss2D:
 
     # ---- reference API
     def domain_energy(self, model, b_force: Optional[Callable] = None) -> torch.Tensor:
-        """loss.py:55-88 (strain energy minus body work), fused."""
+        """loss.py:55-88 (strain energy minus body work), fused.  QUAD4 models: the tiled QUAD4 kernel with the edges off."""
+        if getattr(model, "nodes_per_element", 3) == 4:
+            return ops.Quad4PlanEnergyFn.apply(model.node_coords_free, model.u_free, model.node_coords_fixed.to(model.dtype),
+                                               model.u_fixed_rows(), model.tile_plan(self.tile_elems), self._mat, [0.0] * 4,
+                                               self._quad4_body(b_force), None, HFEM_FLAG_NO_EDGES | self._mode_flags(model))
         return self._fused(model, b_force, None, [0.0] * 4, HFEM_FLAG_NO_EDGES)
 
     def edge_energy(self, model, t_force: Optional[Callable] = None) -> torch.Tensor:

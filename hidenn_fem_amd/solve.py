@@ -12,8 +12,12 @@ and each iteration is two launches whose scalars (alpha, beta, the stopping test
 This is the exact "Step 1" of the alternating scheme of the reference's example 4 (frozen coordinates, optimise ``u_free``),
 the fixed-mesh FEM solution to compare an r-adapted energy against, and a warm start for L-BFGS.  Not deterministic: the LDS
 atomics of the matrix-vector product make iterates differ in the last bits from run to run (the scalars are reduced in a
-fixed order; the deterministic energy path has no solver counterpart).  TRI3 models only; the kernels run on a paired-slot
-tile plan (the model's own, or one built for the solver when the planner chose one element per slot for this mesh).
+fixed order; the deterministic energy path has no solver counterpart).  ``FrozenMeshSolver`` takes TRI3 models; its kernels
+run on a paired-slot tile plan (the model's own, or one built for the solver when the planner chose one element per slot for
+this mesh).  ``Quad4FrozenMeshSolver`` is the same solver for QUAD4 models (``csrc/quad4_cg.hip``: the matrix-vector product,
+the block diagonal and the AMG fine level for bilinear cells on the model's own QUAD4 plan; the residual from
+``hfem_quad4_energy_plan_ex``); everything above the element level -- vector kernels, stopping rule, graph replay, the AMG
+hierarchy -- is shared.  ``solve_displacement_`` picks the class by ``model.nodes_per_element``.
 """
 from __future__ import annotations
 
@@ -37,7 +41,8 @@ ST_ITER, ST_RNORM, ST_FNORM, ST_REASON, ST_HALTED = 0, 1, 2, 4, 10     # hfem_cg
 
 @dataclass
 class SolveInfo:
-    """Outcome of ``FrozenMeshSolver.solve()``.  ``residual_norm``: ||r||_2 over the free u rows of the CG recursion
+    """Outcome of ``FrozenMeshSolver.solve()`` / ``Quad4FrozenMeshSolver.solve()``.
+    ``residual_norm``: ||r||_2 over the free u rows of the CG recursion
     (r is updated, not recomputed); ``rhs_norm``: ||f||_2 = ||dE/du|| at ``u_free = 0`` (it includes the ``u_fixed`` term);
     ``reason``: ``"rtol"``, ``"atol"`` (whichever tolerance was the larger one when ||r|| <= max(rtol ||f||, atol)),
     ``"max_iter"`` or ``"breakdown"`` (p^T K p <= 0 or a non-finite scalar: ``u_free`` keeps the last good iterate)."""
@@ -48,31 +53,16 @@ class SolveInfo:
     reason: str
 
 
-class FrozenMeshSolver:
-    """Preconditioned CG for ``model.u_free`` at frozen coordinates (see the module docstring).
-
-    ``b_force`` / ``t_force``: the callables ``loss_fn(model, b_force, t_force)`` would take (default forces when None);
-    ``precond``: ``"block_jacobi"`` (2x2 diagonal blocks of K), ``"none"`` or ``"amg"`` (one symmetric V-cycle of smoothed
-    aggregation per iteration, ``csrc/tri3_amg.hip``; its host setup is cached on the model, a refresh redoes only the numeric
-    setup; needs Dirichlet rows; ``solver.amg`` reports the hierarchy); stopping test
-    ``||r||_2 <= max(rtol ||f||_2, atol)``; ``max_iter`` None = ``max(1000, 2 x free dofs)``; ``iters_per_graph``: CG
-    iterations per graph replay (iterations behind the one that stopped do nothing on the device).
-
-    ``solve()`` starts from the current ``model.u_free`` (a warm start works), writes the result into it in place and
-    returns a ``SolveInfo``.  Nothing else of the model changes: coordinates, ``.grad`` of both parameters, Dirichlet rows.
-    ``refresh()`` rebuilds the right-hand side inputs and the preconditioner; ``solve()`` calls it by itself when the
-    coordinate rows, ``u_fixed`` or the force inputs changed since the last one (tensor ``_version``).  fp32 models solve
-    in fp64 (coordinates widened once per refresh, ``u_free`` rounded once on write-back).  The gradient convention
-    follows ``loss_fn`` / ``model`` as the energy does; works in the model's storage row order (``reorder`` any)."""
+class _FrozenSolverBase:
+    """What the two element kinds share: argument checks, the solver-owned fp64 working set, the ``refresh`` bookkeeping, the
+    PCG loop with its graph replay and status reads, ``apply`` / ``precondition`` / ``amg``.  A subclass says which models it
+    takes (``_check_model``), which tile plan the kernels run on (``_make_plan``), the body-force table of its element
+    (``_body``) and which graded energy entry point gives ``dE/du`` (``_gradient``)."""
 
     def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None,
                  precond: str = "block_jacobi", rtol: float = 1e-10, atol: float = 0.0, max_iter: Optional[int] = None,
                  iters_per_graph: int = 16):
-        if getattr(model, "nodes_per_element", 3) != 3:
-            raise NotImplementedError("FrozenMeshSolver: TRI3 models only (QUAD4 has no CG kernels)")
-        if getattr(loss_fn, "deterministic", False):
-            raise NotImplementedError("FrozenMeshSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
-                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+        self._check_model(model, loss_fn)
         if precond not in ("block_jacobi", "none", "amg"):
             raise ValueError("precond must be 'block_jacobi', 'none' or 'amg'")
         if precond == "amg" and int(model._idx_udir.shape[0]) == 0:
@@ -88,9 +78,7 @@ class FrozenMeshSolver:
         self.precond, self.rtol, self.atol = precond, float(rtol), float(atol)
         self.iters_per_graph = int(iters_per_graph)
         self.phys = bool(loss_fn._mode_flags(model) & HFEM_FLAG_PHYSICAL_GRAD)
-        self.plan = _paired_plan(model, loss_fn.tile_elems)
-        if not self.plan.stats["paired"]:
-            raise NotImplementedError("FrozenMeshSolver: the CG kernels need a paired-slot tile plan (plan_elem_order 5)")
+        self.plan = self._make_plan(model, loss_fn)
         dev = model.u_free.device
         self.device = dev
         self.n_u = int(model.u_free.shape[0])
@@ -144,23 +132,14 @@ class FrozenMeshSolver:
             self._amg.setup(self._xf, self._xfix, mat, float(lf._W))
         # force tables exactly as EnergyLoss2D builds them (the coordinates are frozen: a position-dependent traction is a
         # constant table here)
-        bk = lf._body_table(self.b_force)
         flags = HFEM_FLAG_NO_GX | (HFEM_FLAG_PHYSICAL_GRAD if self.phys else 0)
         if m.neumann_edges is None or m.N_edges == 0:
             te, tc, flags = None, [0.0] * 4, flags | HFEM_FLAG_NO_EDGES
         else:
             te, tc = lf._traction(_Frozen(m, self._xf, self._xfix), self.t_force)
             te = None if te is None else te.to(device=dev, dtype=F64).contiguous()
-        self._tables = (mat, (C.c_double * 6)(*bk), te, None if tc is None else (C.c_double * 4)(*tc), flags)
+        self._tables = (mat, self._body(), te, None if tc is None else (C.c_double * 4)(*tc), flags)
         self._key = self._state_key()
-
-    def _gradient(self, u, out):
-        """out = dE/du_free at u (fp64 rows), one launch of the graded energy kernel."""
-        mat, bk, te, tc, flags = self._tables
-        check(_lib.lib().hfem_tri3_energy_plan(
-            self.plan.handle, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
-            ptr(self._ufix) if self._ufix.numel() else None, mat, float(self.loss_fn._W), bk, ptr(te), tc, 0, -1,
-            ptr(self._loss), None, ptr(out), flags, stream_ptr(self.device)), "hfem_tri3_energy_plan")
 
     def _read_status(self):
         check(_lib.lib().hfem_cg_status(self._h, self._status, stream_ptr(self.device)), "hfem_cg_status")
@@ -242,17 +221,100 @@ class FrozenMeshSolver:
         return z
 
 
+class FrozenMeshSolver(_FrozenSolverBase):
+    """Preconditioned CG for ``model.u_free`` at frozen coordinates (see the module docstring), TRI3 models
+    (``Quad4FrozenMeshSolver`` is the QUAD4 one; ``solve_displacement_`` takes either).
+
+    ``b_force`` / ``t_force``: the callables ``loss_fn(model, b_force, t_force)`` would take (default forces when None);
+    ``precond``: ``"block_jacobi"`` (2x2 diagonal blocks of K), ``"none"`` or ``"amg"`` (one symmetric V-cycle of smoothed
+    aggregation per iteration, ``csrc/tri3_amg.hip``; its host setup is cached on the model, a refresh redoes only the numeric
+    setup; needs Dirichlet rows; ``solver.amg`` reports the hierarchy); stopping test
+    ``||r||_2 <= max(rtol ||f||_2, atol)``; ``max_iter`` None = ``max(1000, 2 x free dofs)``; ``iters_per_graph``: CG
+    iterations per graph replay (iterations behind the one that stopped do nothing on the device).
+
+    ``solve()`` starts from the current ``model.u_free`` (a warm start works), writes the result into it in place and
+    returns a ``SolveInfo``.  Nothing else of the model changes: coordinates, ``.grad`` of both parameters, Dirichlet rows.
+    ``refresh()`` rebuilds the right-hand side inputs and the preconditioner; ``solve()`` calls it by itself when the
+    coordinate rows, ``u_fixed`` or the force inputs changed since the last one (tensor ``_version``).  fp32 models solve
+    in fp64 (coordinates widened once per refresh, ``u_free`` rounded once on write-back).  The gradient convention
+    follows ``loss_fn`` / ``model`` as the energy does; works in the model's storage row order (``reorder`` any)."""
+
+    @staticmethod
+    def _check_model(model, loss_fn):
+        if getattr(model, "nodes_per_element", 3) != 3:
+            raise NotImplementedError("FrozenMeshSolver: TRI3 models only (QUAD4 models: Quad4FrozenMeshSolver, or "
+                                      "solve_displacement_, which takes either)")
+        if getattr(loss_fn, "deterministic", False):
+            raise NotImplementedError("FrozenMeshSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
+                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+
+    @staticmethod
+    def _make_plan(model, loss_fn):
+        plan = _paired_plan(model, loss_fn.tile_elems)
+        if not plan.stats["paired"]:
+            raise NotImplementedError("FrozenMeshSolver: the CG kernels need a paired-slot tile plan (plan_elem_order 5)")
+        return plan
+
+    def _body(self):
+        return (C.c_double * 6)(*self.loss_fn._body_table(self.b_force))
+
+    def _gradient(self, u, out):
+        """out = dE/du_free at u (fp64 rows), one launch of the graded energy kernel."""
+        mat, bk, te, tc, flags = self._tables
+        check(_lib.lib().hfem_tri3_energy_plan(
+            self.plan.handle, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
+            ptr(self._ufix) if self._ufix.numel() else None, mat, float(self.loss_fn._W), bk, ptr(te), tc, 0, -1,
+            ptr(self._loss), None, ptr(out), flags, stream_ptr(self.device)), "hfem_tri3_energy_plan")
+
+
+class Quad4FrozenMeshSolver(_FrozenSolverBase):
+    """``FrozenMeshSolver`` for QUAD4 models (``QuadShapeNN2D``): the same arguments, the same contract, the same
+    ``SolveInfo``.  ``K p``, the block-Jacobi blocks and the AMG fine level come from ``csrc/quad4_cg.hip`` on the model's own
+    QUAD4 tile plan (no pairing); the residual and ``||f||`` from the graded QUAD4 energy kernel on fp64 rows
+    (``hfem_quad4_energy_plan_ex``), so default forces, a body-force callable (evaluated at the 2x2 reference Gauss points, as
+    ``EnergyLoss2D`` does), a traction callable and nonzero ``u_fixed`` enter with no solver code of their own.  fp32 models
+    solve in fp64 (rows widened per refresh, ``u_free`` rounded once on write-back).  Refuses TRI3 models,
+    ``EnergyLoss2D(deterministic=True)`` and the planless cross-check path (``loss_fn.quad4_planless``)."""
+
+    @staticmethod
+    def _check_model(model, loss_fn):
+        if getattr(model, "nodes_per_element", 3) != 4:
+            raise NotImplementedError("Quad4FrozenMeshSolver: QUAD4 models only (TRI3 models: FrozenMeshSolver)")
+        if getattr(loss_fn, "deterministic", False):
+            raise NotImplementedError("Quad4FrozenMeshSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
+                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+        if getattr(loss_fn, "quad4_planless", False):
+            raise NotImplementedError("Quad4FrozenMeshSolver: quad4_planless=True has no solver counterpart (the CG kernels run "
+                                      "on the tile plan)")
+
+    @staticmethod
+    def _make_plan(model, loss_fn):
+        return model.tile_plan(loss_fn.tile_elems)
+
+    def _body(self):
+        bq = self.loss_fn._quad4_body(self.b_force)
+        return None if bq is None else (C.c_double * 8)(*bq)
+
+    def _gradient(self, u, out):
+        """out = dE/du_free at u (fp64 rows), one launch of the graded QUAD4 energy kernel."""
+        mat, bq, te, tc, flags = self._tables
+        check(_lib.lib().hfem_quad4_energy_plan_ex(
+            self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
+            ptr(self._ufix) if self._ufix.numel() else None, mat, bq, ptr(te), tc, 0, -1, ptr(self._loss), None, ptr(out),
+            flags, stream_ptr(self.device)), "hfem_quad4_energy_plan_ex")
+
+
 class AmgHost:
-    """Host setup of the AMG hierarchy of one mesh (``csrc/amg.cpp``): block pattern, element fan, aggregation and symbolic
-    products of every level.  Depends on the connectivity, the Dirichlet mask and the u row order only (``amg_host``)."""
+    """Host setup of the AMG hierarchy of one mesh (``csrc/amg.cpp``; TRI3 or QUAD4 by the connectivity's width): block
+    pattern, element fan, aggregation and symbolic products of every level.  Depends on the connectivity, the Dirichlet mask and the u row order only (``amg_host``)."""
 
     def __init__(self, model):
         conn = np.ascontiguousarray(model.connectivity.detach().cpu().numpy(), dtype=np.int32)
         xs = np.ascontiguousarray(model._x_src, dtype=np.int32)
         us = np.ascontiguousarray(model._u_src, dtype=np.int32)
         h = C.c_void_p()
-        check(_lib.lib().hfem_amg_host_create(conn.ctypes.data, conn.shape[0], xs.shape[0], xs.ctypes.data, us.ctypes.data,
-                                              C.byref(h)), "hfem_amg_host_create")
+        check(_lib.lib().hfem_amg_host_create_ex(conn.ctypes.data, conn.shape[0], conn.shape[1], xs.shape[0], xs.ctypes.data,
+                                                 us.ctypes.data, C.byref(h)), "hfem_amg_host_create_ex")
         self._h = h
         top = self.info(-1)
         self.seconds = top[4] * 1e-9
@@ -340,9 +402,7 @@ class _AmgDevice:
 def assemble_stiffness(model, loss_fn) -> torch.Tensor:
     """K_ff of the model at its current coordinates: fp64 ``torch.sparse_bsr_tensor`` with 2x2 blocks over the free u rows in
     storage order (Dirichlet columns dropped), from the AMG assembly kernel (one thread per row, deterministic).  The gradient
-    convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 models only."""
-    if getattr(model, "nodes_per_element", 3) != 3:
-        raise NotImplementedError("assemble_stiffness: TRI3 models only")
+    convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 and QUAD4 models."""
     _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
     dev = model.u_free.device
     phys = bool(loss_fn._mode_flags(model) & HFEM_FLAG_PHYSICAL_GRAD)
@@ -392,6 +452,7 @@ class _Frozen:
 
 
 def solve_displacement_(model, loss_fn, **kw) -> SolveInfo:
-    """One-shot ``FrozenMeshSolver(model, loss_fn, **kw).solve()``: ``model.u_free`` minimises the energy at the current
-    coordinates (in place)."""
-    return FrozenMeshSolver(model, loss_fn, **kw).solve()
+    """One-shot ``FrozenMeshSolver(model, loss_fn, **kw).solve()`` -- ``Quad4FrozenMeshSolver`` for a QUAD4 model:
+    ``model.u_free`` minimises the energy at the current coordinates (in place)."""
+    cls = Quad4FrozenMeshSolver if getattr(model, "nodes_per_element", 3) == 4 else FrozenMeshSolver
+    return cls(model, loss_fn, **kw).solve()

@@ -642,12 +642,14 @@ int hfem_rectq4_mse_f32(int device, const float *gx, int64_t nx, const float *gy
                         const float *x_eval, const float *target, int64_t m, float *loss_acc, float *ggx, float *ggy,
                         float *gu, void *stream);
 
-/* ------------------------------------------------------------------ frozen-mesh displacement solve (TRI3)
+/* ------------------------------------------------------------------ frozen-mesh displacement solve (TRI3 and QUAD4)
  * Matrix-free preconditioned conjugate gradients for u_free at FIXED coordinates (hidenn_fem_amd/solve.py; no reference
  * counterpart -- the reference reaches this minimum only by iterating Adam / L-BFGS on the energy).  The energy is exactly
  * quadratic in u there, E(u) = 1/2 u^T K u - f^T u, so K p = dE/du(p) with no forces and r = -dE/du(u): the caller
  * forms g0 = dE/du(u0) and g_zero = dE/du(u_free = 0) with hfem_tri3_energy_plan (fp64 rows, the forces of its loss) and
- * the solver never sees the forces.  Paired-slot TRI3 plans only (the default); all vectors are fp64 free u rows [n_u][2]
+ * the solver never sees the forces.  Paired-slot TRI3 plans (the default), or QUAD4 plans as hfem_quad4_energy_plan_ex takes
+ * them (csrc/quad4_cg.hip: g0 / g_zero from that entry point, W is not read -- the 2x2 rule's weights are 1; the vector
+ * kernels, the status record and the halt logic are shared); all vectors are fp64 free u rows [n_u][2]
  * in the plan's storage order.  Two launches per iteration (csrc/tri3_cg.hip): q = K p with p = z + beta p_old formed in
  * the gather, then u += alpha p, r -= alpha q, z = D^-1 r; alpha, beta and the stopping test |r|_2 <= max(rtol |f|_2, atol)
  * are reduced on the device in a fixed order.  Once halted (converged, max_iter, breakdown: p^T K p <= 0 or a non-finite
@@ -706,22 +708,24 @@ int hfem_tri3_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, c
                                   const float *x_fixed, const float *x_ref, double weight, double *value_acc,
                                   double *grad_acc, void *stream);
 
-/* ------------------------------------------------------------------ smoothed-aggregation AMG for the frozen-mesh solve (TRI3)
+/* ------------------------------------------------------------------ smoothed-aggregation AMG for the frozen-mesh solve
  * A symmetric V-cycle of smoothed aggregation over K_ff in 2x2 node blocks (hidenn_fem_amd/solve.py, precond="amg").
- * Host setup (amg.cpp, no GPU), once per mesh topology: conn [ne][3] int32, x_src / u_src [nn] the model's row maps (u_src < 0:
+ * Host setup (amg.cpp, no GPU), once per mesh topology: conn [ne][npe] int32 (host_create: npe = 3, TRI3; host_create_ex: npe
+ * 3 or 4, QUAD4 -- a cell's diagonal partners are neighbours), x_src / u_src [nn] the model's row maps (u_src < 0:
  * a Dirichlet node).  Builds the fine block pattern (diagonal + free neighbours through shared elements, sorted columns), the
  * node -> element fan with the block slots each corner writes to, the aggregation of every level (SA phases 1-3, no strength
  * filter, singletons merged into a neighbour's aggregate; until a level has <= 1500 dofs or stops shrinking) and the
  * symbolic products P = pattern(A) pattern(P_tent), R = P^T, A P and A_c = R A P.  Never reads coordinates.
- *   host_info   level -1: {levels, n_u, ne, fan entries, host setup ns, 0, 0, 0}; level l: {block rows, block size, A block
+ *   host_info   level -1: {levels, n_u, ne, fan entries, host setup ns, npe, 0, 0}; level l: {block rows, block size, A block
  *               nnz, aggregates (0 on the coarsest), P block nnz, AP block nnz, 0, 0}
  *   host_copy   *n_out = length of an int32 array, copied into out when out != NULL.  level -1: which 0 fan_ptr, 1 fan
- *               element, 2 fan corner, 3 fan slots [.][3]; level l: 0 A row_ptr, 1 A columns, 2 A diagonal slot, 3 aggregate
+ *               element, 2 fan corner, 3 fan slots [.][npe]; level l: 0 A row_ptr, 1 A columns, 2 A diagonal slot, 3 aggregate
  *               of each row, 4 P row_ptr, 5 P columns, 6 R row_ptr, 7 R columns (fine rows), 8 R -> P block index,
  *               9 AP row_ptr, 10 AP columns
  * Device hierarchy (tri3_amg.hip, fp64), from a host setup (which may be destroyed afterwards):
  *   assemble    level-0 A values (K_ff, 2x2 blocks, row-major, in the host pattern) at the coordinates x_free / x_fixed (fp64
- *               rows; mat, W as hfem_cg_setup).  One thread per row, no atomics: bit-deterministic.
+ *               rows; mat, W as hfem_cg_setup).  One thread per row, no atomics: bit-deterministic.  A QUAD4 host setup
+ *               selects the QUAD4 instance (csrc/quad4_cg.hip); everything below the assembly is the same code.
  *   setup       assemble + the numeric hierarchy (block-diagonal inverses, lambda_max(D^-1 A) by power iteration, tentative
  *               and smoothed prolongators, Galerkin products); writes the coarsest level as a dense row-major N x N matrix
  *               into coarse_out (an all-zero row gets a 1 on the diagonal).  The caller inverts it and hands the inverse
@@ -737,6 +741,8 @@ typedef struct hfem_amg_host hfem_amg_host;
 typedef struct hfem_amg hfem_amg;
 int hfem_amg_host_create(const int32_t *conn, int64_t ne, int64_t nn, const int32_t *x_src, const int32_t *u_src,
                          hfem_amg_host **out);
+int hfem_amg_host_create_ex(const int32_t *conn, int64_t ne, int32_t npe, int64_t nn, const int32_t *x_src,
+                            const int32_t *u_src, hfem_amg_host **out);
 int hfem_amg_host_destroy(hfem_amg_host *host);
 int hfem_amg_host_info(const hfem_amg_host *host, int32_t level, int64_t info[8]);
 int hfem_amg_host_copy(const hfem_amg_host *host, int32_t level, int32_t which, int32_t *out, int64_t *n_out);

@@ -8,6 +8,11 @@ for AMG (numeric setup included and not) and block Jacobi, one V-cycle and one c
 graph replays of the same buffers: cache regime), and iteration counts in both gradient conventions.
 
     python scripts/amg_timing.py [--grid 1001x501] [--out profiles/amg/amg_timing_T1M.json]
+
+``--quad``: the same record for Q1M, 10^6 QUAD4 cells on the 1001 x 1001 grid (Quad4FrozenMeshSolver), plus the AMG iteration
+count on the 251 x 251 grid (6 x 10^4 cells) of the same run for the mesh-independence bar:
+
+    python scripts/amg_timing.py --quad [--out profiles/amg/amg_timing_Q1M.json]
 """
 import argparse
 import json
@@ -19,9 +24,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from hidenn_fem_amd.loss import EnergyLoss2D
-from hidenn_fem_amd.mesh import structured_tri_mesh
+from hidenn_fem_amd.mesh import structured_quad_mesh, structured_tri_mesh
 from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
-from hidenn_fem_amd.solve import FrozenMeshSolver
+from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver
+
+Solver = FrozenMeshSolver
 
 F64 = torch.float64
 
@@ -45,7 +52,7 @@ def events_us(fn, reps):
 def solve_timed(m, lf, precond, refresh_inside):
     with torch.no_grad():
         m.u_free.zero_()
-    s = FrozenMeshSolver(m, lf, precond=precond, rtol=1e-8)
+    s = Solver(m, lf, precond=precond, rtol=1e-8)
     if not refresh_inside:
         s.refresh()
     torch.cuda.synchronize()
@@ -60,16 +67,28 @@ def solve_timed(m, lf, precond, refresh_inside):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", default="1001x501")
+    ap.add_argument("--grid", default="")
+    ap.add_argument("--quad", action="store_true", help="QUAD4 cells (default grid 1001x1001) instead of TRI3 (1001x501)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    nx, ny = (int(v) for v in a.grid.split("x"))
-    coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
-    torch.manual_seed(0)
-    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
+    global Solver
+    nx, ny = (int(v) for v in (a.grid or ("1001x1001" if a.quad else "1001x501")).split("x"))
+    Solver = Quad4FrozenMeshSolver if a.quad else FrozenMeshSolver
+
+    def model(nx, ny):
+        if a.quad:
+            mesh = structured_quad_mesh(nx, ny, length=2.0, height=2.0, jitter=0.2, seed=0, dtype=F64)
+        else:
+            mesh = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+        coords, conn, geom, bc, mn, edges = mesh
+        torch.manual_seed(0)
+        return PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
+                                        neumann_edges=edges).to(dev)
+
+    m = model(nx, ny)
     lf = EnergyLoss2D(device=dev, dtype=F64)
-    rec = dict(mesh=f"{nx}x{ny} structured, jitter 0.2", n_elems=m.Nelems, n_u_rows=int(m.u_free.shape[0]),
+    rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=m.Nelems, n_u_rows=int(m.u_free.shape[0]),
                regime="cache (back-to-back launches of the same buffers)")
     solve_timed(m, lf, "amg", True)                       # warm-up: code objects, the host setup, torch.linalg
     s, rec["amg_with_numeric_setup"] = solve_timed(m, lf, "amg", True)
@@ -84,7 +103,7 @@ def main():
     r = torch.randn(m.u_free.shape, dtype=F64, device=dev)
     rec["vcycle_us"] = events_us(lambda: s.precondition(r), 50)
     # one captured AMG iteration (rtol 0: never halts while timed)
-    s0 = FrozenMeshSolver(m, lf, precond="amg", rtol=0.0, atol=0.0, max_iter=10 ** 9, iters_per_graph=16)
+    s0 = Solver(m, lf, precond="amg", rtol=0.0, atol=0.0, max_iter=10 ** 9, iters_per_graph=16)
     with torch.no_grad():
         m.u_free.zero_()
     s0.refresh()
@@ -105,6 +124,11 @@ def main():
     rec["bars"] = dict(iterations_le_100=rec["amg_with_numeric_setup"]["iterations"] <= 100, time_le_66ms=am <= 0.066,
                        speedup_ge_5=bj / am >= 5.0, numeric_setup_le_30ms=rec["numeric_setup_seconds_median"] <= 0.030,
                        host_setup_le_10s=rec["hierarchy"]["host_setup_seconds"] <= 10.0)
+    if a.quad:                                           # mesh independence: the same solve on 6 x 10^4 cells of the same run
+        small = model(251, 251)
+        s_small, r_small = solve_timed(small, lf, "amg", True)
+        rec["amg_small_mesh"] = dict(n_elems=small.Nelems, levels=s_small.amg["levels"], **r_small)
+        rec["bars"]["iterations_le_1p5x_small_mesh"] = rec["amg_with_numeric_setup"]["iterations"] <= 1.5 * r_small["iterations"]
     line = json.dumps(rec)
     print(line)
     if a.out:

@@ -13,6 +13,11 @@ eager ctypes / Python numbers beside them are host-bound): the per-iteration wor
 the 256 MB Infinity Cache, so these are cache-regime numbers.
 
     python scripts/cg_timing.py [--grid 1001x501] [--reps 200] [--out profiles/cg/cg_timing_T1M.json]
+
+``--quad``: the same record for Q1M, 10^6 QUAD4 cells on the 1001 x 1001 grid (Quad4FrozenMeshSolver, csrc/quad4_cg.hip; the
+algorithmic bytes are 16 Ne + 48 Nn: two record words per cell):
+
+    python scripts/cg_timing.py --quad [--out profiles/cg/cg_timing_Q1M.json]
 """
 import argparse
 import ctypes as C
@@ -26,9 +31,9 @@ import torch
 
 from hidenn_fem_amd import _lib
 from hidenn_fem_amd.loss import EnergyLoss2D
-from hidenn_fem_amd.mesh import structured_tri_mesh
+from hidenn_fem_amd.mesh import structured_quad_mesh, structured_tri_mesh
 from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
-from hidenn_fem_amd.solve import FrozenMeshSolver
+from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver
 
 F64 = torch.float64
 
@@ -61,25 +66,30 @@ def graphed_us(fn, reps, k=16):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", default="1001x501")
+    ap.add_argument("--grid", default="")
+    ap.add_argument("--quad", action="store_true", help="QUAD4 cells (default grid 1001x1001) instead of TRI3 (1001x501)")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    nx, ny = (int(v) for v in a.grid.split("x"))
-    coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    nx, ny = (int(v) for v in (a.grid or ("1001x1001" if a.quad else "1001x501")).split("x"))
+    Solver = Quad4FrozenMeshSolver if a.quad else FrozenMeshSolver
+    if a.quad:
+        coords, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=2.0, height=2.0, jitter=0.2, seed=0, dtype=F64)
+    else:
+        coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
     torch.manual_seed(0)
     m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
     lf = EnergyLoss2D(device=dev, dtype=F64)
     ne, nn = m.Nelems, m.Nnodes
-    rec = dict(mesh=f"{nx}x{ny} structured, jitter 0.2", n_elems=ne, n_nodes=nn, n_u_rows=int(m.u_free.shape[0]),
+    rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=ne, n_nodes=nn, n_u_rows=int(m.u_free.shape[0]),
                plan=dict((k, v) for k, v in m.tile_plan().stats.items() if k in ("n_tiles", "threads_per_tile", "paired",
                                                                                    "max_tile_nodes", "max_tile_owned")),
                regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
     u_init = m.u_free.detach().clone()
 
     # ---- apply vs the graded energy launch
-    s = FrozenMeshSolver(m, lf, rtol=1e-8)
+    s = Solver(m, lf, rtol=1e-8)
     s.refresh()
     p = torch.randn(m.u_free.shape, dtype=F64, device=dev) * 1e-4
     q, pq = torch.empty_like(p), torch.empty((), dtype=F64, device=dev)
@@ -87,16 +97,17 @@ def main():
     apply_one = lambda: L.hfem_cg_apply(s._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), _lib.stream_ptr(dev))
     apply_host_us = events_us(apply_one, a.reps)
     apply_us = graphed_us(apply_one, a.reps)
-    alg_bytes = 12 * ne + 48 * nn
+    alg_bytes = (16 if a.quad else 12) * ne + 48 * nn
     rec["apply"] = dict(us=apply_us, algorithmic_bytes=alg_bytes, tb_per_s=alg_bytes / apply_us * 1e-6,
                         fraction_of_8TBps=alg_bytes / apply_us * 1e-6 / 8.0, us_eager_ctypes=apply_host_us)
     energy_us = graphed_us(lambda: lf.value_and_grad_(m), a.reps)
     rec["energy_value_and_grad"] = dict(us=energy_us, us_eager=events_us(lambda: lf.value_and_grad_(m), a.reps),
-                                        note="pair kernel + tile-energy sum launch")
+                                        note="graded energy kernel + tile-energy sum launch")
+    rec["ratio_apply_over_energy"] = apply_us / energy_us
     rec["bar_apply_faster_than_energy"] = apply_us < energy_us
 
     # ---- one captured iteration (rtol = 0: never halts while timed)
-    s0 = FrozenMeshSolver(m, lf, rtol=0.0, atol=0.0, max_iter=10 ** 9, iters_per_graph=16)
+    s0 = Solver(m, lf, rtol=0.0, atol=0.0, max_iter=10 ** 9, iters_per_graph=16)
     s0.refresh()
     with torch.no_grad():
         s0._u.copy_(u_init)
@@ -111,7 +122,7 @@ def main():
     for pc in ("block_jacobi", "none"):
         with torch.no_grad():
             m.u_free.copy_(u_init)
-        sv = FrozenMeshSolver(m, lf, precond=pc, rtol=1e-8)
+        sv = Solver(m, lf, precond=pc, rtol=1e-8)
         sv.refresh()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
