@@ -12,7 +12,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
-        r_adapt=False, outer=20, precond="block_jacobi"):
+        r_adapt=False, outer=20, precond="block_jacobi", quad=False):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -27,7 +27,10 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     the frozen-mesh solve, then ``outer`` iterations of ``hidenn_fem_amd.radapt.RAdaptiveSolver`` (re-solve ``u``, an L-BFGS step
     on the coordinates bounded so that no element inverts, Armijo on the energy); prints the energy history, the smallest
     element quality and the stopping reason, and returns the r-adapted energy ``Pi*``.
-    ``precond``: the CG preconditioner of ``solve_first`` and ``r_adapt`` (``"block_jacobi"`` or ``"amg"``)."""
+    ``precond``: the CG preconditioner of ``solve_first`` and ``r_adapt`` (``"block_jacobi"`` or ``"amg"``).
+    ``quad=True`` (with ``r_adapt``): the same plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
+    (``structured_quad_mesh``: the structured mesher cuts holes into triangles only), same sides, material and traction, run
+    through ``hidenn_fem_amd.radapt.r_adapt_`` (``Quad4RAdaptiveSolver``); prints the same three kinds of line."""
     import os
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -39,7 +42,13 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     length, height = 2.0, 1.0
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
-    nodes, conn, geom, bc, mn, edges = generate_mesh(length, height, holes, sides, nx, ny)
+    if quad:
+        if not r_adapt:
+            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve only (pass r_adapt=True / --r-adapt)")
+        from hidenn_fem_amd.mesh import structured_quad_mesh
+        nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
+    else:
+        nodes, conn, geom, bc, mn, edges = generate_mesh(length, height, holes, sides, nx, ny)
     if rank0:
         print(f"nodes {tuple(nodes.shape)} elements {tuple(conn.shape)} boundary {int(geom.sum())} "
               f"dirichlet {int(bc.sum())} neumann edges {tuple(edges.shape)}")
@@ -110,17 +119,17 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
 
 def _r_adapt(model, loss_fn, outer, precond="block_jacobi"):
     import time
-    from hidenn_fem_amd.radapt import RAdaptiveSolver, mesh_quality
+    from hidenn_fem_amd.radapt import mesh_quality, quad4_mesh_quality, r_adapt_
+    quality = quad4_mesh_quality if getattr(model, "nodes_per_element", 3) == 4 else mesh_quality
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    solver = RAdaptiveSolver(model, loss_fn, max_outer=outer, cg_precond=precond)
-    info = solver.run()
+    info = r_adapt_(model, loss_fn, max_outer=outer, cg_precond=precond)      # RAdaptiveSolver / Quad4RAdaptiveSolver
     torch.cuda.synchronize()
     print(f"frozen-mesh energy {info.energy[0]:.9e} ({info.cg_iterations[0]} CG iterations)")
     for k in range(1, info.iterations + 1):
         print(f"outer {k:3d}: energy {info.energy[k]:.9e} |g_x|inf {info.grad_inf[k]:.3e} alpha {info.alpha[k]:.3e} "
               f"(max {info.alpha_max[k]:.3e}) CG {info.cg_iterations[k]} min q {info.min_q[k]:.4f}")
-    mq = mesh_quality(model)
+    mq = quality(model)
     print(f"r-adapted energy {info.energy[-1]:.9e} after {info.iterations} outer iterations ({info.reason}), "
           f"min q {mq.min_q:.4f}, inverted elements {mq.n_inverted}, {time.perf_counter() - t0:.3f} s")
     return model, info.energy[-1]
@@ -138,9 +147,10 @@ if __name__ == "__main__":
     ap.add_argument("--r-adapt", action="store_true",
                     help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS")
     ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
+    ap.add_argument("--quad", action="store_true", help="with --r-adapt: the plate as nx x ny nodes of QUAD4 cells (no holes)")
     ap.add_argument("--precond", choices=["block_jacobi", "amg"], default="block_jacobi",
                     help="CG preconditioner of --solve-first and --r-adapt")
     a = ap.parse_args()
     run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,
-        precond=a.precond)
+        precond=a.precond, quad=a.quad)

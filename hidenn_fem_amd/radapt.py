@@ -1,7 +1,8 @@
-"""r-adaptive TRI3 solve: alternate the frozen-mesh displacement solve with inversion-safe coordinate steps.
+"""r-adaptive solve (TRI3 and QUAD4): alternate the frozen-mesh displacement solve with inversion-safe coordinate steps.
 
 HiDeNN-FEM treats the nodal coordinates as trainable: the FE energy is lowered by moving the interior nodes.  With the reduced
-energy ``Pi*(x) = min_u E(u, x)`` (evaluated by ``solve.FrozenMeshSolver``), the envelope theorem gives
+energy ``Pi*(x) = min_u E(u, x)`` (evaluated by ``solve.FrozenMeshSolver`` / ``solve.Quad4FrozenMeshSolver``), the envelope
+theorem gives
 ``grad Pi*(x) = dE/dx`` at ``u = u*(x)`` -- the coordinate gradient the graded energy kernel already returns.  A step on ``x``
 at fixed ``u_k`` that passes an Armijo test gives ``Pi*(x_k+1) <= E(u_k, x_k+1) < E(u_k, x_k) = Pi*(x_k)``: re-solving ``u`` (CG
 from ``u_k``, whose energy only decreases) can only lower it further, so every outer iteration lowers the reduced energy.
@@ -11,7 +12,17 @@ mean-ratio quality ``q``, the ``detJ`` ratio to the initial mesh, the inverted c
 ``Q(x) = (w / Ne) sum (1/q - 1)``: the ``mesh_quality_loss`` the reference's example 4 sketches (examples/example4.py:83-110)
 and never defines.
 
-TRI3 models only; coordinate rows fp64 or fp32 (fp64 inside the kernels), any storage row order (``reorder``).
+QUAD4 models (``csrc/quad4_mesh.hip``): the same three pieces per CORNER of a bilinear cell.  With the corner cross product
+``c_k = (X_k+1 - X_k) x (X_k-1 - X_k)`` (``= 4 detJ`` at corner ``k``; ``detJ`` is affine over the reference square, so its
+extremes are at the corners) a cell is valid everywhere iff all four ``s c_k > 0``, the step bound is the first step at which
+some ``c_k`` keeps only ``eta`` of its value (every Gauss-point ``detJ`` then keeps at least ``eta``), ``q = min_k q_k`` with
+``q_k = 2 s c_k / (|X_k+1 - X_k|^2 + |X_k-1 - X_k|^2)`` (1 at a right-angled corner with equal sides), ``det_ratio = min_k
+c_k / c_k_initial`` and ``Q(x) = (w / (4 Ne)) sum_e sum_k (1/q_ek - 1)``.
+
+Each function and class takes one element kind: ``RAdaptiveSolver``, ``mesh_quality``, ``max_feasible_step``, ``quality_barrier``
+TRI3 models, ``Quad4RAdaptiveSolver``, ``quad4_mesh_quality``, ``quad4_max_feasible_step``, ``quad4_quality_barrier`` QUAD4
+models; ``r_adapt_`` takes either.  The outer loop, the line search and the stopping rules are one piece of code
+(``_RAdaptBase``).  Coordinate rows fp64 or fp32 (fp64 inside the kernels), any storage row order (``reorder``).
 """
 from __future__ import annotations
 
@@ -27,11 +38,6 @@ from ._lib import check, dev_index, ptr, stream_ptr
 F64 = torch.float64
 
 
-def _require_tri3(model, what):
-    if getattr(model, "nodes_per_element", 3) != 3:
-        raise NotImplementedError(f"{what}: TRI3 models only (QUAD4 has no mesh-validity kernels)")
-
-
 def _check_eta(eta):
     if not (0.0 < float(eta) < 1.0):
         raise ValueError(f"eta must be in (0, 1), got {eta!r}")
@@ -39,10 +45,19 @@ def _check_eta(eta):
 
 class _Mesh:
     """What the mesh kernels read of a model: the int32 connectivity, the x row map, the fixed and the reference rows (all on
-    the model's device, in its coordinate dtype)."""
+    the model's device, in its coordinate dtype).  TRI3 (``csrc/tri3_mesh.hip``); ``_QuadMesh`` is the QUAD4 one."""
+
+    abi, npe, kind = "hfem_tri3", 3, "TRI3"                    # prefix of the three entry points, nodes per element
+    other = "QUAD4 models: quad4_mesh_quality, quad4_max_feasible_step, quad4_quality_barrier, Quad4RAdaptiveSolver"
+    measure_f32_trials = False                                 # _RAdaptBase._line_search: measure fp32 trials as stored
+
+    @classmethod
+    def require(cls, model, what):
+        if getattr(model, "nodes_per_element", 3) != cls.npe:
+            raise NotImplementedError(f"{what}: {cls.kind} models only ({cls.other}; r_adapt_ takes either kind)")
 
     def __init__(self, model):
-        _require_tri3(model, "hidenn_fem_amd.radapt")
+        self.require(model, "hidenn_fem_amd.radapt")
         xf = _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
         if xf.dtype not in (F64, torch.float32):
             raise RuntimeError(f"hidenn_fem_amd.radapt: coordinate rows must be fp64 or fp32, got {xf.dtype}")
@@ -58,9 +73,10 @@ class _Mesh:
         t = self.model.node_coords_fixed.to(device=self.device, dtype=self.dtype).contiguous()
         return t if t.numel() else None
 
-    def fn(self, name):
-        L = _lib.lib()
-        return getattr(L, name + "_f32") if self.f32 else getattr(L, name)
+    def _call(self, name, *args):
+        """Call the entry point ``name`` of this element kind (its ``_f32`` twin for fp32 rows) and check its return code."""
+        name = f"{self.abi}_{name}"
+        check(getattr(_lib.lib(), name + "_f32" if self.f32 else name)(*args), name)
 
     def measure(self, x_ref=None, per_element=True):
         """(q [Ne] or None, ratio [Ne] or None, summary [3] fp64 device) against ``x_ref`` (default: initial coordinates)."""
@@ -71,9 +87,8 @@ class _Mesh:
         xr = self.x_ref if x_ref is None else x_ref.to(dtype=self.dtype).contiguous()
         xf = self.model.node_coords_free.detach()
         xfix = self.fixed()
-        check(self.fn("hfem_tri3_mesh_measure")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
-                                                 ptr(xr), ptr(q), ptr(r), ptr(summary), stream_ptr(dev)),
-              "hfem_tri3_mesh_measure")
+        self._call("mesh_measure", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix), ptr(xr), ptr(q),
+                   ptr(r), ptr(summary), stream_ptr(dev))
         return q, r, summary
 
     def step_bound(self, d, eta, out=None):
@@ -83,8 +98,8 @@ class _Mesh:
         out = torch.empty((), dtype=F64, device=dev) if out is None else out
         xf = self.model.node_coords_free.detach()
         xfix = self.fixed()
-        check(self.fn("hfem_tri3_step_bound")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
-                                               ptr(d), float(eta), ptr(out), stream_ptr(dev)), "hfem_tri3_step_bound")
+        self._call("step_bound", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix), ptr(d), float(eta),
+                   ptr(out), stream_ptr(dev))
         return out
 
     def barrier(self, weight, grad=True):
@@ -94,16 +109,37 @@ class _Mesh:
         g = torch.zeros((self.n_x, 2), dtype=F64, device=dev) if grad else None
         xf = self.model.node_coords_free.detach()
         xfix = self.fixed()
-        check(self.fn("hfem_tri3_quality_barrier")(dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf),
-                                                    ptr(xfix), ptr(self.x_ref), float(weight), ptr(val), ptr(g),
-                                                    stream_ptr(dev)), "hfem_tri3_quality_barrier")
+        self._call("quality_barrier", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
+                   ptr(self.x_ref), float(weight), ptr(val), ptr(g), stream_ptr(dev))
         return val, g
+
+    # ---- the public functions of an element kind
+    def quality(self):
+        q, r, s = self.measure()
+        s = s.tolist()
+        return MeshQuality(q=q, det_ratio=r, min_q=s[0], min_det_ratio=s[1], n_inverted=int(s[2]))
+
+    def feasible_step(self, d, eta, as_tensor):
+        if tuple(d.shape) != (self.n_x, 2):
+            raise ValueError(f"d must have the shape of node_coords_free {(self.n_x, 2)}, got {tuple(d.shape)}")
+        d64 = d.detach().to(device=self.device, dtype=F64).contiguous()
+        a = self.step_bound(d64, eta)
+        return a if as_tensor else a.item()
+
+
+class _QuadMesh(_Mesh):
+    """``_Mesh`` of a QUAD4 model: connectivity ``[Ne, 4]``, the corner-wise kernels of ``csrc/quad4_mesh.hip``."""
+
+    abi, npe, kind = "hfem_quad4", 4, "QUAD4"
+    other = "TRI3 models: mesh_quality, max_feasible_step, quality_barrier, RAdaptiveSolver"
+    measure_f32_trials = True
 
 
 @dataclass
 class MeshQuality:
     """Element measure against the model's ``initial_node_coords``.  ``q`` [Ne]: signed mean-ratio quality (1 = equilateral,
-    <= 0 = inverted); ``det_ratio`` [Ne]: ``detJ / detJ_initial``; both fp64 on the device, elements in the caller's order."""
+    <= 0 = inverted); ``det_ratio`` [Ne]: ``detJ / detJ_initial``; both fp64 on the device, elements in the caller's order.
+    From ``quad4_mesh_quality``: the smallest corner value of each (``q`` = 1 for a square, module docstring)."""
     q: torch.Tensor
     det_ratio: torch.Tensor
     min_q: float
@@ -114,9 +150,8 @@ class MeshQuality:
 def mesh_quality(model) -> MeshQuality:
     """Per-element quality and ``detJ`` ratio of the current coordinates, with the minimum of each and the number of inverted
     elements (one measure launch; the summary is reduced on the device, deterministically)."""
-    q, r, s = _Mesh(model).measure()
-    s = s.tolist()
-    return MeshQuality(q=q, det_ratio=r, min_q=s[0], min_det_ratio=s[1], n_inverted=int(s[2]))
+    _Mesh.require(model, "mesh_quality")
+    return _Mesh(model).quality()
 
 
 def max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool = False):
@@ -124,30 +159,52 @@ def max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool
     at or above ``eta`` times its current value (``+inf`` if no step along ``d`` gets there).  ``d``: ``[n_x, 2]`` in the
     storage order of ``node_coords_free`` (any float dtype; used in fp64).  For any caller's optimiser: a trial step below it
     cannot invert an element.  ``as_tensor=True`` returns the 0-d fp64 device tensor without a host sync."""
-    _require_tri3(model, "max_feasible_step")
+    _Mesh.require(model, "max_feasible_step")
     _check_eta(eta)
-    mesh = _Mesh(model)
-    if tuple(d.shape) != (mesh.n_x, 2):
-        raise ValueError(f"d must have the shape of node_coords_free {(mesh.n_x, 2)}, got {tuple(d.shape)}")
-    d64 = d.detach().to(device=mesh.device, dtype=F64).contiguous()
-    a = mesh.step_bound(d64, eta)
-    return a if as_tensor else a.item()
+    return _Mesh(model).feasible_step(d, eta, as_tensor)
 
 
 def quality_barrier(model, weight: float = 1.0):
     """``Q = (weight / Ne) sum_e (1/q_e - 1)`` at the current coordinates and its gradient with respect to the free coordinate
     rows (fp64 ``[n_x, 2]``, storage order).  Accumulated with fp64 atomics: not bit-reproducible run to run."""
-    _require_tri3(model, "quality_barrier")
+    _Mesh.require(model, "quality_barrier")
     return _Mesh(model).barrier(weight)
+
+
+def quad4_mesh_quality(model) -> MeshQuality:
+    """``mesh_quality`` for a QUAD4 model: per element the smallest corner quality ``q = min_k q_k`` and the smallest corner
+    ratio ``min_k c_k / c_k_initial``, the minimum of each over the mesh and the number of inverted elements (a cell counts
+    when any corner has ``s c_k <= 0``: ``detJ`` is then <= 0 somewhere in it).  Deterministic."""
+    _QuadMesh.require(model, "quad4_mesh_quality")
+    return _QuadMesh(model).quality()
+
+
+def quad4_max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool = False):
+    """``max_feasible_step`` for a QUAD4 model: the largest ``alpha`` such that moving the free coordinate rows by
+    ``alpha * d`` keeps every corner cross product -- and with them ``detJ`` at every point of every cell -- at or above ``eta``
+    times its current value (``+inf`` if no step along ``d`` gets there).  Same arguments and return types."""
+    _QuadMesh.require(model, "quad4_max_feasible_step")
+    _check_eta(eta)
+    return _QuadMesh(model).feasible_step(d, eta, as_tensor)
+
+
+def quad4_quality_barrier(model, weight: float = 1.0):
+    """``Q = (weight / (4 Ne)) sum_e sum_k (1/q_ek - 1)`` over the corners of a QUAD4 model at the current coordinates and its
+    gradient with respect to the free coordinate rows (fp64 ``[n_x, 2]``, storage order).  Accumulated with fp64 atomics: not
+    bit-reproducible run to run."""
+    _QuadMesh.require(model, "quad4_quality_barrier")
+    return _QuadMesh(model).barrier(weight)
 
 
 @dataclass
 class RAdaptInfo:
-    """Outcome of ``RAdaptiveSolver.run()``, one entry per outer iteration (entry 0: the frozen-mesh solve at the start).
+    """Outcome of ``RAdaptiveSolver.run()`` / ``Quad4RAdaptiveSolver.run()``, one entry per outer iteration (entry 0: the
+    frozen-mesh solve at the start).
     ``energy``: ``Pi*`` (the energy at the solved ``u``); ``objective``: ``Pi* + Q`` (what the line search lowers; equal to
     ``energy`` without the barrier); ``grad_inf``: ``|g_x|_inf`` of the objective; ``alpha`` / ``alpha_max``: the accepted step
     and the step bound (0 / nan at entry 0); ``cg_iterations``; ``min_q`` against the initial mesh; ``step_ratio``: the smallest
-    ``detJ(x_k) / detJ(x_k-1)`` over the elements (>= ``eta`` by construction); ``trials``: line-search evaluations.
+    ``detJ(x_k) / detJ(x_k-1)`` over the elements (QUAD4: over their corners; >= ``eta`` by construction); ``trials``:
+    line-search evaluations.
     ``reason``: ``"gtol"``, ``"ftol"``, ``"max_outer"``, ``"line_search"`` (no trial passed the Armijo test, not even along the
     steepest descent: the coordinates are left at the last accepted point) or ``"stalled"`` (the accepted step rounded away)."""
     energy: List[float] = field(default_factory=list)
@@ -166,35 +223,29 @@ class RAdaptInfo:
         return len(self.energy) - 1
 
 
-class RAdaptiveSolver:
-    """Alternating r-adaptive minimisation of the TRI3 energy over ``u_free`` and ``node_coords_free`` (module docstring).
+class _RAdaptBase:
+    """The alternating loop both element kinds share: argument checks, the pieces of an outer iteration, the L-BFGS direction,
+    the line search and ``run``.  A subclass names its mesh class (``_mesh_cls``: which models it takes and which mesh kernels
+    run) and its displacement solver (``_solver_cls()``), and may refuse more in ``_check``."""
 
-    One outer iteration: (1) ``u <- FrozenMeshSolver.solve()``, warm-started (one solver instance; it refreshes itself when the
-    coordinates moved; fp64 models restart it from the true residual when that drifted, ``solve_and_grad``); (2) ``g_x = dE/dx_free`` at that ``u`` through ``loss_fn(model, b_force, t_force)`` and
-    ``torch.autograd.grad`` on ``node_coords_free`` alone (every force table enters as in training), plus ``dQ/dx`` when
-    ``quality_weight > 0``; (3) an L-BFGS direction over the x rows (``history`` pairs, a pair with ``s^T y <= 0`` skipped;
-    ``history=0``: steepest descent with a Barzilai-Borwein initial step); (4) ``alpha_max`` from the step-bound kernel, trial
-    ``min(alpha_init, 0.9 alpha_max)`` (``alpha_init`` = 1 with curvature pairs, the BB step without, ``0.9 alpha_max`` at the
-    very first step), halved until ``E(u_k, x + a d) + Q(x + a d)`` passes the Armijo test with ``c1`` -- one loss-only
-    evaluation per trial, ``x + a d`` written into ``node_coords_free`` in place.  A failed search retries once along the
-    steepest descent, then restores ``x`` and stops.
+    _mesh_cls = None
 
-    Stopping: ``gtol`` -- ``|g_x|_inf <= gtol * |Pi*_0 + Q_0| / L`` (``L``: diagonal of the initial mesh's bounding box, so the
-    test is free of units); ``ftol`` -- the objective fell by no more than ``ftol * max(|f_k|, |f_k+1|, 1)``; ``max_outer``
-    coordinate steps.  Only ``node_coords_free`` and ``u_free`` change: ``.grad`` of both, the Dirichlet rows and the fixed
-    coordinate rows are untouched.  fp32 models: fp64 inside the kernels, coordinates rounded once per trial on write-back (the
-    0.9 margin and ``eta`` absorb the rounding).  QUAD4 models and ``EnergyLoss2D(deterministic=True)`` are refused.
-    ``cg_precond`` is the ``precond`` of the inner ``FrozenMeshSolver`` (``"amg"``: the AMG host setup is done once, every
-    coordinate step redoes only its numeric setup)."""
+    @staticmethod
+    def _solver_cls():
+        raise NotImplementedError
+
+    @classmethod
+    def _check(cls, model, loss_fn):
+        cls._mesh_cls.require(model, cls.__name__)
+        if getattr(loss_fn, "deterministic", False):
+            raise NotImplementedError(f"{cls.__name__}: EnergyLoss2D(deterministic=True) has no solver counterpart "
+                                      "(the CG matrix-vector product accumulates with LDS atomics)")
 
     def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None, *,
                  history: int = 10, eta: float = 0.25, quality_weight: float = 0.0, cg_rtol: float = 1e-10,
                  gtol: float = 1e-9, ftol: float = 1e-12, max_outer: int = 50, max_ls: int = 20, c1: float = 1e-4,
                  max_restarts: int = 5, cg_precond: str = "block_jacobi"):
-        _require_tri3(model, "RAdaptiveSolver")
-        if getattr(loss_fn, "deterministic", False):
-            raise NotImplementedError("RAdaptiveSolver: EnergyLoss2D(deterministic=True) has no solver counterpart "
-                                      "(the CG matrix-vector product accumulates with LDS atomics)")
+        self._check(model, loss_fn)
         _check_eta(eta)
         if int(history) < 0 or int(max_outer) < 0 or int(max_ls) < 1 or int(max_restarts) < 0:
             raise ValueError("history, max_outer and max_restarts must be >= 0, max_ls >= 1")
@@ -204,14 +255,13 @@ class RAdaptiveSolver:
             raise ValueError("quality_weight must be finite and >= 0")
         if gtol < 0 or ftol < 0:
             raise ValueError("gtol and ftol must be >= 0")
-        from .solve import FrozenMeshSolver
-        self.mesh = _Mesh(model)
+        self.mesh = self._mesh_cls(model)
         self.model, self.loss_fn, self.b_force, self.t_force = model, loss_fn, b_force, t_force
         self.history, self.eta, self.quality_weight = int(history), float(eta), float(quality_weight)
         self.gtol, self.ftol, self.max_outer, self.max_ls, self.c1 = float(gtol), float(ftol), int(max_outer), int(max_ls), float(c1)
         self.max_restarts = int(max_restarts)
-        self.solver = FrozenMeshSolver(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol,
-                                       precond=cg_precond)
+        self.solver = self._solver_cls()(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol,
+                                         precond=cg_precond)
         self.last_solve = None                                 # SolveInfo of the latest displacement solve
         x0 = model.initial_node_coords.detach().double()
         self.length = float((x0.max(dim=0).values - x0.min(dim=0).values).norm()) if x0.numel() else 1.0
@@ -279,19 +329,26 @@ class RAdaptiveSolver:
             q = q + (a - b) * s
         return q
 
-    def _line_search(self, x0, d, f0, gd, alpha_init):
+    def _line_search(self, x0, d, f0, gd, alpha_init, coords0=None):
         """Backtracking Armijo along ``d`` from the rows ``x0`` (fp64 flat).  Returns (accepted alpha or None, alpha_max, f, trials);
-        on failure ``node_coords_free`` holds ``x0`` again."""
+        on failure ``node_coords_free`` holds ``x0`` again.  fp32 rows of a mesh class with ``measure_f32_trials`` (QUAD4;
+        ``coords0`` is ``x0`` by node id): the step bound
+        holds for ``x0 + alpha d``, the rows hold that rounded, and on an element that earlier steps shrank to the spacing of
+        the float grid the rounding moves ``detJ`` by more than the 0.9 margin leaves.  So each trial is measured against
+        ``coords0`` first, and one that keeps less than ``eta`` is halved like one that fails the Armijo test (it counts as
+        a trial; the energy is not evaluated)."""
         xf = self.model.node_coords_free
         d2 = d.reshape(xf.shape).contiguous()
         amax = float(self.mesh.step_bound(d2, self.eta).item())
         alpha = min(alpha_init, 0.9 * amax)
         if not math.isfinite(alpha):                          # no element shrinks along d and no curvature yet
             alpha = 1.0
+        measured = self.mesh.f32 and self.mesh.measure_f32_trials and coords0 is not None
         for t in range(self.max_ls):
             with torch.no_grad():
                 xf.copy_((x0 + alpha * d).reshape(xf.shape))   # rounds once for fp32 rows
-            f = self.objective()
+            kept = not measured or float(self.mesh.measure(x_ref=coords0, per_element=False)[2][1].item()) >= self.eta
+            f = self.objective() if kept else math.inf
             if math.isfinite(f) and f <= f0 + self.c1 * alpha * gd:
                 return alpha, amax, f, t + 1
             alpha *= 0.5
@@ -342,7 +399,7 @@ class RAdaptiveSolver:
                     alpha_init = float(torch.dot(last[0], last[0]).item()) / sy if sy > 0.0 else math.inf
                 else:
                     alpha_init = math.inf
-                alpha, amax, _, trials = self._line_search(x0, d, f, gd, alpha_init)
+                alpha, amax, _, trials = self._line_search(x0, d, f, gd, alpha_init, coords0)
                 if alpha is not None:
                     step = (alpha, amax, trials)
                     break
@@ -372,3 +429,64 @@ class RAdaptiveSolver:
                 info.reason = "ftol"
                 break
         return info
+
+
+class RAdaptiveSolver(_RAdaptBase):
+    """Alternating r-adaptive minimisation of the TRI3 energy over ``u_free`` and ``node_coords_free`` (module docstring).
+
+    One outer iteration: (1) ``u <- FrozenMeshSolver.solve()``, warm-started (one solver instance; it refreshes itself when the
+    coordinates moved; fp64 models restart it from the true residual when that drifted, ``solve_and_grad``); (2) ``g_x = dE/dx_free`` at that ``u`` through ``loss_fn(model, b_force, t_force)`` and
+    ``torch.autograd.grad`` on ``node_coords_free`` alone (every force table enters as in training), plus ``dQ/dx`` when
+    ``quality_weight > 0``; (3) an L-BFGS direction over the x rows (``history`` pairs, a pair with ``s^T y <= 0`` skipped;
+    ``history=0``: steepest descent with a Barzilai-Borwein initial step); (4) ``alpha_max`` from the step-bound kernel, trial
+    ``min(alpha_init, 0.9 alpha_max)`` (``alpha_init`` = 1 with curvature pairs, the BB step without, ``0.9 alpha_max`` at the
+    very first step), halved until ``E(u_k, x + a d) + Q(x + a d)`` passes the Armijo test with ``c1`` -- one loss-only
+    evaluation per trial, ``x + a d`` written into ``node_coords_free`` in place.  A failed search retries once along the
+    steepest descent, then restores ``x`` and stops.
+
+    Stopping: ``gtol`` -- ``|g_x|_inf <= gtol * |Pi*_0 + Q_0| / L`` (``L``: diagonal of the initial mesh's bounding box, so the
+    test is free of units); ``ftol`` -- the objective fell by no more than ``ftol * max(|f_k|, |f_k+1|, 1)``; ``max_outer``
+    coordinate steps.  Only ``node_coords_free`` and ``u_free`` change: ``.grad`` of both, the Dirichlet rows and the fixed
+    coordinate rows are untouched.  fp32 models: fp64 inside the kernels, coordinates rounded once per trial on write-back (the
+    0.9 margin and ``eta`` absorb the rounding).  QUAD4 models (``Quad4RAdaptiveSolver``, or ``r_adapt_``, which takes either)
+    and ``EnergyLoss2D(deterministic=True)`` are refused.
+    ``cg_precond`` is the ``precond`` of the inner ``FrozenMeshSolver`` (``"amg"``: the AMG host setup is done once, every
+    coordinate step redoes only its numeric setup)."""
+
+    _mesh_cls = _Mesh
+
+    @staticmethod
+    def _solver_cls():
+        from .solve import FrozenMeshSolver
+        return FrozenMeshSolver
+
+
+class Quad4RAdaptiveSolver(_RAdaptBase):
+    """``RAdaptiveSolver`` for QUAD4 models (``QuadShapeNN2D``): the same arguments, the same ``RAdaptInfo``, the same outer
+    loop, line search and stopping rules (one piece of code).  The displacement solve is ``Quad4FrozenMeshSolver``; the step
+    bound, the measure and the opt-in barrier are the corner-wise kernels of ``csrc/quad4_mesh.hip`` (module docstring): a step
+    keeps every corner cross product, and so ``detJ`` at every Gauss point, at or above ``eta`` of its value, and
+    ``step_ratio`` is the smallest corner ratio.  fp32 models: each rounded trial of the line search is measured against
+    ``x_k`` and halved while it keeps less than ``eta`` (``_line_search``), so the bound holds for the rows as stored.  Refuses TRI3 models, ``EnergyLoss2D(deterministic=True)`` and the planless
+    cross-check path (``loss_fn.quad4_planless``: the CG kernels run on the tile plan)."""
+
+    _mesh_cls = _QuadMesh
+
+    @staticmethod
+    def _solver_cls():
+        from .solve import Quad4FrozenMeshSolver
+        return Quad4FrozenMeshSolver
+
+    @classmethod
+    def _check(cls, model, loss_fn):
+        super()._check(model, loss_fn)
+        if getattr(loss_fn, "quad4_planless", False):
+            raise NotImplementedError("Quad4RAdaptiveSolver: quad4_planless=True has no solver counterpart (the CG kernels run "
+                                      "on the tile plan)")
+
+
+def r_adapt_(model, loss_fn, **kw) -> RAdaptInfo:
+    """One-shot ``RAdaptiveSolver(model, loss_fn, **kw).run()`` -- ``Quad4RAdaptiveSolver`` for a QUAD4 model:
+    ``model.node_coords_free`` and ``model.u_free`` are r-adapted in place."""
+    cls = Quad4RAdaptiveSolver if getattr(model, "nodes_per_element", 3) == 4 else RAdaptiveSolver
+    return cls(model, loss_fn, **kw).run()

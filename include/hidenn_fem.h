@@ -708,6 +708,38 @@ int hfem_tri3_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, c
                                   const float *x_fixed, const float *x_ref, double weight, double *value_acc,
                                   double *grad_acc, void *stream);
 
+/* ------------------------------------------------------------------ mesh validity for r-adaptivity (QUAD4)
+ * The bilinear-cell twins of the TRI3 entry points above (csrc/quad4_mesh.hip; Quad4RAdaptiveSolver in
+ * hidenn_fem_amd/radapt.py): the same argument lists, row maps, row types and argument checks, over conn [ne][4] (local nodes
+ * counter-clockwise, neighbour indices mod 4).  Corner cross product c_k = (X_k+1 - X_k) x (X_k-1 - X_k) = 4 detJ at corner k;
+ * detJ is affine over the reference square, so a cell is valid everywhere iff all four s c_k > 0, s = sign of c_0 + c_2 (twice
+ * the signed area) on x_ref.  q_k = 2 s c_k / (|X_k+1 - X_k|^2 + |X_k-1 - X_k|^2) (1 at a right-angled corner with equal
+ * sides), q = min_k q_k.
+ *   mesh_measure     q_out [ne] = q, ratio_out [ne] = min_k c_k / c_k_ref (both may be NULL); summary_out [3] (device) = {min q,
+ *                    min ratio, number of inverted elements (some s c_k <= 0)}.  Deterministic.
+ *   step_bound       alpha_out [1] (device) = the smallest alpha > 0 at which some corner of some element has
+ *                    c_k(x + alpha d) = eta c_k(x) (exact quadratics; +inf if there is none, 0 for a corner with c_k(x) = 0).
+ *                    Every Gauss-point detJ then keeps at least eta of its value.  Deterministic; launch-only.
+ *   quality_barrier  ACCUMULATES value_acc[0] += Q = (weight / (4 ne)) sum_e sum_k (1/q_ek - 1) and grad_acc [n_x][2] +=
+ *                    dQ/dx_free (either may be NULL).  fp64 atomics: not deterministic in the last bits.  Finite for valid
+ *                    elements only.                                                                                     */
+int hfem_quad4_mesh_measure(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                            const double *x_fixed, const double *x_ref, double *q_out, double *ratio_out, double *summary_out,
+                            void *stream);
+int hfem_quad4_mesh_measure_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                const float *x_fixed, const float *x_ref, double *q_out, double *ratio_out,
+                                double *summary_out, void *stream);
+int hfem_quad4_step_bound(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                          const double *x_fixed, const double *d, double eta, double *alpha_out, void *stream);
+int hfem_quad4_step_bound_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                              const float *x_fixed, const double *d, double eta, double *alpha_out, void *stream);
+int hfem_quad4_quality_barrier(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                               const double *x_fixed, const double *x_ref, double weight, double *value_acc, double *grad_acc,
+                               void *stream);
+int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                   const float *x_fixed, const float *x_ref, double weight, double *value_acc,
+                                   double *grad_acc, void *stream);
+
 /* ------------------------------------------------------------------ smoothed-aggregation AMG for the frozen-mesh solve
  * A symmetric V-cycle of smoothed aggregation over K_ff in 2x2 node blocks (hidenn_fem_amd/solve.py, precond="amg").
  * Host setup (amg.cpp, no GPU), once per mesh topology: conn [ne][npe] int32 (host_create: npe = 3, TRI3; host_create_ex: npe

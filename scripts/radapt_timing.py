@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """r-adaptive solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/radapt.py, csrc/tri3_mesh.hip).
+--quad: the same records for 10^6 QUAD4 cells (Quad4RAdaptiveSolver, csrc/quad4_mesh.hip).
 
 Records, as one JSON object:
   * the step-bound launch (init + element kernel), the measure launch (init + element kernel + finish), the barrier launch
@@ -9,10 +10,11 @@ Records, as one JSON object:
     (loss_fn + autograd.grad on node_coords_free): host clock, synchronised, median of repeats;
   * three outer iterations of RAdaptiveSolver: per iteration the warm-started CG solve and everything else (host clock);
   * the 36 k-element example-4 plate (200 x 100, fp64), without and with the quality barrier (weight 0.05): outer iterations,
-    Pi* before and after, reason, min q, wall time.
+    Pi* before and after, reason, min q, wall time (--quad: the plate without holes, 200 x 100 nodes of QUAD4 cells).
 Cache regime: the working sets stay in the 256 MB Infinity Cache.
 
     python scripts/radapt_timing.py [--grid 1001x501] [--reps 200] [--out profiles/radapt/radapt_timing_T1M.json]
+    python scripts/radapt_timing.py --quad [--grid 1415x708] [--out profiles/radapt/radapt_timing_quad4_T1M.json]
 """
 import argparse
 import json
@@ -24,9 +26,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from hidenn_fem_amd.loss import EnergyLoss2D
-from hidenn_fem_amd.mesh import generate_mesh, structured_tri_mesh
+from hidenn_fem_amd.mesh import generate_mesh, structured_quad_mesh, structured_tri_mesh
 from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
-from hidenn_fem_amd.radapt import RAdaptiveSolver, mesh_quality
+from hidenn_fem_amd.radapt import Quad4RAdaptiveSolver, RAdaptiveSolver, mesh_quality, quad4_mesh_quality
 
 F64 = torch.float64
 
@@ -87,33 +89,36 @@ class Clock:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", default="1001x501")
+    ap.add_argument("--grid", default="")
+    ap.add_argument("--quad", action="store_true", help="QUAD4 cells (default grid 1415x708: 10^6 cells)")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    nx, ny = (int(v) for v in a.grid.split("x"))
-    coords, conn, geom, bc, mn, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    nx, ny = (int(v) for v in (a.grid or ("1415x708" if a.quad else "1001x501")).split("x"))
+    mesher, Solver, quality = (structured_quad_mesh, Quad4RAdaptiveSolver, quad4_mesh_quality) if a.quad else \
+        (structured_tri_mesh, RAdaptiveSolver, mesh_quality)
+    coords, conn, geom, bc, mn, edges = mesher(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
     torch.manual_seed(0)
     m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
     lf = EnergyLoss2D(device=dev, dtype=F64)
     ne, nn = m.Nelems, m.Nnodes
-    rec = dict(mesh=f"{nx}x{ny} structured, jitter 0.2", n_elems=ne, n_nodes=nn, n_x_rows=int(m.node_coords_free.shape[0]),
+    rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=ne, n_nodes=nn, n_x_rows=int(m.node_coords_free.shape[0]),
                regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
 
-    s = RAdaptiveSolver(m, lf, max_outer=3)
+    s = Solver(m, lf, max_outer=3)
     mesh = s.mesh
     d = torch.randn(m.node_coords_free.shape, dtype=F64, device=dev) * 1e-3
     alpha = torch.empty((), dtype=F64, device=dev)
     bound_us = graphed_us(lambda: mesh.step_bound(d, 0.25, out=alpha), a.reps)
-    alg = 12 * ne + (4 + 16 + 16) * nn
+    alg = 4 * conn.shape[1] * ne + (4 + 16 + 16) * nn
     rec["step_bound"] = dict(us=bound_us, launches=2, algorithmic_bytes=alg, tb_per_s=alg / bound_us * 1e-6,
-                             note="12 B/element of connectivity + per node: x_src 4 B, x row 16 B, d row 16 B")
+                             note=f"{4 * conn.shape[1]} B/element of connectivity + per node: x_src 4 B, x row 16 B, d row 16 B")
     rec["measure"] = dict(us=graphed_us(lambda: mesh.measure(per_element=False), a.reps), launches=3)
     rec["measure_per_element_outputs"] = dict(us=graphed_us(lambda: mesh.measure(per_element=True), a.reps))
     rec["barrier"] = dict(us=graphed_us(lambda: mesh.barrier(1.0), a.reps), launches="2 fills + 1")
     energy_us = graphed_us(lambda: lf.value_and_grad_(m), a.reps)
-    rec["energy_value_and_grad"] = dict(us=energy_us, note="pair kernel + tile-energy sum launch")
+    rec["energy_value_and_grad"] = dict(us=energy_us, note="graded energy kernel + tile-energy sum launch")
     rec["step_bound_over_energy"] = bound_us / energy_us
     m.node_coords_free.grad = None
     m.u_free.grad = None
@@ -146,17 +151,21 @@ def main():
                             other_over_cg=(total - solve_clock.total) / solve_clock.total)
 
     # ---- the example-4 plate (36 k elements)
-    nodes, conn4, geom4, bc4, mn4, edges4 = generate_mesh(2.0, 1.0, [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)],
-                                                          {"up": 0, "down": 0, "right": 2, "left": 1}, 200, 100)
+    sides = {"up": 0, "down": 0, "right": 2, "left": 1}
+    if a.quad:
+        nodes, conn4, geom4, bc4, mn4, edges4 = structured_quad_mesh(200, 100, length=2.0, height=1.0, boundaries=sides)
+    else:
+        nodes, conn4, geom4, bc4, mn4, edges4 = generate_mesh(2.0, 1.0, [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)],
+                                                              sides, 200, 100)
     for key, w in (("example4_plate", 0.0), ("example4_plate_barrier_0.05", 0.05)):
         torch.manual_seed(0)
         p = PiecewiseLinearShapeNN2D(nodes.double(), conn4, boundary_mask=geom4, dirichlet_mask=bc4, u_fixed=0.0,
                                      neumann_edges=edges4).to(dev)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        pi = RAdaptiveSolver(p, lf, max_outer=50, quality_weight=w).run()
+        pi = Solver(p, lf, max_outer=50, quality_weight=w).run()
         torch.cuda.synchronize()
-        mq = mesh_quality(p)
+        mq = quality(p)
         rec[key] = dict(n_elems=p.Nelems, quality_weight=w, iterations=pi.iterations, reason=pi.reason,
                         energy_frozen=pi.energy[0], energy_final=pi.energy[-1], decrease=pi.energy[0] - pi.energy[-1],
                         cg_iterations=pi.cg_iterations, min_q_initial=pi.min_q[0], min_q_final=mq.min_q,
