@@ -7,6 +7,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+from cg_reference import _bsr, _mgs, _power
 from test_gpu_solve import _dev_forces, _golden_model, _loss, _oracle, _plate, _solve_cases, _structured
 
 pytestmark = pytest.mark.gpu
@@ -60,42 +61,6 @@ def test_assembled_kp_equals_the_matrix_free_apply_on_tile_major_delaunay_rows(c
 
 
 # ---------------------------------------------------------------- 3. the numeric setup vs a numpy restatement
-def _bsr(vals, ptr, col, rb, cb, ncols):
-    nb = len(ptr) - 1
-    return sp.bsr_matrix((vals.reshape(-1, rb, cb), col, ptr), shape=(nb * rb, ncols * cb)).tocsr()
-
-
-def _power(A, Dinv, n_rows):
-    i = np.arange(n_rows, dtype=np.uint64)
-    h = ((i + 1) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
-    v = (h >> np.uint64(8)).astype(np.float64) / 16777216.0 - 0.5
-    v /= np.linalg.norm(v)
-    nrm = 0.0
-    for _ in range(30):
-        w = Dinv @ (A @ v)
-        nrm = np.linalg.norm(w)
-        v = w / nrm
-    return 1.1 * nrm
-
-
-def _mgs(B, tol_rel=1e-10):
-    Q = B.copy()
-    R = np.zeros((3, 3))
-    n0 = np.linalg.norm(Q[:, 0])
-    for j in range(3):
-        for k in range(j):
-            R[k, j] = Q[:, k] @ Q[:, j]
-            Q[:, j] -= R[k, j] * Q[:, k]
-        nj = np.linalg.norm(Q[:, j])
-        if j > 0 and not nj > tol_rel * n0:
-            Q[:, j] = 0.0
-            R[j, :] = 0.0
-        else:
-            R[j, j] = nj
-            Q[:, j] /= nj
-    return Q, R
-
-
 @pytest.mark.parametrize("conv", ["reference", "physical"])
 def test_every_level_matches_a_numpy_restatement_and_coarse_operators_are_symmetric(conv):
     from hidenn_fem_amd.solve import FrozenMeshSolver
