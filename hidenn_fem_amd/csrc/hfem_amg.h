@@ -1,5 +1,5 @@
-// Smoothed-aggregation AMG for the frozen-mesh TRI3 solve: the host-side hierarchy (amg.cpp, no GPU) and the hooks the
-// CG driver (tri3_cg.hip) uses to run the V-cycle of tri3_amg.hip inside its iteration.
+// Smoothed-aggregation AMG for the frozen-mesh solve (TRI3 and QUAD4): the host-side hierarchy (amg.cpp, no GPU), the CG
+// status record, and the hooks the CG driver (cg.hip) uses to run the V-cycle of tri3_amg.hip inside its iteration.
 #pragma once
 #include <cstdint>
 #include <vector>

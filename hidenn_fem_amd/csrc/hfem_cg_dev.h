@@ -1,12 +1,18 @@
-// Device-side pieces the frozen-mesh solve's element kernels share (tri3_cg.hip, quad4_cg.hip): the status publication, the
-// last-workgroup hand-off and the fixed-order partial sum; and the launchers of the QUAD4 kernels, which the one PCG driver
-// (tri3_cg.hip) and the AMG numeric setup (tri3_amg.hip) call for npe == 4.
+// Device-side pieces the frozen-mesh solve's kernels share.  For every kernel with a last workgroup (cg.hip, tri3_cg.hip,
+// quad4_cg.hip): the status publication, the hand-off and the fixed-order partial sum.  For the four element kernels
+// (apply and block diagonal of tri3_cg.hip and quad4_cg.hip) the phases that do not depend on the element: the iteration
+// state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
+// block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
+// element, 3 or 4 corners, and the x row code.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
+// calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the index loads, the
+// staging of coordinates and p, and the slot loop.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "hfem_amg.h"
 #include "hfem_device.h"
 #include "hfem_plan_dev.h"
+#include "hfem_quad4_dev.h"
 
 namespace hfem {
 
@@ -47,25 +53,150 @@ __device__ __forceinline__ double ordered_sum(const double *v, int n, double *re
     return block_sum(a, red);
 }
 
-// ---------------------------------------------------------------- QUAD4 launchers (quad4_cg.hip)
-// What the driver binds of a solve, by value: the model's own QUAD4 tile plan (one element per slot, no pairing).
-struct Quad4CgArgs {
+// ---------------------------------------------------------------- q = K p: the phases both elements share
+// What an apply launch is: an iteration (st != NULL: p = z + beta p_old, stored to the other buffer of the ping-pong pair
+// picked by the parity of kIter) or the standalone apply (st == NULL: p = z as given, nothing stored).
+struct CgIter {
+    double beta = 0.0;
+    const double2 *p_old = nullptr;
+    double2 *p_new = nullptr;
+};
+
+__device__ __forceinline__ CgIter cg_iter(const double *st, double2 *pbuf0, double2 *pbuf1) {
+    CgIter it;
+    if (st) {
+        const int par = ((long long)st[kIter]) & 1;
+        it.beta = st[kBeta];
+        it.p_old = par ? pbuf1 : pbuf0;
+        it.p_new = par ? pbuf0 : pbuf1;
+    }
+    return it;
+}
+
+// One gathered row of p through the u row map: 0 on a fixed row (row < 0), else z, plus beta p_old when iterating.
+__device__ __forceinline__ double2 gather_p(const CgIter &it, const double2 *__restrict__ z, int row) {
+    double2 p = make_double2(0.0, 0.0);
+    if (row >= 0) {
+        p = z[row];
+        if (it.p_old) {
+            const double2 o = it.p_old[row];
+            p.x = __builtin_fma(it.beta, o.x, p.x);
+            p.y = __builtin_fma(it.beta, o.y, p.y);
+        }
+    }
+    return p;
+}
+
+// Owned free rows: q (one 16-byte store per row), and (iterations) the new p into the other buffer.
+template <int BLOCK, int NPT>
+__device__ __forceinline__ void store_q_p(const int2 (&s)[NPT], int n_owned, const double *acc0, const double *acc1,
+                                          const double2 *nd_p, double2 *__restrict__ q, double2 *p_new) {
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = threadIdx.x + j * BLOCK;
+        if (l < n_owned && s[j].y >= 0) {
+            q[s[j].y] = make_double2(acc0[l], acc1[l]);
+            if (p_new) p_new[s[j].y] = nd_p[l];
+        }
+    }
+}
+
+// The epilogue, in two parts around the caller's barrier and write-out.  First: every wave's sum of the home elements'
+// energy into red[].
+__device__ __forceinline__ void wave_energy(double e_loc, double *red) {
+    const double w = wave_sum(e_loc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+}
+
+// Second: the tile's partial of p^T q; the last workgroup (ticket) sums the partials in tile order and writes pq_out[0]
+// (standalone) or alpha and kPq, and halts with breakdown where K is not positive definite on p.  red: BLOCK / 64 doubles
+// + one flag word.
+template <int BLOCK>
+__device__ __forceinline__ void apply_finish(double *red, double *__restrict__ partials, int slot, unsigned *ticket, int n_tiles,
+                                             double *st, double *host, double *pq_out) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        double tile_e = 0.0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) tile_e += red[w];
+        put_partial(partials + slot, 2.0 * tile_e);         // p^T K_tile p over the home elements
+    }
+    if (!last_block(ticket, (unsigned)n_tiles, reinterpret_cast<int *>(red + BLOCK / 64))) return;
+    const double pq = ordered_sum<BLOCK>(partials, n_tiles, red);
+    if (tid == 0) {
+        if (!st) {
+            pq_out[0] = pq;
+            return;
+        }
+        const double alpha = st[kRho] / pq;
+        st[kPq] = pq;
+        st[kAlpha] = alpha;
+        if (!(pq > 0.0) || !isfinite(alpha)) {              // K not positive definite on p, or a non-finite scalar
+            st[kHalted] = 1.0;
+            st[kReason] = kBreakdown;
+            publish(st, host);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- block Jacobi and the AMG fine level
+// The symmetric 2x2 block [[a, b], [b, c]] of free row `row` (3 doubles) into diag (optional), its inverse into dinv; the
+// identity for precond "none" or a block that is not positive definite.
+__device__ __forceinline__ void store_jacobi_block(double *__restrict__ diag, double *__restrict__ dinv, int row, int precond,
+                                                   double a, double b, double c) {
+    const size_t r = (size_t)row * 3;
+    if (diag) { diag[r] = a; diag[r + 1] = b; diag[r + 2] = c; }
+    const double det = a * c - b * b;
+    if (precond && det > 0.0 && isfinite(det)) {
+        const double inv = 1.0 / det;
+        dinv[r] = c * inv; dinv[r + 1] = -b * inv; dinv[r + 2] = a * inv;
+    } else {
+        dinv[r] = 1.0; dinv[r + 1] = 0.0; dinv[r + 2] = 1.0;
+    }
+}
+
+// Columns (a, x) and (a, y) of K_e: the element's u-gradient at u_a = e_x (gu) and at u_a = e_y (hu), u_b = 0 (b != a).
+// By symmetry these are also rows (a, x) and (a, y).
+template <bool PHYS>
+__device__ __forceinline__ void unit_columns(const double2 (&X)[3], int a, const Tri3Consts &k, double2 (&gu)[3], double2 (&hu)[3]) {
+    const double2 o = make_double2(0.0, 0.0), ex = make_double2(1.0, 0.0), ey = make_double2(0.0, 1.0);
+    double2 gx[3];
+    tri3_element<true, false, PHYS>(X[0], X[1], X[2], a == 0 ? ex : o, a == 1 ? ex : o, a == 2 ? ex : o, k, gx, gu);
+    tri3_element<true, false, PHYS>(X[0], X[1], X[2], a == 0 ? ey : o, a == 1 ? ey : o, a == 2 ? ey : o, k, gx, hu);
+}
+
+template <bool PHYS>
+__device__ __forceinline__ void unit_columns(const double2 (&X)[4], int a, const Tri3Consts &k, double2 (&gu)[4], double2 (&hu)[4]) {
+    const double2 o = make_double2(0.0, 0.0), ex = make_double2(1.0, 0.0), ey = make_double2(0.0, 1.0);
+    const double2 Ux[4] = {a == 0 ? ex : o, a == 1 ? ex : o, a == 2 ? ex : o, a == 3 ? ex : o};
+    const double2 Uy[4] = {a == 0 ? ey : o, a == 1 ? ey : o, a == 2 ? ey : o, a == 3 ? ey : o};
+    quad4_element_u<PHYS>(X, Ux, k, gu);
+    quad4_element_u<PHYS>(X, Uy, k, hu);
+}
+
+// A coordinate row by its x row code: a free row, or fixed row -1 - code.
+__device__ __forceinline__ double2 x_row(const double2 *x_free, const double2 *x_fixed, int32_t code) {
+    return code >= 0 ? x_free[code] : x_fixed[-1 - code];
+}
+
+// ---------------------------------------------------------------- element launchers (tri3_cg.hip, quad4_cg.hip)
+// What the driver binds of a solve, by value.  block: threads per tile of a paired TRI3 plan (QUAD4 tiles are 256).
+struct CgElemArgs {
     const hfem_plan *plan = nullptr;
-    int n_tiles = 0;
+    int n_tiles = 0, block = 256;
     bool phys = false;
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     Tri3Consts k{};
     size_t lds = 0;
     hipStream_t s = nullptr;
 };
-// q = K p (the contract of tri3_cg_apply_kernel: st != NULL an iteration, st == NULL the standalone apply)
-void launch_quad4_cg_apply(const Quad4CgArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
+// q = K p (st != NULL an iteration, st == NULL the standalone apply)
+void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
+                          unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_quad4_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                            unsigned *ticket, double *st, double *host, double *pq_out);
-// 2x2 diagonal blocks of K and their inverses (the layout and the identity fallback of tri3_cg_diag_kernel)
-void launch_quad4_cg_diag(const Quad4CgArgs &A, double *diag, double *dinv, int precond);
-// fine-level K_ff of the AMG hierarchy over a QUAD4 fan (four fan_slot entries per record)
-void launch_quad4_amg_assemble(int32_t n, const int32_t *fan_ptr, const int32_t *fan_elem, const int32_t *fan_corner,
-                               const int32_t *fan_slot, const int32_t *conn_x, const double2 *x_free, const double2 *x_fixed,
-                               const int32_t *a_ptr, double *a_val, const Tri3Consts &k, bool phys, hipStream_t s);
+// 2x2 diagonal blocks of K and their inverses (store_jacobi_block)
+void launch_tri3_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
+void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 
 }  // namespace hfem

@@ -1,4 +1,5 @@
-// QUAD4 element closed forms shared by the energy kernels (quad4.hip) and the frozen-mesh solve (quad4_cg.hip).
+// QUAD4 element closed forms shared by the energy kernels (quad4.hip) and the frozen-mesh solve (quad4_cg.hip;
+// hfem_cg_dev.h for the unit-displacement columns of the diag and AMG assembly kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 

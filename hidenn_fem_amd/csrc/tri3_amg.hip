@@ -1,10 +1,11 @@
-// Smoothed-aggregation AMG for the frozen-mesh TRI3 solve, gfx950 (MI355X): the numeric setup of the hierarchy whose patterns
-// amg.cpp built, and the symmetric V-cycle that preconditions CG (tri3_cg.hip, hfem_cg_iterate_amg).  All fp64.
+// Smoothed-aggregation AMG for the frozen-mesh solve (TRI3 and QUAD4), gfx950 (MI355X): the numeric setup of the hierarchy
+// whose patterns amg.cpp built, and the symmetric V-cycle that preconditions CG (cg.hip, hfem_cg_iterate_amg).  All fp64.
 //
 // Numeric setup (hfem_amg_setup, at every solver refresh):
-//   amg_assemble_kernel   K_ff in 2x2 blocks: one thread per free row walks the row's element fan in a fixed order and adds
-//                         that corner's 2x6 rows of K_e (two tri3_element calls at unit displacements, the closed forms of
-//                         the CG apply, both gradient conventions) into the row's blocks.  No atomics: bit-deterministic.
+//   amg_assemble_kernel   K_ff in 2x2 blocks, NPE = 3 | 4 corners per element: one thread per free row walks the row's element
+//                         fan in ascending element order and adds that corner's 2 x 2 NPE rows of K_e (unit_columns,
+//                         hfem_cg_dev.h: the closed forms of the CG apply at unit displacements, both gradient conventions)
+//                         into the row's blocks through NPE fan slots per record.  No atomics: bit-deterministic.
 //   amg_dinv_kernel       inverse of every (symmetrised) diagonal block; an all-zero row counts as an identity row.
 //   amg_power_*           lambda_max(D^-1 A) by kAmgPowerIters power steps from a fixed start; lambda_hat = 1.1 x estimate.
 //   amg_tentative_kernel  one thread per aggregate: modified Gram-Schmidt of the aggregate's near-null-space rows (2k x 3 on
@@ -48,12 +49,8 @@ __device__ __forceinline__ int32_t find_slot(const int32_t *__restrict__ col, in
     return lo;
 }
 
-__device__ __forceinline__ double2 x_row(const double2 *x_free, const double2 *x_fixed, int32_t code) {
-    return code >= 0 ? x_free[code] : x_fixed[-1 - code];
-}
-
 // ---------------------------------------------------------------- assembly (fine level, 2x2 blocks)
-template <bool PHYS>
+template <int NPE, bool PHYS>
 __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
                                                               const int32_t *__restrict__ fan_elem,
                                                               const int32_t *__restrict__ fan_corner,
@@ -67,18 +64,16 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
     if (r >= n) return;
     for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
         *reinterpret_cast<double4 *>(a_val + 4 * (size_t)s) = make_double4(0.0, 0.0, 0.0, 0.0);
-    const double2 o = make_double2(0.0, 0.0), ex = make_double2(1.0, 0.0), ey = make_double2(0.0, 1.0);
     for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
         const int32_t e = fan_elem[f], a = fan_corner[f];
-        const double2 X0 = x_row(x_free, x_fixed, conn_x[3 * (size_t)e]), X1 = x_row(x_free, x_fixed, conn_x[3 * (size_t)e + 1]),
-                      X2 = x_row(x_free, x_fixed, conn_x[3 * (size_t)e + 2]);
-        // column (a, x) and (a, y) of K_e = rows (a, x) and (a, y) by symmetry
-        double2 gx[3], gu[3], hu[3];
-        tri3_element<true, false, PHYS>(X0, X1, X2, a == 0 ? ex : o, a == 1 ? ex : o, a == 2 ? ex : o, k, gx, gu);
-        tri3_element<true, false, PHYS>(X0, X1, X2, a == 0 ? ey : o, a == 1 ? ey : o, a == 2 ? ey : o, k, gx, hu);
+        const int32_t *cx = conn_x + NPE * (size_t)e;
+        double2 X[NPE], gu[NPE], hu[NPE];
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            const int32_t s = fan_slot[3 * (size_t)f + b];
+        for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
+        unit_columns<PHYS>(X, a, k, gu, hu);                   // column (a, x) and (a, y) of K_e = rows (a, x) and (a, y)
+#pragma unroll
+        for (int b = 0; b < NPE; ++b) {
+            const int32_t s = fan_slot[NPE * (size_t)f + b];
             if (s < 0) continue;
             double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
             double4 v = *p;
@@ -662,18 +657,19 @@ hfem::Tri3Consts consts(const double mat[4], double W) { return hfem::make_const
 
 void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, hipStream_t s) {
     const DevLevel &L = a->lv[0];
-    if (a->npe == 4) {                                       // QUAD4 fan (quad4_cg.hip); the 2x2 rule's weights are 1: W is not read
-        hfem::launch_quad4_amg_assemble(L.n, a->fan_ptr, a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free,
-                                        (const double2 *)x_fixed, L.a_ptr, L.a_val, consts(mat, 1.0), a->phys, s);
-        return;
-    }
-    const hfem::Tri3Consts k = consts(mat, W);
-#define HFEM_AMG_ASM(PH)                                                                                                      \
-    hipLaunchKernelGGL(hfem::amg_assemble_kernel<PH>, grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr, a->fan_elem,         \
+    const bool quad = a->npe == 4;
+    const hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);  // QUAD4: the 2x2 rule's weights are 1, W is not read
+#define HFEM_AMG_ASM(NPE, PH)                                                                                                 \
+    hipLaunchKernelGGL((hfem::amg_assemble_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr, a->fan_elem,  \
                        a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed, L.a_ptr,      \
                        L.a_val, k)
-    if (a->phys) HFEM_AMG_ASM(true);
-    else HFEM_AMG_ASM(false);
+    if (quad) {
+        if (a->phys) HFEM_AMG_ASM(4, true);
+        else HFEM_AMG_ASM(4, false);
+    } else {
+        if (a->phys) HFEM_AMG_ASM(3, true);
+        else HFEM_AMG_ASM(3, false);
+    }
 #undef HFEM_AMG_ASM
 }
 

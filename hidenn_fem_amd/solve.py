@@ -3,7 +3,8 @@
 With the nodal coordinates held fixed the HiDeNN-FEM energy is classical P1 finite elements and exactly quadratic in the
 displacements, ``E(u) = 1/2 u^T K u - f^T u`` (K symmetric positive definite on the free rows once Dirichlet rows exist), so
 its minimum is the linear system ``K_ff u = f - K_fd u_d``.  ``FrozenMeshSolver`` solves it by matrix-free preconditioned
-conjugate gradients on the GPU (``csrc/tri3_cg.hip``): ``K p`` is the displacement half of the tuned energy kernel at
+conjugate gradients on the GPU (driver ``csrc/cg.hip``, element kernels ``csrc/tri3_cg.hip``): ``K p`` is the
+displacement half of the tuned energy kernel at
 ``u = p`` with no forces, the residual ``r = -dE/du`` comes from the graded energy kernel itself (so every force table of
 ``EnergyLoss2D`` -- default traction, a traction or body-force callable, nonzero ``u_fixed`` -- enters with no extra code),
 and each iteration is two launches whose scalars (alpha, beta, the stopping test) are reduced on the device.  Iterations run
@@ -14,8 +15,9 @@ the fixed-mesh FEM solution to compare an r-adapted energy against, and a warm s
 atomics of the matrix-vector product make iterates differ in the last bits from run to run (the scalars are reduced in a
 fixed order; the deterministic energy path has no solver counterpart).  ``FrozenMeshSolver`` takes TRI3 models; its kernels
 run on a paired-slot tile plan (the model's own, or one built for the solver when the planner chose one element per slot for
-this mesh).  ``Quad4FrozenMeshSolver`` is the same solver for QUAD4 models (``csrc/quad4_cg.hip``: the matrix-vector product,
-the block diagonal and the AMG fine level for bilinear cells on the model's own QUAD4 plan; the residual from
+this mesh).  ``Quad4FrozenMeshSolver`` is the same solver for QUAD4 models (``csrc/quad4_cg.hip``: the matrix-vector product
+and the block diagonal for bilinear cells on the model's own QUAD4 plan; the AMG fine level from the four-corner instance of
+the assembly kernel of ``csrc/tri3_amg.hip``; the residual from
 ``hfem_quad4_energy_plan_ex``); everything above the element level -- vector kernels, stopping rule, graph replay, the AMG
 hierarchy -- is shared.  ``solve_displacement_`` picks the class by ``model.nodes_per_element``.
 """
@@ -269,8 +271,8 @@ class FrozenMeshSolver(_FrozenSolverBase):
 
 class Quad4FrozenMeshSolver(_FrozenSolverBase):
     """``FrozenMeshSolver`` for QUAD4 models (``QuadShapeNN2D``): the same arguments, the same contract, the same
-    ``SolveInfo``.  ``K p``, the block-Jacobi blocks and the AMG fine level come from ``csrc/quad4_cg.hip`` on the model's own
-    QUAD4 tile plan (no pairing); the residual and ``||f||`` from the graded QUAD4 energy kernel on fp64 rows
+    ``SolveInfo``.  ``K p`` and the block-Jacobi blocks come from ``csrc/quad4_cg.hip`` on the model's own QUAD4 tile plan (no
+    pairing), the AMG fine level from the four-corner instance of ``csrc/tri3_amg.hip``'s assembly kernel; the residual and ``||f||`` from the graded QUAD4 energy kernel on fp64 rows
     (``hfem_quad4_energy_plan_ex``), so default forces, a body-force callable (evaluated at the 2x2 reference Gauss points, as
     ``EnergyLoss2D`` does), a traction callable and nonzero ``u_fixed`` enter with no solver code of their own.  fp32 models
     solve in fp64 (rows widened per refresh, ``u_free`` rounded once on write-back).  Refuses TRI3 models,

@@ -648,9 +648,10 @@ int hfem_rectq4_mse_f32(int device, const float *gx, int64_t nx, const float *gy
  * quadratic in u there, E(u) = 1/2 u^T K u - f^T u, so K p = dE/du(p) with no forces and r = -dE/du(u): the caller
  * forms g0 = dE/du(u0) and g_zero = dE/du(u_free = 0) with hfem_tri3_energy_plan (fp64 rows, the forces of its loss) and
  * the solver never sees the forces.  Paired-slot TRI3 plans (the default), or QUAD4 plans as hfem_quad4_energy_plan_ex takes
- * them (csrc/quad4_cg.hip: g0 / g_zero from that entry point, W is not read -- the 2x2 rule's weights are 1; the vector
- * kernels, the status record and the halt logic are shared); all vectors are fp64 free u rows [n_u][2]
- * in the plan's storage order.  Two launches per iteration (csrc/tri3_cg.hip): q = K p with p = z + beta p_old formed in
+ * them (g0 / g_zero from that entry point, W is not read -- the 2x2 rule's weights are 1).  The driver -- the vector
+ * kernels, the status record, the halt logic -- is csrc/cg.hip and knows no element; q = K p and the Jacobi blocks are the
+ * element kernels of csrc/tri3_cg.hip or csrc/quad4_cg.hip.  All vectors are fp64 free u rows [n_u][2]
+ * in the plan's storage order.  Two launches per iteration: q = K p with p = z + beta p_old formed in
  * the gather, then u += alpha p, r -= alpha q, z = D^-1 r; alpha, beta and the stopping test |r|_2 <= max(rtol |f|_2, atol)
  * are reduced on the device in a fixed order.  Once halted (converged, max_iter, breakdown: p^T K p <= 0 or a non-finite
  * scalar) later iterations do nothing on the device: u keeps the last good iterate.
@@ -757,7 +758,7 @@ int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, 
  * Device hierarchy (tri3_amg.hip, fp64), from a host setup (which may be destroyed afterwards):
  *   assemble    level-0 A values (K_ff, 2x2 blocks, row-major, in the host pattern) at the coordinates x_free / x_fixed (fp64
  *               rows; mat, W as hfem_cg_setup).  One thread per row, no atomics: bit-deterministic.  A QUAD4 host setup
- *               selects the QUAD4 instance (csrc/quad4_cg.hip); everything below the assembly is the same code.
+ *               selects the four-corner instance of the same kernel; everything below the assembly is the same code.
  *   setup       assemble + the numeric hierarchy (block-diagonal inverses, lambda_max(D^-1 A) by power iteration, tentative
  *               and smoothed prolongators, Galerkin products); writes the coarsest level as a dense row-major N x N matrix
  *               into coarse_out (an all-zero row gets a 1 on the diagonal).  The caller inverts it and hands the inverse

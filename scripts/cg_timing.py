@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Frozen-mesh CG solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/solve.py, csrc/tri3_cg.hip).
+"""Frozen-mesh CG solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/solve.py, csrc/cg.hip,
+csrc/tri3_cg.hip).
 
 Records, as one JSON object:
   * the standalone apply launch (q = K p) and its fraction of 8 TB/s on the algorithmic bytes 12 Ne + 48 Nn (slot records,

@@ -1,6 +1,6 @@
 """Plain-numpy references of the frozen-mesh solve's inner workings, shared by the tests (not a conftest): block-sparse
 products that work in ``np.longdouble`` (scipy's sparse types do not), the PCG recursion in the order the driver of
-csrc/tri3_cg.hip runs it, the smoothed-aggregation V-cycle as ``cycle_level`` of csrc/tri3_amg.hip runs it, the scalar
+csrc/cg.hip runs it, the smoothed-aggregation V-cycle as ``cycle_level`` of csrc/tri3_amg.hip runs it, the scalar
 Chebyshev coefficients of ``amg_power_finish_kernel``, and the helpers of the numeric-setup restatement
 (``_bsr``, ``_power``, ``_mgs``; test_gpu_amg.py imports them back).
 
@@ -171,7 +171,7 @@ def pcg_deviation(lo, hi):
 
 def block_jacobi(diag, dtype, identity=False):
     """M of the block-Jacobi preconditioner from the solver's ``diag`` rows {K_xx, K_xy, K_yy}: the adjugate inverse of every
-    2x2 block, the identity for ``precond="none"`` or a block that is not positive definite (tri3_cg_diag_kernel)."""
+    2x2 block, the identity for ``precond="none"`` or a block that is not positive definite (store_jacobi_block, csrc/hfem_cg_dev.h)."""
     d = np.asarray(diag, dtype=dtype)
     a, b, c = d[:, 0], d[:, 1], d[:, 2]
     det = a * c - b * b

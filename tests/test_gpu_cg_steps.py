@@ -1,4 +1,5 @@
-"""The PCG recursion and the stopping rule of the frozen-mesh solve (csrc/tri3_cg.hip, csrc/quad4_cg.hip), step by step:
+"""The PCG recursion and the stopping rule of the frozen-mesh solve (csrc/cg.hip; element kernels csrc/tri3_cg.hip,
+csrc/quad4_cg.hip), step by step:
 every slot of the status record and ``u`` after every iteration against ``cg_reference.pcg_steps`` in longdouble on an
 operator that does not come from the code under test (the dense oracle Hessian; for AMG the assembled K_ff, which
 test_gpu_amg.py holds to the oracle, and the reference V-cycle on the arrays read back from the device), the recursion's |r|

@@ -1,4 +1,4 @@
-"""Frozen-mesh displacement solve (hidenn_fem_amd/solve.py, csrc/tri3_cg.hip): the CG matrix-vector product against the
+"""Frozen-mesh displacement solve (hidenn_fem_amd/solve.py, csrc/cg.hip, csrc/tri3_cg.hip): the CG matrix-vector product against the
 graded energy kernel, the block-Jacobi blocks and the solution against the dense oracle Hessian of the reference chain, the
 minimum of the graded energy, the model contract, graph replay / halt and breakdown."""
 import numpy as np
