@@ -50,6 +50,38 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// DPP control of v_mov_b32_dpp: row_shl:N -- within a row of 16 lanes, lane i reads lane i + N (lanes past the row read 0).
+constexpr int kDppRowShl = 0x100;
+template <int N> __device__ __forceinline__ double row_shl(double v) {
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), kDppRowShl + N, 0xF, 0xF, true),
+                            __builtin_amdgcn_update_dpp(0, __double2loint(v), kDppRowShl + N, 0xF, 0xF, true));
+}
+
+// wave_sum without the LDS unit (__shfl_down is ds_bpermute_b32: six dependent LDS round trips, queued behind whatever the
+// wave has in flight there).  Lane 0's association tree is wave_sum's -- v[i] + v[i+32], then +16, +8, +4, +2, +1 -- so its
+// result has the same bits; the other lanes hold garbage.  v_permlane32_swap / v_permlane16_swap of a register with its own
+// copy leave "mine" in one result and "lane + 32" / "lane + 16" in the other (lanes 0-31 / rows 0 and 2); below a row of 16
+// lanes, DPP row_shl.
+__device__ __forceinline__ double wave_sum_valu(double v) {
+    unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    {
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        v = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+        lo = (unsigned)__double2loint(v); hi = (unsigned)__double2hiint(v);
+    }
+    {
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+    }
+    v += row_shl<8>(v);
+    v += row_shl<4>(v);
+    v += row_shl<2>(v);
+    v += row_shl<1>(v);
+    return v;
+}
+
 // Block sum; `scratch` holds >= blockDim.x/64 doubles in LDS.  Result in thread 0.
 __device__ __forceinline__ double block_sum(double v, double *scratch) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -270,9 +270,11 @@ __device__ __forceinline__ void mem_phase_end() {
 // L2).  Map block -> tile so that each XCD walks one contiguous run of the
 // Morton-ordered tiles: neighbouring tiles share halo nodes, which then hit the
 // same L2.  Bijective for any grid size; placement only affects speed.
+// XCD x starts at x * q + min(x, r) (= x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q, written without the select: the
+// compiler turns that one into branches, which split a kernel's entry block and with it the scalar loads of its arguments).
 __device__ __forceinline__ int xcd_tile(int b, int nb) {
     const int q = nb >> 3, r = nb & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+    return x * q + min(x, r) + (b >> 3);
 }
 
 }  // namespace hfem

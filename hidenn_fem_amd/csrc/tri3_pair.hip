@@ -57,19 +57,16 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
         bid -= lag.pg_blocks;                           // a multiple of 8: the block -> XCD mapping of the tiles is unchanged
     }
     const int n_launch = (int)gridDim.x - (lag.prev ? 1 : 0) - (PG ? lag.pg_blocks : 0);
-    if (lag.prev && bid == n_launch) {                  // HFEM_FLAG_SUM_PREVIOUS: reduce the previous launch's tile energies
-        double v = 0.0;
-        if (tid < 256)
-            for (int i = tid; i < lag.prev_n; i += 256) v += lag.prev[i];
-        const double tot = block_sum(v, red);
-        if (tid == 0) lag.out[0] = tot;
-        return;
-    }
-    const int slot = xcd_tile(bid, n_launch);
+    // ONE scalar round trip in front of the index loads: no branch splits the entry block, so every kernel argument the
+    // prologue needs is requested before the first wait.  The sum workgroup of a HFEM_FLAG_SUM_PREVIOUS launch (block
+    // n_launch, one past the tiles) is told apart AFTER the index loads are issued: it takes the last tile's index, its loads
+    // stay inside the plan arrays and are dropped.
+    const bool sum_wg = lag.prev && bid == n_launch;
+    const int slot = xcd_tile(sum_wg ? n_launch - 1 : bid, n_launch);
     mem_phase_begin();                                  // prologue at raised wave priority (hfem_plan_dev.h)
-    // span stamps (hfem_plan_set_span_stamps, off by default): when this workgroup started -- scalar registers only
-    unsigned long long t_start = 0;
-    if (pd.span) t_start = __builtin_amdgcn_s_memrealtime();
+    // span stamps (hfem_plan_set_span_stamps, off by default): when this workgroup started -- scalar registers only; taken
+    // unconditionally (a branch on pd.span would split the block)
+    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     // ---- row maps first, from the tile index alone (uniform node stride, plan.cpp): these loads and the descriptor's are in
     //      flight together.  Unguarded: lanes past n_node read padding / the next tile's records -- valid rows, never stored.
     int2 s[NPT];
@@ -86,6 +83,23 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
         const size_t i = rec0 + min(tid + j * col_stride, pd.elem_stride - 1);
         w0[j] = pd.elem_pack[i];
         w1[j] = pd.elem_pack_hi[i];
+    }
+    // ---- accumulators cleared NOW, under the first memory round trip (the LDS is idle): up to the accumulator stride, which
+    //      needs no load -- rows n_owned <= l < cap_owned are cleared as well and never read
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if ((CAPO > 0 && (j + 1) * BLOCK <= CAPO) || l < cap_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; acc3[l] = 0.0; }
+    }
+    __builtin_amdgcn_sched_barrier(0);                  // ... in front of everything that waits for a load
+    if (sum_wg) {                                       // HFEM_FLAG_SUM_PREVIOUS: reduce the previous launch's tile energies
+        mem_phase_end();
+        double v = 0.0;
+        if (tid < 256)
+            for (int i = tid; i < lag.prev_n; i += 256) v += lag.prev[i];
+        const double tot = block_sum(v, red);
+        if (tid == 0) lag.out[0] = tot;
+        return;
     }
     // HFEM_FLAG_PEER_PUT: a boundary tile will publish the new rows of its interface nodes at write-out -- where each row sits
     // in the payload is looked up NOW, behind the row maps and under the wait below, not as a late dependent load
@@ -135,7 +149,6 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
             nd_xy[l] = make_double2((double)vx[j].x, (double)vx[j].y);
             nd_uv[l] = make_double2((double)vu[j].x, (double)vu[j].y);
         }
-        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; acc3[l] = 0.0; }
     }
     __syncthreads();
     mem_phase_end();
@@ -239,7 +252,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
         if (l1 < n_owned) add_row(l1, gx[1], gu[1]);
     }
     {
-        const double w = wave_sum(e_loc);
+        const double w = wave_sum_valu(e_loc);           // no LDS round trips behind the wave's last atomics
         if ((tid & 63) == 0) red[tid >> 6] = w;          // one slot per wave: summed in wave order below
     }
     // every load has long returned; saying so keeps the compiler from guarding each write-out store with a vmcnt(0) of its

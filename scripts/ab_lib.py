@@ -4,6 +4,8 @@ processes on the same box: the T1M paired kernel (same buffers / rotating sets),
 QUAD4 kernel, kernel only (hipGraph of K launches between HIP events, median of 5).
 
     python scripts/ab_lib.py libhidenn_hip.so libhidenn_hip_noprio.so [more .so ...] [rounds]
+
+AB_LEGS=t1m in the environment: only the first leg (T1M paired kernel, same buffers / rotating sets) -- many builds in one short run.
 """
 import ctypes as C
 import json
@@ -99,6 +101,9 @@ def child(lib_name):
 
     t1m = structured_tri_mesh(1001, 501, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=f64)
     a, b = case(t1m, f64, False, 10, 8)
+    if os.environ.get("AB_LEGS") == "t1m":
+        print(json.dumps(dict(lib=lib_name, t1m_replayed_us=a, t1m_rotating_us=b)), flush=True)
+        return
     f = fused_step(t1m)
     t2, _ = case(structured_tri_mesh(1001, 1001, length=2.0, height=2.0, jitter=0.2, seed=0, dtype=f64), f64, False, 1, 8)
     c, _ = case(t1m, torch.float32, False, 1, 8 | 1024)
