@@ -12,7 +12,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
-        r_adapt=False, outer=20, precond="block_jacobi", quad=False):
+        r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -30,7 +30,11 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     ``precond``: the CG preconditioner of ``solve_first`` and ``r_adapt`` (``"block_jacobi"`` or ``"amg"``).
     ``quad=True`` (with ``r_adapt``): the same plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
     (``structured_quad_mesh``: the structured mesher cuts holes into triangles only), same sides, material and traction, run
-    through ``hidenn_fem_amd.radapt.r_adapt_`` (``Quad4RAdaptiveSolver``); prints the same three kinds of line."""
+    through ``hidenn_fem_amd.radapt.r_adapt_`` (``Quad4RAdaptiveSolver``); prints the same three kinds of line.
+    ``error_estimate=True``: prints the relative ZZ error estimate eta_rel (``hidenn_fem_amd.post.StressRecovery``: recovered
+    nodal stress, energy-norm indicator) after the solve and, with ``r_adapt``, on the frozen mesh and on the r-adapted one.
+    The estimate measures the discretisation error only in the physical gradient convention, so under this switch the loss is
+    built with ``grad_convention="physical"`` (and the run says so): the energies then differ from the reference convention's."""
     import os
     import torch.distributed as dist
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -56,9 +60,12 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
         torch.manual_seed(0)                                       # every rank must draw the same initial u_free
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
-    loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype)
+    loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype,
+                           grad_convention="physical" if error_estimate else None)
+    if error_estimate and rank0:
+        print('error estimate: the loss uses grad_convention="physical" (eta estimates the discretisation error only there)')
     if r_adapt:
-        return _r_adapt(model, loss_fn, outer, precond)
+        return _r_adapt(model, loss_fn, outer, precond, error_estimate)
     if solve_first:
         import time
         from hidenn_fem_amd.solve import solve_displacement_
@@ -69,6 +76,8 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
         if rank0:
             print(f"frozen-mesh solve: {info.iterations} CG iterations, |r|/|f| = {info.residual_norm / max(info.rhs_norm, 1e-300):.2e} "
                   f"({info.reason}), {time.perf_counter() - t0:.3f} s, energy {loss_fn(model).item():.6e}")
+            if error_estimate:
+                _print_error(model, loss_fn, "after the frozen-mesh solve")
     if sharded:
         import time
         from hidenn_fem_amd.optim import ShardedLBFGS
@@ -87,6 +96,8 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
         if rank0:
             print(f"{opt.state['func_evals']} closure calls, final loss {value.item():.6e}, {time.perf_counter() - t0:.3f} s "
                   f"(ShardedLBFGS over {sh.world} rank(s), {opt._n} of {model.node_coords_free.numel() + model.u_free.numel()} parameters here)")
+            if error_estimate:
+                _print_error(model, loss_fn, "after the loop")
         return model, value.item()
     if fused_lbfgs:                      # same algorithm and defaults, device-resident (hidenn_fem_amd/optim.py)
         from hidenn_fem_amd.optim import FusedLBFGS
@@ -114,13 +125,30 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     torch.cuda.synchronize()
     print(f"{calls[0]} closure calls, final loss {value.item():.6e}, {time.perf_counter() - t0:.3f} s "
           f"({'FusedLBFGS' if fused_lbfgs else 'torch.optim.LBFGS'})")
+    if error_estimate:
+        _print_error(model, loss_fn, "after the loop")
     return model, value.item()
 
 
-def _r_adapt(model, loss_fn, outer, precond="block_jacobi"):
+def _print_error(model, loss_fn, when, recovery=None):
+    """One line with the relative ZZ error estimate; returns the ``StressRecovery`` (reusable: the connectivity never changes)."""
+    from hidenn_fem_amd.post import StressRecovery
+    recovery = recovery or StressRecovery(model, loss_fn)
+    err = recovery.error()
+    print(f"ZZ error estimate {when}: eta_rel {err.relative:.6e} (eta {err.eta:.6e}, ||u_h|| {err.energy_norm2 ** 0.5:.6e}, "
+          f"largest element share {(err.eta2.max().item() / max(err.eta ** 2, 1e-300)):.3e})")
+    return recovery
+
+
+def _r_adapt(model, loss_fn, outer, precond="block_jacobi", error_estimate=False):
     import time
     from hidenn_fem_amd.radapt import mesh_quality, quad4_mesh_quality, r_adapt_
     quality = quad4_mesh_quality if getattr(model, "nodes_per_element", 3) == 4 else mesh_quality
+    recovery = None
+    if error_estimate:                    # the frozen-mesh state r_adapt_ starts from: the same solve, made once more there
+        from hidenn_fem_amd.solve import solve_displacement_
+        solve_displacement_(model, loss_fn, rtol=1e-10, precond=precond)
+        recovery = _print_error(model, loss_fn, "on the frozen mesh")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     info = r_adapt_(model, loss_fn, max_outer=outer, cg_precond=precond)      # RAdaptiveSolver / Quad4RAdaptiveSolver
@@ -132,6 +160,8 @@ def _r_adapt(model, loss_fn, outer, precond="block_jacobi"):
     mq = quality(model)
     print(f"r-adapted energy {info.energy[-1]:.9e} after {info.iterations} outer iterations ({info.reason}), "
           f"min q {mq.min_q:.4f}, inverted elements {mq.n_inverted}, {time.perf_counter() - t0:.3f} s")
+    if error_estimate:
+        _print_error(model, loss_fn, "on the r-adapted mesh", recovery)
     return model, info.energy[-1]
 
 
@@ -150,7 +180,10 @@ if __name__ == "__main__":
     ap.add_argument("--quad", action="store_true", help="with --r-adapt: the plate as nx x ny nodes of QUAD4 cells (no holes)")
     ap.add_argument("--precond", choices=["block_jacobi", "amg"], default="block_jacobi",
                     help="CG preconditioner of --solve-first and --r-adapt")
+    ap.add_argument("--error-estimate", action="store_true",
+                    help="print the relative ZZ error estimate after the solve (with --r-adapt: before and after adaptation); "
+                         "builds the loss with grad_convention='physical'")
     a = ap.parse_args()
     run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,
-        precond=a.precond, quad=a.quad)
+        precond=a.precond, quad=a.quad, error_estimate=a.error_estimate)

@@ -84,6 +84,11 @@ PROTOTYPES = {
     "hfem_lbfgs_shard_status": (C.c_int, [_vp, _vp, _vp]),
     "hfem_tri3_von_mises": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, C.c_double, C.c_double, _vp, _vp, _vp]),
     "hfem_line2_slopes": (C.c_int, [C.c_int, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "hfem_quad4_von_mises": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "hfem_tri3_stress_recover": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "hfem_quad4_stress_recover": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "hfem_tri3_zz_error": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hfem_quad4_zz_error": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "hfem_tri3_energy_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _f64, _f64, _f64, _f64, _f64, _vp, _vp, _i32, _vp]),
     "hfem_tri3_energy_adam_step_ex": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -426,6 +426,37 @@ int hfem_tri3_von_mises(int device, const double *X, const double *U, const int3
                         double E, double nu, double *von_mises, double *grad_u, void *stream);
 int hfem_line2_slopes(int device, const double *grid, const double *u, int64_t n_nodes, int32_t dim_u,
                       double *out, void *stream);
+/* hfem_quad4_von_mises: the QUAD4 twin of hfem_tri3_von_mises -- the same chain and outputs with grad_u taken at the cell
+ * centre (xi = eta = 0), reference convention; conn[Ne][4], local nodes counter-clockwise from (-1, -1).           */
+int hfem_quad4_von_mises(int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
+                         double E, double nu, double *von_mises, double *grad_u, void *stream);
+
+/* ------------------------------------------------------------------ nodal stress recovery and ZZ error estimate
+ * No reference counterpart.  X[Nn][2], U[Nn][2] by node id, conn[Ne][3 or 4]; mat[4] = (c11, c12, c22, c33) of the
+ * plane-stress C (HOST pointer), S = C^-1; Voigt stress sigma = C (eps_xx, eps_yy, gamma_xy) of grad_u in the reference
+ * convention or, with flags = HFEM_FLAG_PHYSICAL_GRAD, the physical one.  Points: TRI3 the centroid with w = |det J| / 2,
+ * QUAD4 the 2x2 Gauss points with w_q = |det J_q| (|det|: either orientation).
+ * hfem_*_stress_recover (lumped L2 projection): nodal_stress[Nn][3] = sum_{e at n} sum_q w_q N_n(q) sigma_h(q) /
+ *   sum_{e at n} sum_q w_q N_n(q); nodal_area[Nn] (optional, NULL) = that denominator, the lumped nodal area.  adj_ptr[Nn + 1],
+ *   adj[npe Ne]: node -> (element, corner) CSR, entries e << 2 | c ascending in e at every node (hence Ne < 2^29).  One
+ *   thread per node adds in that order: no atomics, bitwise reproducible.  A node of no element gets zeros.
+ * hfem_*_zz_error: eta2[Ne] = sum_q w_q d_q.S.d_q with d_q = sum_k N_k(q) sigma*_k - sigma_h(q) (TRI3: the exact closed form
+ *   A/12 [sum_k d_k.S.d_k + (sum_k d_k).S.(sum_k d_k)]); norm2[Ne] (optional, NULL) = sum_q w_q sigma_h.S.sigma_h = twice the
+ *   element's strain energy; totals[2] = {sum eta2, sum norm2}, summed on the device in a fixed order (no atomics).
+ *   partials: caller-owned workspace of 2 * ceil(Ne / 256) doubles.
+ * All device pointers except mat; launch-only (capturable).  Ne == 0 (or Nn == 0) returns 0 without touching a device. */
+int hfem_tri3_stress_recover(int device, const double *X, const double *U, const int32_t *conn, int64_t ne, int64_t nn,
+                             const int32_t *adj_ptr, const int32_t *adj, const double *mat, int32_t flags,
+                             double *nodal_stress, double *nodal_area, void *stream);
+int hfem_quad4_stress_recover(int device, const double *X, const double *U, const int32_t *conn, int64_t ne, int64_t nn,
+                              const int32_t *adj_ptr, const int32_t *adj, const double *mat, int32_t flags,
+                              double *nodal_stress, double *nodal_area, void *stream);
+int hfem_tri3_zz_error(int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
+                       const double *nodal_stress, const double *mat, int32_t flags, double *eta2, double *norm2,
+                       double *partials, double *totals, void *stream);
+int hfem_quad4_zz_error(int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
+                        const double *nodal_stress, const double *mat, int32_t flags, double *eta2, double *norm2,
+                        double *partials, double *totals, void *stream);
 
 /* ------------------------------------------------------------------ multi-GPU interface exchange
  * Owner-sharded mode (no reference counterpart): one all_gather per step of a fixed-size

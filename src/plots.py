@@ -1,1 +1,2 @@
-from hidenn_fem_amd.post import compute_du_dx_per_element, von_mises  # noqa: F401  (compute cores of src/plots.py)
+from hidenn_fem_amd.post import (StressRecovery, ZZError, compute_du_dx_per_element, node_adjacency, recover_stress,  # noqa: F401
+                                 von_mises, zz_error)    # compute cores of src/plots.py + the stress recovery
