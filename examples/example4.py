@@ -130,6 +130,80 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     return model, value.item()
 
 
+def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3):
+    """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
+    clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
+    of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
+    ``u_free`` by ``steps`` outer ``FusedLBFGS`` steps, started from the previous state scaled to the new load (the first one:
+    from the linear frozen-mesh solve).  An increment after which an element is inverted (``loss_fn.info[1] > 0``) or the
+    energy is not finite is taken back and halved.  Prints energy, min J and the tip deflection per load step and, at the
+    smallest load, the gap to the linear solution.  Returns ``(model, energy)``."""
+    from hidenn_fem_amd.loss import NeoHookeanLoss2D
+    from hidenn_fem_amd.optim import FusedLBFGS
+    from hidenn_fem_amd.solve import solve_displacement_
+    dev = torch.device("cuda")
+    length, height = 2.0, 1.0
+    holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
+    sides = {"up": 0, "down": 0, "right": 2, "left": 1}
+    nodes, conn, geom, bc, mn, edges = generate_mesh(length, height, holes, sides, nx, ny)
+    print(f"nodes {tuple(nodes.shape)} elements {tuple(conn.shape)} dirichlet {int(bc.sum())} neumann edges {tuple(edges.shape)}")
+    model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
+                                     neumann_edges=edges).to(dev)
+    model.node_coords_free.requires_grad_(False)                   # frozen mesh: the launch skips the coordinate gradient
+    loss_fn = NeoHookeanLoss2D(E=E, nu=nu, length=length, height=height, device=dev, dtype=dtype)
+    tau = E / 500.0
+    tip = torch.nonzero(model.from_caller_order(nodes[~bc][:, 0:1].to(dev), "u")[:, 0] > length - 1e-6)[:, 0]
+
+    def traction(scale):
+        return lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -scale * tau)], dim=1)
+
+    def minimise(scale):
+        opt = FusedLBFGS([model.u_free])
+        t = traction(scale)
+
+        def closure():
+            opt.zero_grad()
+            value = loss_fn(model, None, t)
+            value.backward()
+            return value
+
+        for _ in range(steps):
+            opt.step(closure)
+        with torch.no_grad():
+            value = loss_fn(model, None, t)
+        return value.item(), float(loss_fn.info[0]), int(loss_fn.info[1]), model.u_free.grad.abs().max().item()
+
+    done, inc, first = 0.0, 1.0 / load_steps, True
+    energy = float("nan")
+    prev, prev_load = torch.zeros_like(model.u_free), 0.0          # the accepted state before the last one (secant predictor)
+    while done < 1.0 - 1e-12 and inc > 1e-4:
+        target = min(1.0, done + inc)
+        keep = model.u_free.detach().clone()
+        with torch.no_grad():
+            if first:
+                lin = EnergyLoss2D(E=E, nu=nu, length=length, height=height, device=dev, dtype=dtype, grad_convention="physical")
+                solve_displacement_(model, lin, t_force=traction(target), rtol=1e-10)
+                u_lin = model.u_free.detach().clone()
+            else:                                                  # along the secant through the last two accepted states
+                model.u_free.add_((keep - prev) * ((target - done) / (done - prev_load)))
+        value, min_j, inverted, ginf = minimise(target)
+        if inverted > 0 or value != value or value in (float("inf"), float("-inf")):
+            with torch.no_grad():
+                model.u_free.copy_(keep)
+            inc *= 0.5
+            print(f"load {target:.4f}: {inverted} inverted element(s), energy {value:.6e} -- increment halved to {inc:.4f}")
+            continue
+        prev, prev_load = keep if not first else torch.zeros_like(keep), done
+        energy, done = value, target
+        defl = model.u_free.detach()[tip, 1].mean().item()
+        print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|inf {ginf:.3e}")
+        if first:
+            gap = (model.u_free.detach() - u_lin).abs().max().item() / u_lin.abs().max().item()
+            print(f"load {target:.4f}: gap to the linear frozen-mesh solution max|u - u_lin| / max|u_lin| = {gap:.3e}")
+            first = False
+    return model, energy
+
+
 def _print_error(model, loss_fn, when, recovery=None):
     """One line with the relative ZZ error estimate; returns the ``StressRecovery`` (reusable: the connectivity never changes)."""
     from hidenn_fem_amd.post import StressRecovery
@@ -169,7 +243,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=200)
     ap.add_argument("--ny", type=int, default=100)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="outer L-BFGS steps (default 30; per load increment of --neo-hookean: 100)")
     ap.add_argument("--fp64", action="store_true")
     ap.add_argument("--fused-lbfgs", action="store_true")
     ap.add_argument("--sharded", action="store_true", help="owner-sharded energy + node-sharded L-BFGS (one process per GPU)")
@@ -183,7 +257,13 @@ if __name__ == "__main__":
     ap.add_argument("--error-estimate", action="store_true",
                     help="print the relative ZZ error estimate after the solve (with --r-adapt: before and after adaptation); "
                          "builds the loss with grad_convention='physical'")
+    ap.add_argument("--neo-hookean", action="store_true",
+                    help="the plate at finite strain: Neo-Hookean material, load ramped in steps, FusedLBFGS on u_free (fp64)")
+    ap.add_argument("--load-steps", type=int, default=8, help="load increments of --neo-hookean")
     a = ap.parse_args()
-    run(a.nx, a.ny, a.steps, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
+    if a.neo_hookean:
+        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps)
+        raise SystemExit(0)
+    run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,
         precond=a.precond, quad=a.quad, error_estimate=a.error_estimate)

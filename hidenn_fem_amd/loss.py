@@ -256,6 +256,121 @@ class EnergyLoss2D:
         return self._fused(model, b_force, T_edge, Tconst, 0)
 
 
+class NeoHookeanLoss2D(EnergyLoss2D):
+    """Compressible Neo-Hookean total potential of a TRI3 model -- finite-strain elasticity with ``EnergyLoss2D``'s call
+    contract: ``loss = loss_fn(model, b_force=None, t_force=None)``, differentiable in ``node_coords_free`` and ``u_free``,
+    plus ``value_and_grad_``.  One launch of ``csrc/tri3_hyper.hip`` (+ a one-block reduction).
+
+    Per element ``H = G Jg^-1`` is the true displacement gradient (``grad_convention`` is always ``"physical"``: the
+    reference convention's ``G Jg^-T`` is no deformation gradient), ``F = I + H``, ``J = det F`` and
+    ``psi = mu/2 (tr F^T F - 2) - mu ln J + lambda/2 ln^2 J``, evaluated in a cancellation-free form.  Body
+    forces and tractions are dead loads on the reference configuration, tabulated exactly as ``EnergyLoss2D`` does.
+
+    Material from ``(E, nu)``: ``mu = E / (2 (1 + nu))``; ``plane="stress"`` (default) ``lambda = E nu / (1 - nu^2)``,
+    ``plane="strain"`` ``lambda = E nu / ((1 + nu)(1 - 2 nu))``; ``loss_fn.lame = (lambda, mu)``.  ``plane="stress"`` is the
+    usual 2D effective-lambda model -- its linearisation is ``EnergyLoss2D``'s ``C`` entry for entry, so the two losses agree
+    in the small-strain limit --, NOT a solved-for out-of-plane stretch.
+
+    An element with ``J <= 0`` contributes ``+inf`` to the loss (a backtracking caller comparing losses does the right thing)
+    and zero to both gradients (no NaN reaches an optimiser's moments).  ``loss_fn.info`` is the fp64 device tensor ``[2]``
+    the last launch wrote, ``{min J, number of elements with J <= 0}``: the same tensor on every call, no host sync.
+
+    fp32 models: float rows widened on load, fp64 arithmetic, one rounding on store.  Not available: ``deterministic=True``,
+    ``arithmetic="fp32"``, QUAD4 models, ``FrozenMeshSolver`` / ``StressRecovery`` (they are linear)."""
+
+    def __init__(self, E: float = 10e9, nu: float = 0.3, length: float = 1.0, height: float = 1.0,
+                 gauss_order: int = 4, gauss_order_1d: int = 2, device: Optional[torch.device] = None,
+                 dtype: torch.dtype = torch.float32, tile_elems: int = 0, plane: str = "stress",
+                 deterministic: bool = False, arithmetic: str = "auto"):
+        if plane not in ("stress", "strain"):
+            raise ValueError("plane must be 'stress' or 'strain'")
+        if deterministic:
+            raise NotImplementedError("NeoHookeanLoss2D: no fixed-order kernel (deterministic=True) for this energy")
+        if arithmetic == "fp32":
+            raise NotImplementedError("NeoHookeanLoss2D: fp64 arithmetic only (fp32 models: float rows, fp64 arithmetic)")
+        super().__init__(E, nu, length, height, gauss_order, gauss_order_1d, device, dtype, tile_elems,
+                         grad_convention="physical", deterministic=False, arithmetic=arithmetic)
+        self.plane = plane
+        mu = E / (2.0 * (1.0 + nu))
+        lam = E * nu / (1.0 - nu ** 2) if plane == "stress" else E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+        self.lame = (lam, mu)
+        self._info = None
+        self._work = {}
+
+    @property
+    def info(self) -> torch.Tensor:
+        if self._info is None:
+            self._info = torch.zeros(2, dtype=torch.float64, device=self.device)
+        return self._info
+
+    def _launch_state(self, model):
+        """(one-element-per-slot plan, info, workspace) for a launch on the model's device."""
+        if getattr(model, "nodes_per_element", 3) != 3:
+            raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only")
+        from .plan import model_plan
+        plan = model_plan(model, self.tile_elems, paired=False)
+        dev = model.node_coords_free.device
+        if self._info is None or self._info.device != dev:
+            self._info = torch.zeros(2, dtype=torch.float64, device=dev)
+        hit = self._work.get(id(plan))
+        if hit is None or hit[0] is not plan or hit[1].device != dev:
+            hit = self._work[id(plan)] = (plan, torch.empty(3 * max(plan.n_tiles, 1), dtype=torch.float64, device=dev))
+        return plan, self._info, hit[1]
+
+    def _fused(self, model, b_force, T_edge, Tconst, flags, tile_range=(0, -1)):
+        plan, info, work = self._launch_state(model)
+        return ops.Tri3HyperEnergyFn.apply(model.node_coords_free, model.u_free, model.node_coords_fixed.to(model.dtype),
+                                           model.u_fixed_rows(), plan, self.lame, self._W, self._body_table(b_force), T_edge,
+                                           Tconst, flags, info, work)
+
+    def _quad4(self, model, b_force, t_force):
+        raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only")
+
+    def domain_energy(self, model, b_force: Optional[Callable] = None) -> torch.Tensor:
+        """Strain energy minus body work (the edges off), fused."""
+        return self._fused(model, b_force, None, [0.0] * 4, HFEM_FLAG_NO_EDGES)
+
+    def value_and_grad_(self, model) -> torch.Tensor:
+        """As ``EnergyLoss2D.value_and_grad_``: ONE launch writes both gradients straight into ``.grad`` (overwritten) and
+        returns the loss (0-d, fp64; the same tensor every call).  Default forces; fp64 or fp32 rows.  Only launches:
+        capturable into a graph."""
+        import ctypes as C
+        import weakref
+        from . import _lib
+        plan, info, work = self._launch_state(model)
+        xf, uf = model.node_coords_free, model.u_free
+        if xf.dtype != uf.dtype or xf.dtype not in (torch.float64, torch.float32):
+            raise RuntimeError("value_and_grad_: parameters must both be fp64 or both fp32")
+        for p in (xf, uf):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        cache = getattr(self, "_direct_cache", None)
+        key = (xf.dtype, xf.device)
+        if cache is None or cache[0][0]() is not model or cache[0][1:] != key:
+            _, Tconst = self._traction(model, None)
+            dv = lambda v: (C.c_double * len(v))(*v)
+            cache = self._direct_cache = ((weakref.ref(model),) + key, dv(self.lame), dv([0.0] * 6), dv(Tconst),
+                                          torch.zeros((), dtype=torch.float64, device=xf.device))
+        _, lame, Bk, Tc, loss = cache
+        xfix = model.node_coords_fixed.to(device=xf.device, dtype=xf.dtype).contiguous()
+        ufix = model.u_fixed_rows().to(device=xf.device, dtype=xf.dtype).contiguous()
+        _lib.check(_lib.lib().hfem_tri3_hyper_energy_plan(
+            plan.handle, 1 if xf.dtype == torch.float32 else 0, xf.data_ptr(), xfix.data_ptr() if xfix.numel() else None,
+            uf.data_ptr(), ufix.data_ptr() if ufix.numel() else None, lame, self._W, Bk, None, Tc, loss.data_ptr(),
+            info.data_ptr(), work.data_ptr(), xf.grad.data_ptr(), uf.grad.data_ptr(), 0 if model.N_edges else HFEM_FLAG_NO_EDGES,
+            _lib.stream_ptr(xf.device)), "hfem_tri3_hyper_energy_plan")
+        return loss
+
+
+def require_linear(loss_fn, who: str):
+    """The linear tools (frozen-mesh solve, stiffness assembly, stress recovery) refuse a finite-strain loss: they would
+    silently work on its linearisation."""
+    if isinstance(loss_fn, NeoHookeanLoss2D):
+        raise NotImplementedError(f"{who}: small-strain linear elasticity only; a NeoHookeanLoss2D would be linearised "
+                                  "silently (a Newton-Krylov solve on its tangent does not exist yet) -- minimise it with "
+                                  "FusedLBFGS / FusedAdam, or pass an EnergyLoss2D")
+
+
 # ---------------------------------------------------------------- inline losses of examples 1-3
 def l2_projection_loss(model, x_eval, target):
     """``((model(x) - target)**2).mean()`` of examples/example1.py:38 as one fused launch

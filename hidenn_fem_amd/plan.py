@@ -45,6 +45,23 @@ def row_maps(free_mask: np.ndarray):
     return src
 
 
+def model_plan(model, tile_elems, paired: bool):
+    """The TRI3 model's own tile plan when its slot layout is the wanted one -- ``paired`` slots (plan_elem_order 5) or one
+    element per slot (order 3) --, else a plan of the same mesh and row maps in that layout, cached on the model beside its
+    own plans.  The planner's auto policy pairs where enough fan-adjacent partners exist (structured splits) and gives
+    zigzag and Delaunay meshes one element per slot; the CG kernels exist for paired plans only, the Neo-Hookean kernel for
+    unpaired ones."""
+    plan = model.tile_plan(tile_elems)
+    if bool(plan.stats["paired"]) == bool(paired):
+        return plan
+    key = (str(model.device), int(tile_elems), "paired" if paired else "single")
+    if key not in model._plans:
+        model._plans[key] = TilePlan(model.connectivity, model.Nnodes, coords_hint=model.initial_node_coords,
+                                     x_src=model._x_src, u_src=model._u_src, edges=model.neumann_edges, tile_elems=tile_elems,
+                                     device=model.device, elem_order=5 if paired else 3, nodes_per_elem=3)
+    return model._plans[key]
+
+
 class TilePlan:
     """Owner-computes tiling of a TRI3 mesh.  ``device=None`` -> host-only plan
     (no HIP call; what the CPU tests inspect)."""

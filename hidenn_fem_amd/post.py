@@ -127,6 +127,8 @@ class StressRecovery:
     results back."""
 
     def __init__(self, model, loss_fn):
+        from .loss import require_linear
+        require_linear(loss_fn, "StressRecovery")
         npe = getattr(model, "nodes_per_element", 3)
         if npe not in (3, 4) or not hasattr(model, "_conn32"):
             raise NotImplementedError("StressRecovery: TRI3 and QUAD4 mesh models")

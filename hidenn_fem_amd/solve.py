@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .loss import require_linear
 
 F64 = torch.float64
 HFEM_FLAG_NO_GX = 1
@@ -243,6 +244,7 @@ class FrozenMeshSolver(_FrozenSolverBase):
 
     @staticmethod
     def _check_model(model, loss_fn):
+        require_linear(loss_fn, "FrozenMeshSolver")
         if getattr(model, "nodes_per_element", 3) != 3:
             raise NotImplementedError("FrozenMeshSolver: TRI3 models only (QUAD4 models: Quad4FrozenMeshSolver, or "
                                       "solve_displacement_, which takes either)")
@@ -280,6 +282,7 @@ class Quad4FrozenMeshSolver(_FrozenSolverBase):
 
     @staticmethod
     def _check_model(model, loss_fn):
+        require_linear(loss_fn, "Quad4FrozenMeshSolver")
         if getattr(model, "nodes_per_element", 3) != 4:
             raise NotImplementedError("Quad4FrozenMeshSolver: QUAD4 models only (TRI3 models: FrozenMeshSolver)")
         if getattr(loss_fn, "deterministic", False):
@@ -405,6 +408,7 @@ def assemble_stiffness(model, loss_fn) -> torch.Tensor:
     """K_ff of the model at its current coordinates: fp64 ``torch.sparse_bsr_tensor`` with 2x2 blocks over the free u rows in
     storage order (Dirichlet columns dropped), from the AMG assembly kernel (one thread per row, deterministic).  The gradient
     convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 and QUAD4 models."""
+    require_linear(loss_fn, "assemble_stiffness")
     _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
     dev = model.u_free.device
     phys = bool(loss_fn._mode_flags(model) & HFEM_FLAG_PHYSICAL_GRAD)
@@ -426,16 +430,8 @@ def _paired_plan(model, tile_elems):
     beside its own plans).  The planner's auto policy gives meshes with few fan-adjacent partners -- zigzag splits such as
     example 4's plate, Delaunay meshes -- the one-element-per-slot order; the CG kernels exist for paired plans only, where an
     element without a partner is simply a slot with one element."""
-    from .plan import TilePlan
-    plan = model.tile_plan(tile_elems)
-    if plan.stats["paired"]:
-        return plan
-    key = (str(model.device), int(tile_elems), "paired")
-    if key not in model._plans:
-        model._plans[key] = TilePlan(model.connectivity, model.Nnodes, coords_hint=model.initial_node_coords,
-                                     x_src=model._x_src, u_src=model._u_src, edges=model.neumann_edges, tile_elems=tile_elems,
-                                     device=model.device, elem_order=5, nodes_per_elem=3)
-    return model._plans[key]
+    from .plan import model_plan
+    return model_plan(model, tile_elems, paired=True)
 
 
 class _Frozen:

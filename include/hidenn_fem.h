@@ -458,6 +458,24 @@ int hfem_quad4_zz_error(int device, const double *X, const double *U, const int3
                         const double *nodal_stress, const double *mat, int32_t flags, double *eta2, double *norm2,
                         double *partials, double *totals, void *stream);
 
+/* ------------------------------------------------------------------ compressible Neo-Hookean energy (TRI3)
+ * No reference counterpart.  Total potential of a TRI3 model at finite strain on a ONE-ELEMENT-PER-SLOT tile plan
+ * (plan_elem_order 3), with its gradients w.r.t. the free coordinate and displacement rows.  Per element, with
+ * Jg = [X0 - X2, X1 - X2], G = [U0 - U2, U1 - U2]:  H = G Jg^-1 (the true displacement gradient, always), j = tr H + det H
+ * (= J - 1), L = log1p(j), psi = mu (tr H + H:H / 2 - L) + lambda L^2 / 2, e = |det Jg| (W psi - sum_k U_k . B_k); Neumann
+ * edges are dead loads on the reference configuration (T_edge / Tconst as hfem_tri3_energy_plan).  lame[2] = (lambda, mu),
+ * Bk[6] (may be NULL = 0) and Tconst[4] are HOST pointers.  dtype: 0 = every row array double, 1 = float (widened on load,
+ * fp64 arithmetic, gradient rows rounded once on store).  An element with J <= 0 contributes +inf to the loss and ZERO to
+ * both gradients.  loss_out[1] and info_out[2] (may be NULL) = {min J over the elements, number of elements with J <= 0}
+ * are device doubles; work = caller-owned device workspace of 3 * n_tiles doubles (the plan's own partials banks are not
+ * used, so a lagged loss sum in flight on the plan is undisturbed).  gx_free / gu_free may be NULL only with the matching
+ * flag.  flags: HFEM_FLAG_NO_GX, HFEM_FLAG_NO_GU, HFEM_FLAG_NO_EDGES; any other flag, a QUAD4, paired or host-only plan or a
+ * missing pointer is an argument error.  Launch-only (capturable).                                                      */
+int hfem_tri3_hyper_energy_plan(hfem_plan *plan, int32_t dtype, const void *x_free, const void *x_fixed,
+                                const void *u_free, const void *u_fixed, const double lame[2], double W,
+                                const double Bk[6], const double *T_edge, const double Tconst[4], double *loss_out,
+                                double *info_out, double *work, void *gx_free, void *gu_free, int32_t flags, void *stream);
+
 /* ------------------------------------------------------------------ multi-GPU interface exchange
  * Owner-sharded mode (no reference counterpart): one all_gather per step of a fixed-size
  * payload per rank, in double2 units:  [x rows | u rows | padding][loss partial, 0].
