@@ -130,14 +130,19 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     return model, value.item()
 
 
-def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3):
+def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3, newton=False,
+                    precond="block_jacobi"):
     """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
     clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
     of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
     ``u_free`` by ``steps`` outer ``FusedLBFGS`` steps, started from the previous state scaled to the new load (the first one:
     from the linear frozen-mesh solve).  An increment after which an element is inverted (``loss_fn.info[1] > 0``) or the
     energy is not finite is taken back and halved.  Prints energy, min J and the tip deflection per load step and, at the
-    smallest load, the gap to the linear solution.  Returns ``(model, energy)``."""
+    smallest load, the gap to the linear solution.  Returns ``(model, energy)``.
+    ``newton=True`` (``--newton``): the same ramp, predictor and halving rule, each increment solved to equilibrium by
+    ``hidenn_fem_amd.newton.NewtonKrylovSolver`` (inexact Newton, truncated PCG on the tangent, preconditioner ``precond``)
+    instead of ``FusedLBFGS``; the line then also shows the Newton and CG iterations.  An increment whose Newton solve does
+    not converge is taken back and halved like an inverted one."""
     from hidenn_fem_amd.loss import NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
     from hidenn_fem_amd.solve import solve_displacement_
@@ -173,6 +178,12 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
             value = loss_fn(model, None, t)
         return value.item(), float(loss_fn.info[0]), int(loss_fn.info[1]), model.u_free.grad.abs().max().item()
 
+    def equilibrium(scale):
+        from hidenn_fem_amd.newton import NewtonKrylovSolver
+        info = NewtonKrylovSolver(model, loss_fn, t_force=traction(scale), precond=precond).solve()
+        ginf = float("inf") if not info.converged else info.grad_norm       # an unconverged increment is taken back
+        return info.energy, info.min_J, 0 if info.converged else 1, ginf, info
+
     done, inc, first = 0.0, 1.0 / load_steps, True
     energy = float("nan")
     prev, prev_load = torch.zeros_like(model.u_free), 0.0          # the accepted state before the last one (secant predictor)
@@ -186,17 +197,25 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
                 u_lin = model.u_free.detach().clone()
             else:                                                  # along the secant through the last two accepted states
                 model.u_free.add_((keep - prev) * ((target - done) / (done - prev_load)))
-        value, min_j, inverted, ginf = minimise(target)
+        if newton:
+            value, min_j, inverted, ginf, ninfo = equilibrium(target)
+        else:
+            value, min_j, inverted, ginf = minimise(target)
         if inverted > 0 or value != value or value in (float("inf"), float("-inf")):
             with torch.no_grad():
                 model.u_free.copy_(keep)
             inc *= 0.5
-            print(f"load {target:.4f}: {inverted} inverted element(s), energy {value:.6e} -- increment halved to {inc:.4f}")
+            what = f"Newton stopped with {ninfo.reason!r}" if newton else f"{inverted} inverted element(s)"
+            print(f"load {target:.4f}: {what}, energy {value:.6e} -- increment halved to {inc:.4f}")
             continue
         prev, prev_load = keep if not first else torch.zeros_like(keep), done
         energy, done = value, target
         defl = model.u_free.detach()[tip, 1].mean().item()
-        print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|inf {ginf:.3e}")
+        if newton:
+            print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|2 {ginf:.3e} "
+                  f"Newton {ninfo.newton_iterations} CG {ninfo.cg_iterations}")
+        else:
+            print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|inf {ginf:.3e}")
         if first:
             gap = (model.u_free.detach() - u_lin).abs().max().item() / u_lin.abs().max().item()
             print(f"load {target:.4f}: gap to the linear frozen-mesh solution max|u - u_lin| / max|u_lin| = {gap:.3e}")
@@ -260,9 +279,11 @@ if __name__ == "__main__":
     ap.add_argument("--neo-hookean", action="store_true",
                     help="the plate at finite strain: Neo-Hookean material, load ramped in steps, FusedLBFGS on u_free (fp64)")
     ap.add_argument("--load-steps", type=int, default=8, help="load increments of --neo-hookean")
+    ap.add_argument("--newton", action="store_true",
+                    help="with --neo-hookean: solve every load increment with NewtonKrylovSolver instead of FusedLBFGS")
     a = ap.parse_args()
     if a.neo_hookean:
-        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps)
+        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,

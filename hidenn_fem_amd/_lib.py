@@ -154,6 +154,8 @@ PROTOTYPES = {
     "hfem_cg_iterate": (C.c_int, [_vp, _vp, _i32, _vp]),
     "hfem_cg_status": (C.c_int, [_vp, _vp, _vp]),
     "hfem_cg_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "hfem_cg_create_hyper": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
+    "hfem_cg_setup_hyper": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp]),
     "hfem_tri3_mesh_measure": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_tri3_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_tri3_quality_barrier": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp]),

@@ -1,8 +1,9 @@
 // PCG driver of the frozen-mesh displacement solve, gfx950 (MI355X) (hidenn_fem_amd/solve.py): everything above the element
 // level -- the vector kernels, the status record, the halt logic and the hfem_cg_* entry points.  Nothing here knows the
-// element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan) or quad4_cg.hip
-// (the model's own QUAD4 plan), chosen in cg_apply and cg_diag; the residual r = -dE/du comes from the graded energy kernel,
-// called by the host once per solve.
+// element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
+// (the model's own QUAD4 plan) or tri3_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point, one-element-per-slot
+// TRI3 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in cg_apply and cg_diag; the residual r = -dE/du comes from
+// the graded energy kernel, called by the host once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
 //                   order, forms beta, and applies the stopping test (START: r = -g0, z = D^-1 r, |f|).
 //   cg_rz_kernel    rho = r^T z in block order, then beta (precond = AMG only).
@@ -161,17 +162,22 @@ struct hfem_cg {
     int64_t n_u = 0;
     int n_tiles = 0, block = 256, vec_blocks = 1;
     bool phys = false, quad = false;   // quad: a QUAD4 plan (one element per slot; kernels of quad4_cg.hip)
+    bool hyper = false;                // the Neo-Hookean tangent (unpaired TRI3 plan; kernels of tri3_hyper_cg.hip)
     size_t lds_apply = 0, lds_diag = 0;
     // device memory, one allocation: p[2], r, z, q (double2 rows), dinv (3 doubles per row), tile partials, vector partials,
     // status record, tickets
     char *mem = nullptr;
     double2 *p[2] = {nullptr, nullptr}, *r = nullptr, *z = nullptr, *q = nullptr;
     double *dinv = nullptr, *tile_part = nullptr, *vec_part = nullptr, *st = nullptr;
+    double *work = nullptr;            // hyper: the diag launch's tile partials [3][n_tiles]
     unsigned *tickets = nullptr;       // [0] apply, [1] vector kernels, [2] standalone apply
     double *host = nullptr;            // pinned mirror of the status record
     // bound by hfem_cg_setup
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     hfem::Tri3Consts k{};
+    // bound by hfem_cg_setup_hyper
+    const double2 *u_lin = nullptr, *u_fixed = nullptr;
+    hfem::HyperConsts hk{};
     bool ready = false;
 };
 
@@ -180,6 +186,7 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     hfem::CgElemArgs A;
     A.plan = c->plan; A.n_tiles = c->n_tiles; A.block = c->block; A.phys = c->phys; A.x_free = c->x_free; A.x_fixed = c->x_fixed;
     A.k = c->k; A.lds = lds; A.s = s;
+    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk;
     return A;
 }
 
@@ -187,13 +194,15 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
 void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, double *st, double *host, double *pq_out,
               hipStream_t s) {
     const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
-    if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
 
-void cg_diag(const hfem_cg *c, double *diag, int precond, hipStream_t s) {
+void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStream_t s) {
     const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
-    if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
+    if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }
 
@@ -246,6 +255,15 @@ int check_amg(const hfem_cg *c, const hfem_amg *a) {
 }
 }  // namespace
 
+static int cg_alloc(std::unique_ptr<hfem_cg> &c, hfem_cg **out);
+
+// free u rows the plan's row maps address
+static int64_t plan_u_rows(const hfem::HostPlan &h) {
+    int64_t rows = 0;
+    for (size_t i = 1; i < h.node_src.size(); i += 2) rows = std::max<int64_t>(rows, (int64_t)h.node_src[i] + 1);
+    return rows;
+}
+
 extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_cg **out) {
     HFEM_ARG_CHECK(plan && out, "null pointer");
     *out = nullptr;
@@ -262,9 +280,7 @@ extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_
                           : (h.max_nodes <= 4 * 256 && h.max_rows <= 6),
                    "tile shape outside the CG kernels' instances");
     HFEM_ARG_CHECK(!quad || h.max_owned <= h.max_nodes, "QUAD4 plan owns more rows than a tile holds");
-    int64_t rows = 0;                                        // free u rows the plan's row maps address
-    for (size_t i = 1; i < h.node_src.size(); i += 2) rows = std::max<int64_t>(rows, (int64_t)h.node_src[i] + 1);
-    HFEM_ARG_CHECK(n_u >= rows, "n_u is smaller than the plan's free u rows");
+    HFEM_ARG_CHECK(n_u >= plan_u_rows(h), "n_u is smaller than the plan's free u rows");
     HFEM_ARG_CHECK(n_u < ((int64_t)1 << 31), "n_u too large");
     std::unique_ptr<hfem_cg> c(new hfem_cg);
     c->plan = plan; c->device = plan->device; c->n_u = n_u; c->phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0;
@@ -273,11 +289,17 @@ extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_
     c->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(hfem::kVecMaxBlocks, (n_u + hfem::kVecBlock - 1) / hfem::kVecBlock));
     c->lds_apply = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 16 + (c->block / 64 + 2) * 8;
     c->lds_diag = (size_t)h.max_nodes * 16 + (size_t)h.max_owned * 24;
+    return cg_alloc(c, out);
+}
+
+// The solver's device memory and its pinned status mirror; hands the solver over on success.
+static int cg_alloc(std::unique_ptr<hfem_cg> &c, hfem_cg **out) {
+    const int64_t n_u = c->n_u;
     if (int rc = hfem::use_device(c->device)) return rc;
     const size_t rows16 = (size_t)std::max<int64_t>(n_u, 1) * 16;
     const size_t off_r = 2 * rows16, off_z = 3 * rows16, off_q = 4 * rows16, off_d = 5 * rows16;
     const size_t off_tp = off_d + (size_t)std::max<int64_t>(n_u, 1) * 24;
-    const size_t off_vp = off_tp + (size_t)std::max(c->n_tiles, 1) * 8;
+    const size_t off_vp = off_tp + 4 * (size_t)std::max(c->n_tiles, 1) * 8;   // tile partials, then hyper's [3][n_tiles]
     const size_t off_st = off_vp + 3 * (size_t)hfem::kVecMaxBlocks * 8;
     const size_t off_tk = off_st + hfem::kStatusN * 8;
     const size_t bytes = off_tk + 64;
@@ -292,6 +314,7 @@ extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_
     c->r = (double2 *)(c->mem + off_r); c->z = (double2 *)(c->mem + off_z); c->q = (double2 *)(c->mem + off_q);
     c->dinv = (double *)(c->mem + off_d); c->tile_part = (double *)(c->mem + off_tp); c->vec_part = (double *)(c->mem + off_vp);
     c->st = (double *)(c->mem + off_st); c->tickets = (unsigned *)(c->mem + off_tk);
+    c->work = c->tile_part + std::max(c->n_tiles, 1);
     const hipError_t e = hipMemset(c->mem, 0, bytes);                 // tickets zero, p buffers zero (0 * p_old is 0)
     if (e != hipSuccess) {
         (void)hipFree(c->mem); (void)hipHostFree(c->host);
@@ -300,6 +323,28 @@ extern "C" int hfem_cg_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_
     }
     *out = c.release();
     return 0;
+}
+
+// The Neo-Hookean tangent: the plan hfem_tri3_hyper_energy_plan takes (TRI3, one element per slot), tri3_hyper_cg.hip's LDS
+extern "C" int hfem_cg_create_hyper(hfem_plan *plan, int64_t n_u, hfem_cg **out) {
+    HFEM_ARG_CHECK(plan && out, "null pointer");
+    *out = nullptr;
+    HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
+    const hfem::HostPlan &h = plan->host;
+    HFEM_ARG_CHECK(h.npe == 3, "this plan was built for QUAD4: the Neo-Hookean tangent exists for TRI3 only");
+    HFEM_ARG_CHECK(!h.paired, "paired plan: the Neo-Hookean tangent kernels read one element per slot (plan_elem_order 3)");
+    HFEM_ARG_CHECK(h.max_nodes <= hfem::kMaxLocal && h.max_owned <= h.max_nodes, "tile shape outside the tangent kernels' instance");
+    const size_t lds_apply = (size_t)h.max_nodes * 48 + (size_t)h.max_owned * 16 + (512 / 64 + 2) * 8;
+    const size_t lds_diag = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 24 + 2 * (512 / 64) * 8;
+    HFEM_ARG_CHECK(lds_apply <= 64 * 1024 && lds_diag <= 64 * 1024, "tile needs more than 64 KiB of LDS");
+    HFEM_ARG_CHECK(n_u >= plan_u_rows(h), "n_u is smaller than the plan's free u rows");
+    HFEM_ARG_CHECK(n_u < ((int64_t)1 << 31), "n_u too large");
+    std::unique_ptr<hfem_cg> c(new hfem_cg);
+    c->plan = plan; c->device = plan->device; c->n_u = n_u; c->phys = true; c->hyper = true;
+    c->n_tiles = (int)h.tiles.size(); c->block = 512;
+    c->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(hfem::kVecMaxBlocks, (n_u + hfem::kVecBlock - 1) / hfem::kVecBlock));
+    c->lds_apply = lds_apply; c->lds_diag = lds_diag;
+    return cg_alloc(c, out);
 }
 
 extern "C" int hfem_cg_destroy(hfem_cg *c) {
@@ -315,6 +360,7 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
                              int32_t precond, double *diag_out, void *stream) {
     HFEM_ARG_CHECK(c && x_free && mat, "null pointer");
     HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+    HFEM_ARG_CHECK(!c->hyper, "this solver was created by hfem_cg_create_hyper: hfem_cg_setup_hyper binds it");
     bool fixed_rows = false;
     const hfem::HostPlan &h = c->plan->host;
     for (size_t i = 0; i < h.node_src.size(); i += 2) fixed_rows = fixed_rows || h.node_src[i] < 0;
@@ -323,8 +369,35 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
     hipStream_t s = (hipStream_t)stream;
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);   // QUAD4: the 2x2 rule's weights are 1 (hfem_quad4_energy_plan_ex)
-    cg_diag(c, diag_out, precond, s);
+    cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup")) return rc;
+    c->ready = true;
+    return 0;
+}
+
+extern "C" int hfem_cg_setup_hyper(hfem_cg *c, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                                   const double *u_fixed, const double lame[2], double W, int32_t precond, double *diag_out,
+                                   double *info_out, void *stream) {
+    HFEM_ARG_CHECK(c && x_free && lame && (u_lin_free || c->n_u == 0), "null pointer");
+    HFEM_ARG_CHECK(c->hyper, "this solver was created by hfem_cg_create: hfem_cg_setup binds it");
+    HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+    bool fixed_x = false, fixed_u = false;
+    const hfem::HostPlan &h = c->plan->host;
+    for (size_t i = 0; i + 1 < h.node_src.size(); i += 2) {
+        fixed_x = fixed_x || h.node_src[i] < 0;
+        fixed_u = fixed_u || h.node_src[i + 1] < 0;
+    }
+    HFEM_ARG_CHECK(x_fixed || !fixed_x, "the plan reads fixed coordinate rows: x_fixed must be given");
+    HFEM_ARG_CHECK(u_fixed || !fixed_u, "the plan reads Dirichlet rows: u_fixed must be given");
+    HFEM_ARG_CHECK(u_lin_free || !h.tiles.size(), "u_lin_free must be given");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
+    c->u_lin = (const double2 *)u_lin_free; c->u_fixed = (const double2 *)u_fixed;
+    c->hk = hfem::HyperConsts{};
+    c->hk.lambda = lame[0]; c->hk.mu = lame[1]; c->hk.W = W;
+    cg_diag(c, diag_out, precond, info_out, s);
+    if (int rc = hfem::launch_status("hfem_cg_setup_hyper")) return rc;
     c->ready = true;
     return 0;
 }

@@ -1,7 +1,7 @@
 // Device-side pieces the frozen-mesh solve's kernels share.  For every kernel with a last workgroup (cg.hip, tri3_cg.hip,
-// quad4_cg.hip): the status publication, the hand-off and the fixed-order partial sum.  For the four element kernels
-// (apply and block diagonal of tri3_cg.hip and quad4_cg.hip) the phases that do not depend on the element: the iteration
-// state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
+// quad4_cg.hip, tri3_hyper_cg.hip): the status publication, the hand-off and the fixed-order partial sum.  For the element
+// kernels (apply and block diagonal of tri3_cg.hip, quad4_cg.hip and tri3_hyper_cg.hip) the phases that do not depend on
+// the element: the iteration state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
 // block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
 // element, 3 or 4 corners, and the x row code.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
 // calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the index loads, the
@@ -11,6 +11,7 @@
 
 #include "hfem_amg.h"
 #include "hfem_device.h"
+#include "hfem_hyper_dev.h"
 #include "hfem_plan_dev.h"
 #include "hfem_quad4_dev.h"
 
@@ -147,7 +148,7 @@ __device__ __forceinline__ void store_jacobi_block(double *__restrict__ diag, do
     const size_t r = (size_t)row * 3;
     if (diag) { diag[r] = a; diag[r + 1] = b; diag[r + 2] = c; }
     const double det = a * c - b * b;
-    if (precond && det > 0.0 && isfinite(det)) {
+    if (precond && a > 0.0 && det > 0.0 && isfinite(det)) {
         const double inv = 1.0 / det;
         dinv[r] = c * inv; dinv[r + 1] = -b * inv; dinv[r + 2] = a * inv;
     } else {
@@ -189,6 +190,9 @@ struct CgElemArgs {
     Tri3Consts k{};
     size_t lds = 0;
     hipStream_t s = nullptr;
+    // the Neo-Hookean tangent (tri3_hyper_cg.hip): the linearisation point's rows and the material
+    const double2 *u_lin_free = nullptr, *u_fixed = nullptr;
+    HyperConsts hk{};
 };
 // q = K p (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
@@ -198,5 +202,10 @@ void launch_quad4_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0
 // 2x2 diagonal blocks of K and their inverses (store_jacobi_block)
 void launch_tri3_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
+// The Neo-Hookean tangent at A.u_lin_free (tri3_hyper_cg.hip, one-element-per-slot TRI3 plan): q = K_T p, and the blocks with
+// info[2] = {min J, inverted count} of the linearisation point (work: 3 * n_tiles doubles; info may be NULL)
+void launch_tri3_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                                double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_tri3_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
 
 }  // namespace hfem

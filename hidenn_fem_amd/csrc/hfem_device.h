@@ -50,6 +50,13 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// 64-lane wavefront minimum.  Result valid in lane 0.
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
+    return v;
+}
+
 // DPP control of v_mov_b32_dpp: row_shl:N -- within a row of 16 lanes, lane i reads lane i + N (lanes past the row read 0).
 constexpr int kDppRowShl = 0x100;
 template <int N> __device__ __forceinline__ double row_shl(double v) {

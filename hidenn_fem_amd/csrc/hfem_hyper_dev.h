@@ -1,6 +1,7 @@
-// Compressible Neo-Hookean TRI3 element and the per-thread part of its finishing reduction.  Plain C++ over
-// double2 / make_double2 and <cmath> only, so that the very same text compiles for the host (tests/host/hyper_san_main.cpp
-// runs it under the sanitizers against numbers of tests/hyper_reference.py).
+// Compressible Neo-Hookean TRI3 element, the per-thread part of its finishing reduction and its tangent
+// (DESIGN 18).  Plain C++ over double2 / make_double2 and <cmath> only, so that the very same text compiles for the host
+// (tests/host/hyper_san_main.cpp and hyper_tangent_san_main.cpp run it under the sanitizers against numbers of
+// tests/hyper_reference.py and tests/newton_reference.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,6 +84,64 @@ __device__ __forceinline__ double neo_hookean_element(const double2 X0, const do
     gx[1] = make_double2(db, dd);
     gx[2] = make_double2(-(da + db), -(dc + dd));
     return ok ? e : (double)INFINITY;
+}
+
+// The tangent of one element at a linearisation point, in two pieces: the state, computed once, and its
+// application to three rows of a direction p.  With T = F^-T and dH = dG Jg^-1, dG = [p0 - p2, p1 - p2]:
+//   dP = mu dH + (mu - lambda L) T dH^T T + lambda (T : dH) T
+//   q  = A dP Jg^-T                                            (column a -> node a, minus the column sum -> node 2)
+// so that sum_k p_k . q_k = p^T K_e p.  Dead loads do not enter.  The inversion rule is neo_hookean_element's: an element
+// with j <= -1 (or NaN) is evaluated at j = 0 and its six outputs are multiplied by 0 (sA = 0); j keeps the true value.
+struct HyperTangent {
+    double ai, bi, ci, di;       // Jg^-1 = [[di, -bi], [-ci, ai]]
+    double t00, t01, t10, t11;   // T = F^-T
+    double c;                    // mu - lambda L
+    double sA;                   // A = |det Jg| W, 0 for an inverted element
+    double j;                    // J - 1
+};
+
+__device__ __forceinline__ HyperTangent hyper_tangent_state(const double2 X0, const double2 X1, const double2 X2, const double2 U0,
+                                                            const double2 U1, const double2 U2, const HyperConsts &k) {
+    HyperTangent t;
+    const double a = X0.x - X2.x, b = X1.x - X2.x, c = X0.y - X2.y, d = X1.y - X2.y;
+    const double det = a * d - b * c;
+    const double inv = hyper_rcp(det);
+    t.ai = a * inv; t.bi = b * inv; t.ci = c * inv; t.di = d * inv;
+    const double g0x = U0.x - U2.x, g0y = U0.y - U2.y, g1x = U1.x - U2.x, g1y = U1.y - U2.y;
+    const double h00 = g0x * t.di - g1x * t.ci, h01 = g1x * t.ai - g0x * t.bi;
+    const double h10 = g0y * t.di - g1y * t.ci, h11 = g1y * t.ai - g0y * t.bi;
+    const double j = (h00 + h11) + (h00 * h11 - h01 * h10);
+    t.j = j;
+    const bool ok = j > -1.0;
+    const double js = ok ? j : 0.0;
+    const double r = hyper_rcp(1.0 + js);
+    t.t00 = (1.0 + h11) * r; t.t01 = -h10 * r; t.t10 = -h01 * r; t.t11 = (1.0 + h00) * r;
+    t.c = k.mu - k.lambda * log1p(js);
+    t.sA = ok ? fabs(det) * k.W : 0.0;
+    return t;
+}
+
+// q_k = sum_l K_e[k][l] p_l for the three corners; returns p^T K_e p.
+__device__ __forceinline__ double hyper_tangent_apply(const HyperTangent &t, const HyperConsts &k, const double2 p0, const double2 p1,
+                                                      const double2 p2, double2 (&q)[3]) {
+    const double g0x = p0.x - p2.x, g0y = p0.y - p2.y, g1x = p1.x - p2.x, g1y = p1.y - p2.y;
+    const double d00 = g0x * t.di - g1x * t.ci, d01 = g1x * t.ai - g0x * t.bi;         // dH
+    const double d10 = g0y * t.di - g1y * t.ci, d11 = g1y * t.ai - g0y * t.bi;
+    // M = T dH^T, then M T
+    const double m00 = t.t00 * d00 + t.t01 * d01, m01 = t.t00 * d10 + t.t01 * d11;
+    const double m10 = t.t10 * d00 + t.t11 * d01, m11 = t.t10 * d10 + t.t11 * d11;
+    const double lt = k.lambda * (t.t00 * d00 + t.t01 * d01 + t.t10 * d10 + t.t11 * d11);
+    const double s00 = k.mu * d00 + t.c * (m00 * t.t00 + m01 * t.t10) + lt * t.t00;
+    const double s01 = k.mu * d01 + t.c * (m00 * t.t01 + m01 * t.t11) + lt * t.t01;
+    const double s10 = k.mu * d10 + t.c * (m10 * t.t00 + m11 * t.t10) + lt * t.t10;
+    const double s11 = k.mu * d11 + t.c * (m10 * t.t01 + m11 * t.t11) + lt * t.t11;
+    // q = A dP Jg^-T, Jg^-T = [[di, -ci], [-bi, ai]]
+    const double q0x = t.sA * (s00 * t.di - s01 * t.bi), q0y = t.sA * (s10 * t.di - s11 * t.bi);
+    const double q1x = t.sA * (s01 * t.ai - s00 * t.ci), q1y = t.sA * (s11 * t.ai - s10 * t.ci);
+    q[0] = make_double2(q0x, q0y);
+    q[1] = make_double2(q1x, q1y);
+    q[2] = make_double2(-(q0x + q1x), -(q0y + q1y));
+    return g0x * q0x + g0y * q0y + g1x * q1x + g1y * q1y;
 }
 
 // The finishing launch's per-thread part over the tile partials work[3][n] = {energy, min J, inverted count}: thread tid of

@@ -23,12 +23,6 @@ namespace hfem {
 
 constexpr int kHyperBlock = 512, kHyperNpt = 2, kHyperEpt = 4, kHyperFinish = 256;
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    return v;
-}
-
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | acc[4][cap_owned] double | red[3][BLOCK/64]
 template <int BLOCK, int NPT, int EPT, typename V2>
 __global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(

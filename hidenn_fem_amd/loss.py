@@ -367,8 +367,8 @@ def require_linear(loss_fn, who: str):
     silently work on its linearisation."""
     if isinstance(loss_fn, NeoHookeanLoss2D):
         raise NotImplementedError(f"{who}: small-strain linear elasticity only; a NeoHookeanLoss2D would be linearised "
-                                  "silently (a Newton-Krylov solve on its tangent does not exist yet) -- minimise it with "
-                                  "FusedLBFGS / FusedAdam, or pass an EnergyLoss2D")
+                                  "silently -- its equilibrium is hidenn_fem_amd.newton.NewtonKrylovSolver / newton_solve_ "
+                                  "(Newton-Krylov on the tangent); or pass an EnergyLoss2D")
 
 
 # ---------------------------------------------------------------- inline losses of examples 1-3

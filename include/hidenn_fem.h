@@ -724,6 +724,29 @@ int hfem_cg_iterate(hfem_cg *cg, double *u_free, int32_t n_iter, void *stream);
 int hfem_cg_status(hfem_cg *cg, double *status_host, void *stream);
 int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void *stream);
 
+/* ------------------------------------------------------------------ Newton-Krylov on the Neo-Hookean tangent (TRI3)
+ * The same driver with a third element kind (csrc/tri3_hyper_cg.hip; hidenn_fem_amd/newton.py): K is the tangent
+ * K_T = d2Pi/du2 of hfem_tri3_hyper_energy_plan's potential at a linearisation point u_lin, on that entry point's plan (TRI3,
+ * ONE element per slot), so the residual launch and the operator share a plan and its row maps.  Per element, with T = F^-T,
+ * L = log1p(j) and dH = dG Jg^-1:  dP = mu dH + (mu - lambda L) T dH^T T + lambda (T : dH) T,  q = |det Jg| W dP Jg^-T; dead
+ * loads do not enter.  An element with J <= 0 contributes a ZERO block and is counted.  K_T may be indefinite: the driver's
+ * breakdown halt (p^T K p <= 0, before u moves) is then the truncation rule of truncated Newton, and a diagonal block that is
+ * not positive definite is the identity in the block-Jacobi preconditioner.
+ *   create_hyper  a QUAD4, paired or host-only plan, or a tile that needs more than 64 KiB of LDS (48 bytes per local node +
+ *                 16 per owned row), is an argument error.
+ *   setup_hyper   binds the coordinate rows, the linearisation point's rows (u_lin_free [n_u][2], u_fixed; fp64, they must
+ *                 stay allocated and unchanged while iterating) and lame[2] = (lambda, mu) (host), W, and builds the
+ *                 preconditioner at u_lin: precond 1 = block Jacobi, 0 = none.  diag_out [n_u][3] (may be NULL): the blocks;
+ *                 info_out[2] (device, may be NULL) = {min J, number of elements with J <= 0} at u_lin.  Pointers are bound,
+ *                 not copied: writing a new point into the same buffers and calling setup_hyper again re-linearises, and a
+ *                 captured hfem_cg_iterate graph stays valid.
+ * hfem_cg_start / iterate / status / apply / start_amg / iterate_amg work on such a solver unchanged; hfem_cg_setup refuses
+ * it, and hfem_cg_setup_hyper refuses a solver of hfem_cg_create.                                                        */
+int hfem_cg_create_hyper(hfem_plan *plan, int64_t n_u, hfem_cg **out);
+int hfem_cg_setup_hyper(hfem_cg *cg, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                        const double *u_fixed, const double lame[2], double W, int32_t precond, double *diag_out,
+                        double *info_out, void *stream);
+
 /* ------------------------------------------------------------------ mesh validity for r-adaptivity (TRI3)
  * What keeps a coordinate update valid (hidenn_fem_amd/radapt.py; no reference counterpart -- the reference's example 4
  * moves the nodes with L-BFGS unguarded and calls a mesh_quality_loss it never defines).  One thread per element over the

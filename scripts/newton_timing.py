@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""The Newton-Krylov solve on the Neo-Hookean tangent, measured (dev tool; records, asserts nothing).
+
+Launches at T1M (1001 x 501 nodes, 10^6 TRI3, fp64, jitter 0.2, left edge clamped, the finite-strain test field on the free
+rows), device events around back-to-back calls on preallocated buffers, the three ALTERNATING in one process, median of 7
+windows each:
+  * `tangent_apply`: hfem_cg_apply on a hfem_cg_create_hyper solver (csrc/tri3_hyper_cg.hip), one-element-per-slot plan;
+  * `neo_hookean_gradient`: hfem_tri3_hyper_energy_plan with HFEM_FLAG_NO_GX on the SAME plan and buffers (the residual of the
+    Newton loop: tile kernel + one-block finish);
+  * `linear_apply`: hfem_cg_apply of FrozenMeshSolver on the PAIRED plan of the same mesh (csrc/tri3_cg.hip).
+Cache regime: the working set stays in the 256 MB Infinity Cache (same buffers every launch).
+
+One load increment of ``python -m examples.example4 --neo-hookean`` (its mesh, material and traction; load 1 / load_steps from
+the linear frozen-mesh solution): per preconditioner the Newton iterations, CG iterations and seconds of
+``NewtonKrylovSolver.solve()`` (host clock, synchronised; the first solve of a solver includes its graph capture), beside the
+increment as the example minimises it without ``--newton``: 100 outer ``FusedLBFGS`` steps, their seconds and the |g|inf reached.
+
+    python scripts/newton_timing.py [--reps 2000] [--out-dir profiles/newton] [--small]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from hidenn_fem_amd import _lib
+from hidenn_fem_amd.loss import EnergyLoss2D, NeoHookeanLoss2D
+from hidenn_fem_amd.mesh import generate_mesh, structured_tri_mesh
+from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+from hidenn_fem_amd.newton import NewtonKrylovSolver
+from hidenn_fem_amd.solve import FrozenMeshSolver, solve_displacement_
+
+F64 = torch.float64
+
+
+def window_us(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def field(x):
+    return torch.stack([0.25 * torch.sin(2.1 * x[:, 0]) * torch.cos(1.3 * x[:, 1]),
+                        0.15 * torch.cos(1.7 * x[:, 0] + 0.3) * torch.sin(2.4 * x[:, 1])], dim=1)
+
+
+def launches(nx, ny, reps):
+    dev = torch.device("cuda:0")
+    coords, conn, geom, bc, _, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=field(coords)[bc],
+                                 neumann_edges=edges)                # the field on the Dirichlet rows too: no jump, no inversion
+    with torch.no_grad():
+        m.u_free.copy_(m.from_caller_order(field(coords)[~bc], "u"))
+    m = m.to(dev)
+    nk = NewtonKrylovSolver(m, NeoHookeanLoss2D(device=dev, dtype=F64))
+    lin = FrozenMeshSolver(m, EnergyLoss2D(device=dev, dtype=F64))
+    lin.refresh()
+    p = torch.randn(m.u_free.shape, dtype=F64, device=dev) * 1e-4
+    nk.apply(p)                                                     # refresh + linearise at the field
+    q, pq = torch.empty_like(p), torch.empty((), dtype=F64, device=dev)
+    L, st = _lib.lib(), _lib.stream_ptr(dev)
+
+    def tangent():
+        _lib.check(L.hfem_cg_apply(nk._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), st), "hfem_cg_apply")
+
+    def gradient():
+        nk._energy(nk._u, nk._g)
+
+    def linear():
+        _lib.check(L.hfem_cg_apply(lin._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), st), "hfem_cg_apply")
+
+    fns = dict(tangent_apply=tangent, neo_hookean_gradient=gradient, linear_apply=linear)
+    for _ in range(20):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in fns}
+    for _ in range(7):                                              # alternating windows
+        for k, f in fns.items():
+            t[k].append(window_us(f, reps))
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    s = nk.plan.stats
+    rec = dict(mesh=f"{nx}x{ny} structured TRI3, jitter 0.2, left edge clamped", n_elems=m.Nelems, n_nodes=m.Nnodes,
+               n_u_rows=int(m.u_free.shape[0]), min_J=nk.info[0].item(), inverted=nk.info[1].item(),
+               plan_tangent=dict(paired=bool(s["paired"]), n_tiles=s["n_tiles"], max_tile_nodes=s["max_tile_nodes"],
+                                 max_tile_elems=s["max_tile_elems"], threads_per_tile=512),
+               plan_linear=dict(paired=bool(lin.plan.stats["paired"]), n_tiles=lin.plan.stats["n_tiles"]),
+               regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)",
+               reps_per_window=reps, windows=7)
+    for k in fns:
+        rec[k] = dict(us=med[k], windows_us=t[k])
+    rec["ratio_tangent_over_gradient"] = med["tangent_apply"] / med["neo_hookean_gradient"]
+    rec["ratio_tangent_over_linear_apply"] = med["tangent_apply"] / med["linear_apply"]
+    return rec
+
+
+def increment(nx, ny, load_steps=8, lbfgs_steps=100, E=10e9, nu=0.3):
+    from hidenn_fem_amd.optim import FusedLBFGS
+    dev = torch.device("cuda:0")
+    holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
+    sides = {"up": 0, "down": 0, "right": 2, "left": 1}
+    nodes, conn, geom, bc, _, edges = generate_mesh(2.0, 1.0, holes, sides, nx, ny)
+    m = PiecewiseLinearShapeNN2D(nodes.to(F64), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
+    m.node_coords_free.requires_grad_(False)
+    lf = NeoHookeanLoss2D(E=E, nu=nu, length=2.0, height=1.0, device=dev, dtype=F64)
+    scale = 1.0 / load_steps
+    tr = lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -scale * E / 500.0)], dim=1)
+    solve_displacement_(m, EnergyLoss2D(E=E, nu=nu, device=dev, dtype=F64, grad_convention="physical"), t_force=tr, rtol=1e-10)
+    u_lin = m.u_free.detach().clone()
+    rec = dict(mesh=f"example 4 plate with holes, {nx}x{ny}", n_elems=m.Nelems, n_nodes=m.Nnodes, load=scale, newton={})
+    for pc in ("block_jacobi", "amg", "none"):
+        with torch.no_grad():
+            m.u_free.copy_(u_lin)
+        s = NewtonKrylovSolver(m, lf, t_force=tr, precond=pc)
+        s.refresh()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = s.solve()
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        with torch.enable_grad():                                   # |g|inf as the example's L-BFGS column states it
+            m.u_free.grad = None
+            lf(m, None, tr).backward()
+        rec["newton"][pc] = dict(newton_iterations=info.newton_iterations, cg_iterations=info.cg_iterations, seconds=sec,
+                                 reason=info.reason, grad_norm_over_rhs=info.grad_norm / max(info.rhs_norm, 1e-300),
+                                 g_inf=m.u_free.grad.abs().max().item(), energy=info.energy, min_J=info.min_J,
+                                 cg_per_newton=[h["cg_iterations"] for h in info.history],
+                                 cg_reasons=[h["cg_reason"] for h in info.history], steps=[h["step"] for h in info.history])
+    with torch.no_grad():
+        m.u_free.copy_(u_lin)
+    opt = FusedLBFGS([m.u_free])
+
+    def closure():
+        opt.zero_grad()
+        value = lf(m, None, tr)
+        value.backward()
+        return value
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(lbfgs_steps):
+        opt.step(closure)
+    torch.cuda.synchronize()
+    sec = time.perf_counter() - t0
+    value = closure()
+    rec["fused_lbfgs"] = dict(steps=lbfgs_steps, seconds=sec, g_inf=m.u_free.grad.abs().max().item(), energy=value.item(),
+                              min_J=float(lf.info[0]))
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=2000)
+    ap.add_argument("--out-dir", default="")
+    ap.add_argument("--small", action="store_true", help="101x51 / 60x30 nodes (a check that the script runs)")
+    a = ap.parse_args()
+    big = not a.small
+    rec = dict(launches=launches(*((1001, 501) if big else (101, 51)), a.reps),
+               increment=increment(*((200, 100) if big else (60, 30))))
+    line = json.dumps(rec)
+    print(line)
+    if a.out_dir:
+        os.makedirs(a.out_dir, exist_ok=True)
+        with open(os.path.join(a.out_dir, "newton_timing_T1M.json" if big else "newton_timing_small.json"), "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
