@@ -343,10 +343,12 @@ int launch_tri3_stream(const hfem_plan *plan, int n_grid, int tile_begin, const 
                        const double *u_free, const double *u_fixed, const Tri3Consts &kc, const double *T_edge,
                        double4 tc, double *partials, double *gx_free, double *gu_free, int skip_edges, int store_policy,
                        const LagSum &lag, hipStream_t s, int ablate = 0);
-// tri3_pair.hip: paired-slot kernel on a paired plan (plan_elem_order 5, the default); 1 = launched, 0 = tile shape not held
-struct PairLaunch {
+// Everything a tiled TRI3 launch passes to its kernel, whatever the launcher and the instance (host only: kernels receive the
+// fields one by one).  The entry points (tri3_energy.hip) fill it once per call; the pair launchers below take it by value
+// and overwrite the plan-derived fields (pd, max_nodes, max_owned, lds, col_stride, chain) with their own.
+struct TileLaunch {
     PlanDev pd;
-    int grid = 0, tile_begin = 0;
+    int grid = 0, tile_begin = 0;                   // grid: the pair launchers' (the one-element-per-slot ones are told theirs)
     const void *x_free = nullptr, *x_fixed = nullptr, *u_free = nullptr, *u_fixed = nullptr;
     Tri3Consts k;
     const double4 *T_edge = nullptr;
@@ -358,20 +360,23 @@ struct PairLaunch {
     int lab_bits = 0;             // lab build: ablation bits (tri3_pair.hip)
     int col_stride = 256;         // columns of every tile's slot array (HostPlan::col_stride)
     unsigned long long *span = nullptr;   // this launch's span-stamp slot (or NULL)
+    unsigned long long *stamps = nullptr; // one element per slot: the plan's stamp array (lab build; NULL otherwise)
     size_t lds = 0;
     hipStream_t s = nullptr;
+    int stagger = 0, stagger_cfg = 0x108; // one element per slot, lab only (0 in the product build)
 };
-int launch_tri3_pair(const hfem_plan *plan, PairLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
+// tri3_pair.hip: paired-slot kernel on a paired plan (plan_elem_order 5, the default); 1 = launched, 0 = tile shape not held
+int launch_tri3_pair(const hfem_plan *plan, TileLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
                      const AdamFuse &af);
 // tri3_pair_f32.hip: the paired-slot pass in fp32 ARITHMETIC on float rows (HFEM_FLAG_FP32_MATH); 1 = launched, 0 = no instance
-int launch_tri3_pair_f32(const hfem_plan *plan, PairLaunch A, bool hasb, const LagSum &lag, const AdamFuse *adam = nullptr);
+int launch_tri3_pair_f32(const hfem_plan *plan, TileLaunch A, bool hasb, const LagSum &lag, const AdamFuse *adam = nullptr);
 #ifdef HFEM_LAB
 // tri3_pair_lab.hip (lab build only): the instrumented copy of the paired-slot kernel (ablation bits, forced slot loops)
-int launch_tri3_pair_lab(const hfem_plan *plan, PairLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
+int launch_tri3_pair_lab(const hfem_plan *plan, TileLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
                          const AdamFuse &af);
 #endif
 // tri3_pair_pipe.hip: the same pass with tpw tiles per workgroup, software-pipelined; 1 = launched, 0 = no instance
-int launch_tri3_pair_pipe(const hfem_plan *plan, PairLaunch A, int n_tiles, int tpw, const LagSum &lag);
+int launch_tri3_pair_pipe(const hfem_plan *plan, TileLaunch A, int n_tiles, int tpw, const LagSum &lag);
 // tri3_det.hip: fixed-order (bit-reproducible) energy + gradients; phys: the physical gradient convention
 int launch_tri3_det(hfem_plan *plan, const double *x_free, const double *x_fixed, const double *u_free,
                     const double *u_fixed, const Tri3Consts &kc, const double *T_edge, double4 tc, double *loss_out,

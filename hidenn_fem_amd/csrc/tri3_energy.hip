@@ -506,25 +506,30 @@ int grid_for(int64_t n, int cap = 256 * 8) {
     return (int)g;
 }
 
-// everything a tiled launch passes to its kernel, whatever the instance
-struct Tri3Launch {
-    PlanDev pd;
-    int tile_begin = 0;
-    const void *x_free = nullptr, *x_fixed = nullptr, *u_free = nullptr, *u_fixed = nullptr;
-    Tri3Consts k;
-    const double4 *T_edge = nullptr;
-    double4 tc;
-    double *partials = nullptr;
-    void *gx = nullptr, *gu = nullptr;
-    int max_nodes = 0, max_owned = 0, skip_edges = 0;
-    unsigned long long *stamps = nullptr;
-    size_t lds = 0;
-    hipStream_t s = nullptr;
-    int stagger = 0, stagger_cfg = 0x108;          // lab only (0 in the product build)
-};
+// The launch arguments every TRI3 plan entry point fills the same way (TileLaunch, hfem_plan_dev.h), with the plan-derived
+// fields of the one-element-per-slot launchers below; the caller adds `partials` and, for the pair launchers, `grid`.
+TileLaunch tile_launch(const hfem_plan *plan, const void *x_free, const void *x_fixed, const void *u_free, const void *u_fixed,
+                       const double mat[4], double W, const double Bk[6], const double *T_edge, const double Tconst[4],
+                       int tile_begin, void *gx, void *gu, int flags, hipStream_t s) {
+    TileLaunch A;
+    A.pd = plan_dev(plan); A.tile_begin = tile_begin;
+    A.x_free = x_free; A.x_fixed = x_fixed; A.u_free = u_free; A.u_fixed = u_fixed;
+    A.k = make_consts(mat, W, Bk); A.T_edge = (const double4 *)T_edge;
+    A.tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
+    A.gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx; A.gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu;
+    A.max_nodes = plan->host.max_nodes; A.max_owned = plan->host.max_owned; A.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0;
+    A.stamps = plan->d_stamps; A.lds = (size_t)plan->lds_bytes; A.s = s;
+    return A;
+}
+
+bool has_body_force(const double Bk[6]) {
+    for (int i = 0; Bk && i < 6; ++i)
+        if (Bk[i] != 0.0) return true;
+    return false;
+}
 
 template <int BLK, int NPT, int EPT, bool HB, int SP, typename V2, int CO, bool ADAM, bool PHYS, bool STAMP = false>
-void launch_fast(const Tri3Launch &A, int grid, const AdamFuse &af, const LagSum &lag) {
+void launch_fast(const TileLaunch &A, int grid, const AdamFuse &af, const LagSum &lag) {
     const size_t lds = CO > 0 ? (size_t)(A.max_nodes * 32 + CO * 32 + 128) : A.lds;
     if constexpr (!HB && !PHYS && !STAMP && BLK == 512 && (SP == 16 || SP == 2)) {
         if (lag.pg_blocks) {                               // HFEM_FLAG_PEER_GET: the instance with the in-launch get
@@ -542,7 +547,7 @@ void launch_fast(const Tri3Launch &A, int grid, const AdamFuse &af, const LagSum
 }
 
 template <int BLK>
-void launch_generic(const Tri3Launch &A, int grid) {
+void launch_generic(const TileLaunch &A, int grid) {
     hipLaunchKernelGGL((tri3_energy_tiled_kernel<BLK, 0>), dim3(grid), dim3(BLK), A.lds, A.s, A.pd, A.tile_begin,
                        (const double2 *)A.x_free, (const double2 *)A.x_fixed, (const double2 *)A.u_free,
                        (const double2 *)A.u_fixed, A.k, A.T_edge, A.tc, A.partials, (double2 *)A.gx, (double2 *)A.gu,
@@ -552,7 +557,7 @@ void launch_generic(const Tri3Launch &A, int grid) {
 // fp64 rows, reference convention: the instance of the register-prefetched kernel that holds this plan's tile shape
 // (false: none does -- the caller takes the generic loop kernel).  `lag` only reaches the default instances
 // (512 threads, no body force, write-through stores); the entry point has checked that before asking for it.
-bool launch_fast_f64(const hfem_plan *plan, const Tri3Launch &A, int n, bool hasb, const LagSum &lag) {
+bool launch_fast_f64(const hfem_plan *plan, const TileLaunch &A, int n, bool hasb, const LagSum &lag) {
     const HostPlan &h = plan->host;
     const int blk = plan->tune.tiled_block, sp = plan->tune.store_policy;
     const int n_lag = n + (lag.prev ? 1 : 0) + lag.pg_blocks;
@@ -604,6 +609,82 @@ struct PlanLock {
     explicit PlanLock(hfem_plan *p) : g(p->mu) {}
     std::lock_guard<std::mutex> g;
 };
+
+// HFEM_ARG_CHECK inside a helper the entry points share: the message names the entry point (`who` = its __func__)
+#define HFEM_ARG_CHECK_FOR(who, cond, msg) \
+    do { if (!(cond)) { set_error(std::string(who) + ": " + (msg)); return -1; } } while (0)
+
+// tile_end < 0 = the whole plan
+int tile_range(const hfem_plan *plan, const char *who, int32_t tile_begin, int32_t &tile_end) {
+    const int32_t nt = (int32_t)plan->host.tiles.size();
+    if (tile_end < 0) tile_end = nt;
+    HFEM_ARG_CHECK_FOR(who, tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    return 0;
+}
+
+double *bank_ptr(const hfem_plan *plan, int bank) { return plan->d_partials + (size_t)bank * plan->host.tiles.size(); }
+
+int sum_partials(const double *partials, int n, double *loss_out, void *stream, const char *label) {
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, partials, n, loss_out);
+    return launch_status(label);
+}
+
+// The partials banks of the lagged loss sum (hfem_tri3_energy_plan, the fp32-arithmetic branch of hfem_tri3_energy_plan_f32,
+// hfem_tri3_energy_adam_step_ex; under the plan's mutex).  A launch that leaves its tile energies unsummed
+// (HFEM_FLAG_NO_LOSS_SUM) writes the OTHER bank, so that the next launch can reduce them with its one extra workgroup
+// (HFEM_FLAG_SUM_PREVIOUS) while it fills this one.  HFEM_FLAG_SAME_BANK: the launch is another tile range of the SAME
+// evaluation as the previous unsummed launch (boundary tiles after interior tiles, hidenn_fem_amd/sharded.py): its tile
+// energies go to the bank that launch wrote.
+struct LossBanks {
+    int wbank = 0;                 // the bank this launch writes
+    double *partials = nullptr;    // ... and the slot of its first tile there
+
+    // before the launch: the protocol's checks, the write bank, and what the extra workgroup sums (lag.prev / prev_n / out)
+    int begin(const hfem_plan *plan, const char *who, int flags, int tile_begin, int n, void *stream, double *loss_out, LagSum &lag) {
+        const bool no_sum = (flags & HFEM_FLAG_NO_LOSS_SUM) != 0, lag_consume = (flags & HFEM_FLAG_SUM_PREVIOUS) != 0;
+        const bool same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
+        HFEM_ARG_CHECK_FOR(who, !lag_consume || no_sum, "HFEM_FLAG_SUM_PREVIOUS needs HFEM_FLAG_NO_LOSS_SUM");
+        HFEM_ARG_CHECK_FOR(who, !lag_consume || (plan->prev_n > 0 && n > 0), "HFEM_FLAG_SUM_PREVIOUS: no previous unsummed launch on this plan");
+        HFEM_ARG_CHECK_FOR(who, !lag_consume || plan->prev_stream == stream,
+                           "HFEM_FLAG_SUM_PREVIOUS: the previous unsummed launch went to another stream (one plan = one stream)");
+        HFEM_ARG_CHECK_FOR(who, !same_bank || (no_sum && !lag_consume), "HFEM_FLAG_SAME_BANK needs HFEM_FLAG_NO_LOSS_SUM and excludes HFEM_FLAG_SUM_PREVIOUS");
+        wbank = no_sum && !same_bank ? (plan->bank ^ 1) : plan->bank;
+        partials = bank_ptr(plan, wbank) + tile_begin;
+        if (lag_consume) {
+            lag.prev = bank_ptr(plan, plan->bank) + plan->prev_begin;
+            lag.prev_n = plan->prev_n;
+            lag.out = loss_out;
+        }
+        return 0;
+    }
+
+    // after the launch, which left n_partials energies (the tile count, except in lab variants): remember them for the next
+    // launch (HFEM_FLAG_NO_LOSS_SUM) or sum them now
+    int finish(hfem_plan *plan, const char *label, int flags, int tile_begin, int tile_end, int n_partials, void *stream, double *loss_out) const {
+        if (!(flags & HFEM_FLAG_NO_LOSS_SUM)) return sum_partials(partials, n_partials, loss_out, stream, label);
+        const bool same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
+        const int n = tile_end - tile_begin;
+        if (same_bank && plan->prev_n > 0 && n > 0 && n_partials == n &&
+            (tile_end == plan->prev_begin || tile_begin == plan->prev_begin + plan->prev_n)) {
+            plan->prev_begin = std::min(plan->prev_begin, tile_begin);      // adjacent ranges of one evaluation: their union
+            plan->prev_n += n;
+        } else if (!same_bank || n > 0) {
+            plan->prev_begin = tile_begin; plan->prev_n = n > 0 ? n_partials : 0;
+        }
+        plan->bank = wbank; plan->prev_stream = stream;
+        return 0;
+    }
+};
+
+// HFEM_FLAG_PEER_GET: the in-launch get of this plan (hfem_plan_set_peer_get) into `lag`.  plain: the call has the default
+// forces and gradient convention (the instances with the get have no others)
+int peer_get_fill(const hfem_plan *plan, const char *who, bool plain, int n, LagSum &lag) {
+    HFEM_ARG_CHECK_FOR(who, plan->peer_get, "HFEM_FLAG_PEER_GET: hfem_plan_set_peer_get has not been called");
+    HFEM_ARG_CHECK_FOR(who, plain && n > 0, "HFEM_FLAG_PEER_GET: default forces and convention, a non-empty tile range");
+    lag.pg = plan->peer_get; lag.pg_blocks = kPeerGetBlocks;
+    lag.wait_begin = plan->peer_wait_begin; lag.wait_end = plan->peer_wait_end;
+    return 0;
+}
 
 template <typename T>
 int hfem_upload(T **dst, const void *src, size_t count, int64_t &bytes) {
@@ -904,18 +985,15 @@ extern "C" int hfem_tri3_energy_plan(hfem_plan *plan, const double *x_free, cons
     HFEM_ARG_CHECK(plan->host.npe == 3, "this plan was built for QUAD4: use hfem_quad4_energy_plan");
     HFEM_ARG_CHECK(x_free && u_free, "x_free / u_free must be given");
     const HostPlan &h = plan->host;
-    const int32_t nt = (int32_t)h.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     HFEM_ARG_CHECK(h.ned == 0 || T_edge || Tconst, "plan has Neumann edges: need a traction table");
     if (int rc = use_device(plan->device)) return rc;
     PlanLock lock(plan);
     HFEM_LAB_REFRESH_TUNE(plan)
-    hipStream_t s = (hipStream_t)stream;
-    const int n = tile_end - tile_begin;
-    const double4 tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
-    bool hasb = false;
-    for (int i = 0; i < 6; ++i) hasb = hasb || (Bk && Bk[i] != 0.0);
+    const int nt = (int)h.tiles.size(), n = tile_end - tile_begin;
+    TileLaunch A = tile_launch(plan, x_free, x_fixed, u_free, u_fixed, mat, W, Bk, T_edge, Tconst, tile_begin, gx_free, gu_free,
+                               flags, (hipStream_t)stream);
+    const bool hasb = has_body_force(Bk);
     const bool phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0;
     const bool phys_fast = phys && !(flags & HFEM_FLAG_DETERMINISTIC) &&
                            (h.paired || (plan->tune.tiled_block == 512 && h.max_nodes <= 2 * 512 && h.max_elems <= 4 * 512));
@@ -924,61 +1002,29 @@ extern "C" int hfem_tri3_energy_plan(hfem_plan *plan, const double *x_free, cons
         // tiled PHYS instance does not hold
         HFEM_ARG_CHECK(tile_begin == 0 && tile_end == nt, "HFEM_FLAG_DETERMINISTIC / physical fallback: whole plan only");
         HFEM_ARG_CHECK(!(flags & (HFEM_FLAG_NO_LOSS_SUM | HFEM_FLAG_SUM_PREVIOUS | HFEM_FLAG_PEER_GET)), "HFEM_FLAG_DETERMINISTIC always delivers the loss and has no in-launch get");
-        return launch_tri3_det(plan, x_free, x_fixed, u_free, u_fixed, make_consts(mat, W, Bk), T_edge, tc, loss_out,
-                               (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free, (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free,
-                               (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0, phys, s);
+        return launch_tri3_det(plan, x_free, x_fixed, u_free, u_fixed, A.k, T_edge, A.tc, loss_out, (double *)A.gx, (double *)A.gu,
+                               A.skip_edges, phys, A.s);
     }
-    // partials banks: a launch that leaves its tile energies unsummed writes the OTHER bank, so that the next launch
-    // can reduce them with its one extra workgroup (HFEM_FLAG_SUM_PREVIOUS) while it fills this one
     const bool lag_consume = (flags & HFEM_FLAG_SUM_PREVIOUS) != 0;
-    HFEM_ARG_CHECK(!lag_consume || (flags & HFEM_FLAG_NO_LOSS_SUM), "HFEM_FLAG_SUM_PREVIOUS needs HFEM_FLAG_NO_LOSS_SUM");
-    HFEM_ARG_CHECK(!lag_consume || (plan->prev_n > 0 && n > 0), "HFEM_FLAG_SUM_PREVIOUS: no previous unsummed launch on this plan");
-    HFEM_ARG_CHECK(!lag_consume || plan->prev_stream == stream,
-                   "HFEM_FLAG_SUM_PREVIOUS: the previous unsummed launch went to another stream (one plan = one stream)");
-    // HFEM_FLAG_SAME_BANK: this launch is another tile range of the SAME evaluation as the previous unsummed launch (boundary
-    // tiles after interior tiles, hidenn_fem_amd/sharded.py): its tile energies go to the bank that launch wrote
-    const bool same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
-    HFEM_ARG_CHECK(!same_bank || ((flags & HFEM_FLAG_NO_LOSS_SUM) && !lag_consume), "HFEM_FLAG_SAME_BANK needs HFEM_FLAG_NO_LOSS_SUM and excludes HFEM_FLAG_SUM_PREVIOUS");
-    const int wbank = (flags & HFEM_FLAG_NO_LOSS_SUM) ? (same_bank ? plan->bank : (plan->bank ^ 1)) : plan->bank;
-    double *pbase = plan->d_partials + (size_t)wbank * nt;
+    LossBanks banks;
     LagSum lag;
-    if (lag_consume) {
-        HFEM_ARG_CHECK(h.paired || (plan->tune.tiled_fast && plan->tune.tiled_block == 512 && !hasb && !phys && plan->tune.store_policy != 0 &&
-                       h.max_nodes <= 1024 && h.max_elems <= 2048),
-                       "HFEM_FLAG_SUM_PREVIOUS: only the default (register-prefetched, 512-thread) kernel path implements it");
-        lag.prev = plan->d_partials + (size_t)plan->bank * nt + plan->prev_begin;
-        lag.prev_n = plan->prev_n;
-        lag.out = loss_out;
-    }
-    if (flags & HFEM_FLAG_PEER_GET) {
-        HFEM_ARG_CHECK(plan->peer_get, "HFEM_FLAG_PEER_GET: hfem_plan_set_peer_get has not been called");
-        HFEM_ARG_CHECK(!hasb && !phys && n > 0, "HFEM_FLAG_PEER_GET: default forces and convention, a non-empty tile range");
-        lag.pg = plan->peer_get; lag.pg_blocks = kPeerGetBlocks;
-        lag.wait_begin = plan->peer_wait_begin; lag.wait_end = plan->peer_wait_end;
-    }
+    if (int rc = banks.begin(plan, __func__, flags, tile_begin, n, stream, loss_out, lag)) return rc;
+    HFEM_ARG_CHECK(!lag_consume || h.paired || (plan->tune.tiled_fast && plan->tune.tiled_block == 512 && !hasb && !phys && plan->tune.store_policy != 0 &&
+                   h.max_nodes <= 1024 && h.max_elems <= 2048),
+                   "HFEM_FLAG_SUM_PREVIOUS: only the default (register-prefetched, 512-thread) kernel path implements it");
+    if (flags & HFEM_FLAG_PEER_GET)
+        if (int rc = peer_get_fill(plan, __func__, !hasb && !phys, n, lag)) return rc;
     int n_partials = n;
     if (n > 0) {
-        Tri3Launch A;
-        A.pd = plan_dev(plan); A.tile_begin = (int)tile_begin;
-        A.x_free = x_free; A.x_fixed = x_fixed; A.u_free = u_free; A.u_fixed = u_fixed;
-        A.k = make_consts(mat, W, Bk); A.T_edge = (const double4 *)T_edge; A.tc = tc; A.partials = pbase + tile_begin;
-        A.gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free; A.gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free;
-        A.max_nodes = h.max_nodes; A.max_owned = h.max_owned; A.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0;
-        A.stamps = plan->d_stamps; A.lds = (size_t)plan->lds_bytes; A.s = s;
+        A.partials = banks.partials; A.grid = n + (lag.prev ? 1 : 0) + lag.pg_blocks;
         bool launched = false;
         HFEM_LAB_TRI3_LAUNCH(plan, A, n, hasb, phys, lag, n_partials, launched)
         if (!launched && h.paired) {      // paired plan (plan_elem_order 5, the default): its records are the pair kernel's
-            PairLaunch P;
-            P.grid = n + (lag.prev ? 1 : 0) + lag.pg_blocks; P.tile_begin = (int)tile_begin;
-            P.x_free = x_free; P.x_fixed = x_fixed; P.u_free = u_free; P.u_fixed = u_fixed;
-            P.k = A.k; P.T_edge = A.T_edge; P.tc = tc; P.partials = A.partials; P.gx = A.gx; P.gu = A.gu;
-            P.skip_edges = A.skip_edges; P.s = s;
-
             HFEM_ARG_CHECK(!(lag.prev && (hasb || phys)), "HFEM_FLAG_SUM_PREVIOUS: default forces and convention only");
-            if (plan->span_buf) P.span = plan->span_buf + (size_t)(plan->span_next++ % plan->span_slots) * 2 * (size_t)nt;
+            if (plan->span_buf) A.span = plan->span_buf + (size_t)(plan->span_next++ % plan->span_slots) * 2 * (size_t)nt;
             int rc_pair = 0;
-            HFEM_LAB_PAIR_LAUNCH(plan, P, n, hasb, phys, lag, rc_pair)
-            if (!rc_pair) rc_pair = launch_tri3_pair(plan, P, (hasb || phys) ? 1 : 0, hasb, phys, lag, AdamFuse{});
+            HFEM_LAB_PAIR_LAUNCH(plan, A, n, hasb, phys, lag, rc_pair)
+            if (!rc_pair) rc_pair = launch_tri3_pair(plan, A, (hasb || phys) ? 1 : 0, hasb, phys, lag, AdamFuse{});
             HFEM_ARG_CHECK(rc_pair == 1, "paired plan: tile shape outside the pair kernel's instances");
             launched = true;
         }
@@ -998,19 +1044,7 @@ extern "C" int hfem_tri3_energy_plan(hfem_plan *plan, const double *x_free, cons
         }
         if (int rc = launch_status("hfem_tri3_energy_plan")) return rc;
     }
-    if (flags & HFEM_FLAG_NO_LOSS_SUM) {
-        if (same_bank && plan->prev_n > 0 && n > 0 && n_partials == n &&
-            (tile_end == plan->prev_begin || tile_begin == plan->prev_begin + plan->prev_n)) {
-            plan->prev_begin = std::min(plan->prev_begin, (int)tile_begin);      // adjacent ranges of one evaluation: their union
-            plan->prev_n += n;
-        } else if (!same_bank || n > 0) {
-            plan->prev_begin = tile_begin; plan->prev_n = n > 0 ? n_partials : 0;
-        }
-        plan->bank = wbank; plan->prev_stream = stream;
-        return 0;
-    }
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, s, pbase + tile_begin, n_partials, loss_out);
-    return launch_status("hfem_tri3_energy_plan(sum)");
+    return banks.finish(plan, "hfem_tri3_energy_plan(sum)", flags, tile_begin, tile_end, n_partials, stream, loss_out);
 }
 
 // fp32-storage form: x/u rows and the gradient rows are float2 (an fp32 model -- the reference's default dtype --
@@ -1030,100 +1064,51 @@ extern "C" int hfem_tri3_energy_plan_f32(hfem_plan *plan, const float *x_free, c
     HFEM_ARG_CHECK(!(flags & (HFEM_FLAG_PHYSICAL_GRAD | HFEM_FLAG_DETERMINISTIC)), "fp32-storage path: reference convention, atomic accumulation");
     HFEM_ARG_CHECK(f32math || !(flags & HFEM_FLAG_SUM_PREVIOUS), "fp32 rows with fp64 arithmetic: no lagged loss sum (HFEM_FLAG_FP32_MATH has it)");
     const HostPlan &h = plan->host;
-    const int32_t nt = (int32_t)h.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     HFEM_ARG_CHECK(h.ned == 0 || T_edge || Tconst, "plan has Neumann edges: need a traction table");
-    bool hasb = false;
-    for (int i = 0; i < 6; ++i) hasb = hasb || (Bk && Bk[i] != 0.0);
+    const bool hasb = has_body_force(Bk);
+    if (f32math) {
+        HFEM_ARG_CHECK(h.paired && h.n_chained == 0, "HFEM_FLAG_FP32_MATH: paired-slot plans only (this mesh's plan keeps one element per slot: drop the flag)");
+        HFEM_ARG_CHECK(!(flags & HFEM_FLAG_PEER_GET), "HFEM_FLAG_FP32_MATH: no in-launch get (the sharded steps run the fp64-arithmetic float-row instances)");
+    } else {
+        HFEM_ARG_CHECK(!hasb && h.max_nodes <= 2 * 512 && h.max_elems <= 4 * 512,
+                       "fp32-storage path: needs a zero body force and tiles of <= 1024 nodes / 2048 slots");
+    }
+    if (int rc = use_device(plan->device)) return rc;
+    PlanLock lock(plan);
+    const int n = tile_end - tile_begin;
+    TileLaunch A = tile_launch(plan, x_free, x_fixed, u_free, u_fixed, mat, W, Bk, T_edge, Tconst, tile_begin, gx_free, gu_free,
+                               flags, (hipStream_t)stream);
+    LagSum lag;
     if (f32math) {
         // fp32 ARITHMETIC (tri3_pair_f32.hip): paired-slot plans without chained records; body force, tile ranges, the lagged
         // loss sum and the partials banks as hfem_tri3_energy_plan; no in-launch get
-        HFEM_ARG_CHECK(h.paired && h.n_chained == 0, "HFEM_FLAG_FP32_MATH: paired-slot plans only (this mesh's plan keeps one element per slot: drop the flag)");
-        HFEM_ARG_CHECK(!(flags & HFEM_FLAG_PEER_GET), "HFEM_FLAG_FP32_MATH: no in-launch get (the sharded steps run the fp64-arithmetic float-row instances)");
-        if (int rc = use_device(plan->device)) return rc;
-        PlanLock lock(plan);
-        const int n = tile_end - tile_begin;
-        const bool lag_consume = (flags & HFEM_FLAG_SUM_PREVIOUS) != 0, same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
-        HFEM_ARG_CHECK(!lag_consume || (flags & HFEM_FLAG_NO_LOSS_SUM), "HFEM_FLAG_SUM_PREVIOUS needs HFEM_FLAG_NO_LOSS_SUM");
-        HFEM_ARG_CHECK(!lag_consume || (plan->prev_n > 0 && n > 0), "HFEM_FLAG_SUM_PREVIOUS: no previous unsummed launch on this plan");
-        HFEM_ARG_CHECK(!lag_consume || plan->prev_stream == stream, "HFEM_FLAG_SUM_PREVIOUS: the previous unsummed launch went to another stream (one plan = one stream)");
-        HFEM_ARG_CHECK(!same_bank || ((flags & HFEM_FLAG_NO_LOSS_SUM) && !lag_consume), "HFEM_FLAG_SAME_BANK needs HFEM_FLAG_NO_LOSS_SUM and excludes HFEM_FLAG_SUM_PREVIOUS");
-        const int wbank = (flags & HFEM_FLAG_NO_LOSS_SUM) ? (same_bank ? plan->bank : (plan->bank ^ 1)) : plan->bank;
-        double *pb = plan->d_partials + (size_t)wbank * nt;
-        LagSum lag;
-        if (lag_consume) {
-            lag.prev = plan->d_partials + (size_t)plan->bank * nt + plan->prev_begin;
-            lag.prev_n = plan->prev_n;
-            lag.out = loss_out;
-        }
+        LossBanks banks;
+        if (int rc = banks.begin(plan, __func__, flags, tile_begin, n, stream, loss_out, lag)) return rc;
         if (n > 0) {
-            PairLaunch P;
-            P.grid = n + (lag.prev ? 1 : 0); P.tile_begin = (int)tile_begin;
-            P.x_free = x_free; P.x_fixed = x_fixed; P.u_free = u_free; P.u_fixed = u_fixed;
-            P.k = make_consts(mat, W, Bk); P.T_edge = (const double4 *)T_edge;
-            P.tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
-            P.partials = pb + tile_begin;
-            P.gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free; P.gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free;
-            P.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0; P.s = (hipStream_t)stream;
-            HFEM_ARG_CHECK(launch_tri3_pair_f32(plan, P, hasb, lag) == 1, "HFEM_FLAG_FP32_MATH: tile shape outside the fp32 pair kernel's instances");
+            A.partials = banks.partials; A.grid = n + (lag.prev ? 1 : 0);
+            HFEM_ARG_CHECK(launch_tri3_pair_f32(plan, A, hasb, lag) == 1, "HFEM_FLAG_FP32_MATH: tile shape outside the fp32 pair kernel's instances");
             if (int rc = launch_status("hfem_tri3_energy_plan_f32(fp32 arithmetic)")) return rc;
         }
-        if (flags & HFEM_FLAG_NO_LOSS_SUM) {              // the partials-bank bookkeeping of hfem_tri3_energy_plan
-            if (same_bank && plan->prev_n > 0 && n > 0 && (tile_end == plan->prev_begin || tile_begin == plan->prev_begin + plan->prev_n)) {
-                plan->prev_begin = std::min(plan->prev_begin, (int)tile_begin);
-                plan->prev_n += n;
-            } else if (!same_bank || n > 0) {
-                plan->prev_begin = tile_begin; plan->prev_n = n;
-            }
-            plan->bank = wbank; plan->prev_stream = stream;
-            return 0;
-        }
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, pb + tile_begin, n, loss_out);
-        return launch_status("hfem_tri3_energy_plan_f32(sum)");
+        return banks.finish(plan, "hfem_tri3_energy_plan_f32(sum)", flags, tile_begin, tile_end, n, stream, loss_out);
     }
-    HFEM_ARG_CHECK(!hasb && h.max_nodes <= 2 * 512 && h.max_elems <= 4 * 512,
-                   "fp32-storage path: needs a zero body force and tiles of <= 1024 nodes / 2048 slots");
-    if (int rc = use_device(plan->device)) return rc;
-    PlanLock lock(plan);
-    hipStream_t s = (hipStream_t)stream;
-    const int n = tile_end - tile_begin;
-    double *pbase = plan->d_partials + (size_t)plan->bank * nt + tile_begin;
-    LagSum lag;
-    if (flags & HFEM_FLAG_PEER_GET) {
-        HFEM_ARG_CHECK(plan->peer_get && n > 0, "HFEM_FLAG_PEER_GET: hfem_plan_set_peer_get first, and a non-empty tile range");
-        lag.pg = plan->peer_get; lag.pg_blocks = kPeerGetBlocks;
-        lag.wait_begin = plan->peer_wait_begin; lag.wait_end = plan->peer_wait_end;
-    }
-    if (n > 0 && h.paired) {
-        PairLaunch P;
-        P.grid = n + lag.pg_blocks; P.tile_begin = (int)tile_begin;
-        P.x_free = x_free; P.x_fixed = x_fixed; P.u_free = u_free; P.u_fixed = u_fixed;
-        P.k = make_consts(mat, W, Bk); P.T_edge = (const double4 *)T_edge;
-        P.tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
-        P.partials = pbase;
-        P.gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free; P.gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free;
-        P.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0; P.s = s;
-        HFEM_ARG_CHECK(launch_tri3_pair(plan, P, 2, false, false, lag, AdamFuse{}) == 1,
-                       "paired plan: tile shape outside the pair kernel's instances");
-        if (int rc = launch_status("hfem_tri3_energy_plan_f32")) return rc;
-    } else if (n > 0) {
-        Tri3Launch A;
-        A.pd = plan_dev(plan); A.tile_begin = (int)tile_begin;
-        A.x_free = x_free; A.x_fixed = x_fixed; A.u_free = u_free; A.u_fixed = u_fixed;
-        A.k = make_consts(mat, W, Bk); A.T_edge = (const double4 *)T_edge;
-        A.tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
-        A.partials = pbase;
-        A.gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free; A.gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free;
-        A.max_nodes = h.max_nodes; A.max_owned = h.max_owned; A.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0;
-        A.stamps = plan->d_stamps; A.lds = (size_t)plan->lds_bytes; A.s = s;
-        if (h.max_elems <= 3 * 512) launch_fast<512, 2, 3, false, 16, float2, 0, false, false>(A, n + lag.pg_blocks, AdamFuse{}, lag);
-        else launch_fast<512, 2, 4, false, 16, float2, 0, false, false>(A, n + lag.pg_blocks, AdamFuse{}, lag);
+    // fp64 arithmetic on float rows stays OUTSIDE the bank protocol, on purpose (tests/test_gpu_loss_banks.py pins it): it
+    // writes the current bank and never flips it, leaves prev_* alone under HFEM_FLAG_NO_LOSS_SUM, ignores
+    // HFEM_FLAG_SAME_BANK and has refused HFEM_FLAG_SUM_PREVIOUS above.  Not LossBanks.
+    A.partials = bank_ptr(plan, plan->bank) + tile_begin;
+    if (flags & HFEM_FLAG_PEER_GET)
+        if (int rc = peer_get_fill(plan, __func__, true, n, lag)) return rc;
+    A.grid = n + lag.pg_blocks;
+    if (n > 0) {
+        if (h.paired)
+            HFEM_ARG_CHECK(launch_tri3_pair(plan, A, 2, false, false, lag, AdamFuse{}) == 1,
+                           "paired plan: tile shape outside the pair kernel's instances");
+        else if (h.max_elems <= 3 * 512) launch_fast<512, 2, 3, false, 16, float2, 0, false, false>(A, A.grid, AdamFuse{}, lag);
+        else launch_fast<512, 2, 4, false, 16, float2, 0, false, false>(A, A.grid, AdamFuse{}, lag);
         if (int rc = launch_status("hfem_tri3_energy_plan_f32")) return rc;
     }
     if (flags & HFEM_FLAG_NO_LOSS_SUM) return 0;
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, s, pbase, n, loss_out);
-    return launch_status("hfem_tri3_energy_plan_f32(sum)");
+    return sum_partials(A.partials, n, loss_out, stream, "hfem_tri3_energy_plan_f32(sum)");
 }
 
 // One training step in one launch: energy + gradients as hfem_tri3_energy_plan, but the write-out applies
@@ -1174,39 +1159,20 @@ extern "C" int hfem_tri3_energy_adam_step_ex(hfem_plan *plan, int32_t dtype, con
         HFEM_ARG_CHECK(plan->host.paired && plan->host.n_chained == 0, "HFEM_FLAG_FP32_MATH: paired-slot plans only (this mesh's plan keeps one element per slot: drop the flag)");
         HFEM_ARG_CHECK(!(flags & (HFEM_FLAG_PEER_GET | HFEM_FLAG_PEER_PUT)), "HFEM_FLAG_FP32_MATH: no in-launch get / put (the sharded steps run the fp64-arithmetic float-row instances)");
     }
-    bool hasb = false;
-    for (int i = 0; i < 6; ++i) hasb = hasb || (Bk && Bk[i] != 0.0);
+    const bool hasb = has_body_force(Bk);
     if (int rc = use_device(plan->device)) return rc;
     PlanLock lock(plan);
-    hipStream_t s = (hipStream_t)stream;
     // a tile RANGE updates exactly the rows its tiles own (element sharding: hidenn_fem_amd/sharded.py, fused steps); the rows
     // of the other tiles are not touched in x_out / u_out -- the caller keeps both parameter buffers complete
-    const int nt = (int)h.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     const int n = tile_end - tile_begin;
-    const bool lag_consume = (flags & HFEM_FLAG_SUM_PREVIOUS) != 0;
-    const bool same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
-    HFEM_ARG_CHECK(!lag_consume || (flags & HFEM_FLAG_NO_LOSS_SUM), "HFEM_FLAG_SUM_PREVIOUS needs HFEM_FLAG_NO_LOSS_SUM");
-    HFEM_ARG_CHECK(!same_bank || ((flags & HFEM_FLAG_NO_LOSS_SUM) && !lag_consume), "HFEM_FLAG_SAME_BANK needs HFEM_FLAG_NO_LOSS_SUM and excludes HFEM_FLAG_SUM_PREVIOUS");
-    HFEM_ARG_CHECK(!lag_consume || (plan->prev_n > 0 && n > 0), "HFEM_FLAG_SUM_PREVIOUS: no previous unsummed launch on this plan");
-    HFEM_ARG_CHECK(!lag_consume || plan->prev_stream == stream,
-                   "HFEM_FLAG_SUM_PREVIOUS: the previous unsummed launch went to another stream (one plan = one stream)");
-    HFEM_ARG_CHECK(!lag_consume || !hasb, "HFEM_FLAG_SUM_PREVIOUS: zero body force only");
-    const int wbank = (flags & HFEM_FLAG_NO_LOSS_SUM) ? (same_bank ? plan->bank : (plan->bank ^ 1)) : plan->bank;
-    double *pbase = plan->d_partials + (size_t)wbank * nt + tile_begin;
+    const bool lag_consume = (flags & HFEM_FLAG_SUM_PREVIOUS) != 0, same_bank = (flags & HFEM_FLAG_SAME_BANK) != 0;
+    LossBanks banks;
     LagSum lag;
-    if (lag_consume) {
-        lag.prev = plan->d_partials + (size_t)plan->bank * nt + plan->prev_begin;
-        lag.prev_n = plan->prev_n;
-        lag.out = loss_out;
-    }
-    if (flags & HFEM_FLAG_PEER_GET) {
-        HFEM_ARG_CHECK(plan->peer_get, "HFEM_FLAG_PEER_GET: hfem_plan_set_peer_get has not been called");
-        HFEM_ARG_CHECK(!hasb && n > 0, "HFEM_FLAG_PEER_GET: zero body force, a non-empty tile range");
-        lag.pg = plan->peer_get; lag.pg_blocks = kPeerGetBlocks;
-        lag.wait_begin = plan->peer_wait_begin; lag.wait_end = plan->peer_wait_end;
-    }
+    if (int rc = banks.begin(plan, __func__, flags, tile_begin, n, stream, loss_out, lag)) return rc;
+    HFEM_ARG_CHECK(!lag_consume || !hasb, "HFEM_FLAG_SUM_PREVIOUS: zero body force only");
+    if (flags & HFEM_FLAG_PEER_GET)
+        if (int rc = peer_get_fill(plan, __func__, !hasb, n, lag)) return rc;
     if (flags & HFEM_FLAG_PEER_PUT) {
         HFEM_ARG_CHECK((flags & HFEM_FLAG_PEER_GET) && plan->peer_put, "HFEM_FLAG_PEER_PUT: with HFEM_FLAG_PEER_GET, after hfem_plan_set_peer_put");
         HFEM_ARG_CHECK(h.paired && (flags & HFEM_FLAG_NO_LOSS_SUM) && !lag_consume && !same_bank,
@@ -1218,7 +1184,7 @@ extern "C" int hfem_tri3_energy_adam_step_ex(hfem_plan *plan, int32_t dtype, con
         lag.put_pos_x = plan->put_pos[0]; lag.put_pos_u = plan->put_pos[1];
         lag.put_bc_next = bc_dev == plan->put_bc[0] ? plan->put_bc[1] : plan->put_bc[0];
         if (plan->prev_n > 0 && plan->prev_stream == stream) {      // the previous evaluation's tile energies (the other bank)
-            lag.put_prev = plan->d_partials + (size_t)plan->bank * nt + plan->prev_begin;
+            lag.put_prev = bank_ptr(plan, plan->bank) + plan->prev_begin;
             lag.put_prev_n = plan->prev_n;
         }
     }
@@ -1227,33 +1193,23 @@ extern "C" int hfem_tri3_energy_adam_step_ex(hfem_plan *plan, int32_t dtype, con
         af.x_out = x_out; af.u_out = u_out;
         af.mx = m_x; af.vx = v_x; af.mu = m_u; af.vu = v_u;
         af.bc = bc_dev; af.lr_x = lr_x; af.lr_u = lr_u; af.b1 = beta1; af.b2 = beta2; af.eps = eps;
-        Tri3Launch A;
-        A.pd = plan_dev(plan); A.tile_begin = tile_begin;
-        A.x_free = x_free; A.x_fixed = x_fixed; A.u_free = u_free; A.u_fixed = u_fixed;
-        A.k = make_consts(mat, W, hasb ? Bk : nullptr); A.T_edge = (const double4 *)T_edge;
-        A.tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
-        A.partials = pbase;
-        A.max_nodes = h.max_nodes; A.max_owned = h.max_owned; A.skip_edges = (flags & HFEM_FLAG_NO_EDGES) ? 1 : 0;
-        A.stamps = plan->d_stamps; A.lds = (size_t)plan->lds_bytes; A.s = s;
-        const int grid = n + (lag_consume ? 1 : 0) + lag.pg_blocks;
+        TileLaunch A = tile_launch(plan, x_free, x_fixed, u_free, u_fixed, mat, W, Bk, T_edge, Tconst, tile_begin, nullptr, nullptr,
+                                   flags, (hipStream_t)stream);
+        A.partials = banks.partials; A.grid = n + (lag.prev ? 1 : 0) + lag.pg_blocks;
         if (h.paired) {
-            PairLaunch P;
-            P.grid = grid; P.tile_begin = tile_begin;
-            P.x_free = x_free; P.x_fixed = x_fixed; P.u_free = u_free; P.u_fixed = u_fixed;
-            P.k = A.k; P.T_edge = A.T_edge; P.tc = A.tc; P.partials = pbase; P.skip_edges = A.skip_edges; P.s = s;
             if (flags & HFEM_FLAG_FP32_MATH) {          // fp32 rows AND fp32 arithmetic (csrc/tri3_pair_f32.hip, ADAM instances)
-                HFEM_ARG_CHECK(launch_tri3_pair_f32(plan, P, hasb, lag, &af) == 1,
+                HFEM_ARG_CHECK(launch_tri3_pair_f32(plan, A, hasb, lag, &af) == 1,
                                "HFEM_FLAG_FP32_MATH: tile shape outside the fp32 pair kernel's instances");
             } else
-            HFEM_ARG_CHECK(launch_tri3_pair(plan, P, dtype == 0 ? 3 : 4, hasb, false, lag, af) == 1,
+            HFEM_ARG_CHECK(launch_tri3_pair(plan, A, dtype == 0 ? 3 : 4, hasb, false, lag, af) == 1,
                            "paired plan: tile shape outside the pair kernel's instances");
         } else {
             // one element per slot (meshes whose elements do not pair): one general instance per row type and force
             const bool e3 = h.max_elems <= 3 * 512;
 #define HFEM_ADAM_FAST(HB, V)                                                                            \
     {                                                                                                    \
-        if (e3) launch_fast<512, 2, 3, HB, 16, V, 0, true, false>(A, grid, af, lag);                     \
-        else launch_fast<512, 2, 4, HB, 16, V, 0, true, false>(A, grid, af, lag);                        \
+        if (e3) launch_fast<512, 2, 3, HB, 16, V, 0, true, false>(A, A.grid, af, lag);                   \
+        else launch_fast<512, 2, 4, HB, 16, V, 0, true, false>(A, A.grid, af, lag);                      \
     }
             if (dtype == 0 && !hasb) HFEM_ADAM_FAST(false, double2)
             else if (dtype == 0) HFEM_ADAM_FAST(true, double2)
@@ -1263,19 +1219,7 @@ extern "C" int hfem_tri3_energy_adam_step_ex(hfem_plan *plan, int32_t dtype, con
         }
         if (int rc = launch_status("hfem_tri3_energy_adam_step")) return rc;
     }
-    if (flags & HFEM_FLAG_NO_LOSS_SUM) {
-        if (same_bank && plan->prev_n > 0 && n > 0 &&
-            (tile_end == plan->prev_begin || tile_begin == plan->prev_begin + plan->prev_n)) {
-            plan->prev_begin = std::min(plan->prev_begin, (int)tile_begin);      // adjacent ranges of one evaluation: their union
-            plan->prev_n += n;
-        } else if (!same_bank || n > 0) {
-            plan->prev_begin = tile_begin; plan->prev_n = n;
-        }
-        plan->bank = wbank; plan->prev_stream = stream;
-        return 0;
-    }
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, s, pbase, n, loss_out);
-    return launch_status("hfem_tri3_energy_adam_step(sum)");
+    return banks.finish(plan, "hfem_tri3_energy_adam_step(sum)", flags, tile_begin, tile_end, n, stream, loss_out);
 }
 
 // Sum, in tile order, of the per-tile partial energies a launch with HFEM_FLAG_NO_LOSS_SUM left in the plan
@@ -1285,14 +1229,10 @@ extern "C" int hfem_plan_loss_sum(hfem_plan *plan, int32_t tile_begin, int32_t t
                                   void *stream) {
     HFEM_ARG_CHECK(plan && loss_out, "null pointer");
     HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
-    const int32_t nt = (int32_t)plan->host.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     if (int rc = use_device(plan->device)) return rc;
     PlanLock lock(plan);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream,
-                       plan->d_partials + (size_t)plan->bank * nt + tile_begin, tile_end - tile_begin, loss_out);
-    return launch_status("hfem_plan_loss_sum");
+    return sum_partials(bank_ptr(plan, plan->bank) + tile_begin, tile_end - tile_begin, loss_out, stream, "hfem_plan_loss_sum");
 }
 
 // Span stamps: a measurement aid for callers that need the duration of the energy kernel INSIDE a launch sequence
@@ -1326,14 +1266,11 @@ static int plan_iface_pack_any(int dtype, hfem_plan *plan, int32_t tile_begin, i
     HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
     HFEM_ARG_CHECK(n_x >= 0 && n_u >= 0 && loss_slot >= n_x + n_u, "bad sizes");
     HFEM_ARG_CHECK((n_x + n_u == 0 || rows) && (n_x == 0 || x_free) && (n_u == 0 || u_free), "null pointer");
-    const int32_t nt = (int32_t)plan->host.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     if (int rc = use_device(plan->device)) return rc;
     PlanLock lock(plan);
-    return launch_iface_pack_sum(dtype, x_free, u_free, rows, n_x, n_u, out, loss_slot,
-                                 plan->d_partials + (size_t)plan->bank * nt + tile_begin, tile_end - tile_begin, counter,
-                                 beta1, beta2, bc_next, (hipStream_t)stream);
+    return launch_iface_pack_sum(dtype, x_free, u_free, rows, n_x, n_u, out, loss_slot, bank_ptr(plan, plan->bank) + tile_begin,
+                                 tile_end - tile_begin, counter, beta1, beta2, bc_next, (hipStream_t)stream);
 }
 
 extern "C" int hfem_plan_iface_pack(hfem_plan *plan, int32_t tile_begin, int32_t tile_end, const double *x_free,
@@ -1402,14 +1339,11 @@ static int plan_iface_put_any(int dtype, hfem_plan *plan, hfem_peer *peer, int32
     HFEM_ARG_CHECK(peer->device == plan->device, "plan and peer windows live on different devices");
     HFEM_ARG_CHECK(n_x >= 0 && n_u >= 0 && loss_slot >= n_x + n_u && loss_slot < peer->stride, "bad sizes");
     HFEM_ARG_CHECK((n_x + n_u == 0 || rows) && (n_x == 0 || x_free) && (n_u == 0 || u_free), "null pointer");
-    const int32_t nt = (int32_t)plan->host.tiles.size();
-    if (tile_end < 0) tile_end = nt;
-    HFEM_ARG_CHECK(tile_begin >= 0 && tile_begin <= tile_end && tile_end <= nt, "bad tile range");
+    if (int rc = tile_range(plan, __func__, tile_begin, tile_end)) return rc;
     if (int rc = use_device(plan->device)) return rc;
     PlanLock lock(plan);
-    return launch_iface_put(peer, dtype, x_free, u_free, rows, n_x, n_u, loss_slot,
-                            plan->d_partials + (size_t)plan->bank * nt + tile_begin, tile_end - tile_begin, counter, beta1,
-                            beta2, bc_next, (hipStream_t)stream);
+    return launch_iface_put(peer, dtype, x_free, u_free, rows, n_x, n_u, loss_slot, bank_ptr(plan, plan->bank) + tile_begin,
+                            tile_end - tile_begin, counter, beta1, beta2, bc_next, (hipStream_t)stream);
 }
 
 extern "C" int hfem_plan_iface_put(hfem_plan *plan, hfem_peer *peer, int32_t tile_begin, int32_t tile_end,

@@ -261,7 +261,7 @@ int g_pair_chain = -1, g_pair_ablate = 0;   // pair kernel: force the slot loop 
 
 #if HFEM_LAB_SECTION == 3
 // lab variants of the TRI3 plan launch (ablations, stamps, pipelined and streamed kernels).  true: launched.
-bool launch_tri3_lab(const hfem_plan *plan, Tri3Launch &A, int n, bool hasb, const LagSum &lag, int *n_partials) {
+bool launch_tri3_lab(const hfem_plan *plan, TileLaunch &A, int n, bool hasb, const LagSum &lag, int *n_partials) {
     const HostPlan &h = plan->host;
     const int blk = plan->tune.tiled_block, abl = g_tiled_ablate;
     if (g_tiled_pipe > 0 && abl == 0) {

@@ -349,7 +349,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_kernel(
 
 constexpr int kPairCapN = 656, kPairCapO = 560;          // compile-time LDS strides of the default tile shape (557 owned nodes)
 template <int BLK, int NPT, int EPT, int CAPO, bool HASB, bool PHYS, typename V2, bool ADAM, bool CHAIN, int SP = 16>
-static void launch_pair_inst2(const PairLaunch &A, const LagSum &lag, const AdamFuse &af) {
+static void launch_pair_inst2(const TileLaunch &A, const LagSum &lag, const AdamFuse &af) {
     constexpr int CAPN = CAPO > 0 ? kPairCapN : 0;
     const size_t lds = CAPO > 0 ? (size_t)(CAPN * 32 + CAPO * 32 + 128) : A.lds;
     if constexpr (!HASB && !PHYS && !CHAIN) {
@@ -367,7 +367,7 @@ static void launch_pair_inst2(const PairLaunch &A, const LagSum &lag, const Adam
                        CAPO > 0 ? CAPO : A.max_owned, A.skip_edges, lag, af, A.col_stride);
 }
 template <int BLK, int NPT, int EPT, int CAPO, bool HASB, bool PHYS, typename V2, bool ADAM>
-static void launch_pair_inst(const PairLaunch &A, const LagSum &lag, const AdamFuse &af) {
+static void launch_pair_inst(const TileLaunch &A, const LagSum &lag, const AdamFuse &af) {
 #ifdef HFEM_LAB
     if (A.chain) { launch_pair_inst2<BLK, NPT, EPT, CAPO, HASB, PHYS, V2, ADAM, true>(A, lag, af); return; }   // strip order: lab evidence only
 #endif
@@ -383,7 +383,7 @@ static void launch_pair_inst(const PairLaunch &A, const LagSum &lag, const AdamF
 // tile, nt stores for the big-mesh policy, and the in-launch get (PG) of each; body force and the physical convention -- not
 // the reference's defaults (src/loss.py:43-45, src/models.py:351) -- share ONE generic shape per block size (<256, 4, 6> /
 // <512, 2, 2>).  Chained records (strip order, plan_elem_order 6) and the store-policy A/B instances exist in the lab build only.
-int launch_tri3_pair(const hfem_plan *plan, PairLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
+int launch_tri3_pair(const hfem_plan *plan, TileLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
                      const AdamFuse &af) {
     const HostPlan &h = plan->host;
     if (!h.paired || !plan->d_elem_pack_hi) return 0;

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 512 ? 3 : (ADAM && EPT > 4 ? 4 : 5)
 }
 
 template <int BLK, int NPT, int EPT, int CAPO, int CAPN, int SP, bool HASB, bool ADAM = false>
-static void launch_pair_f32_inst(const PairLaunch &A, const Tri3ConstsF &kf, const LagSum &lag, const AdamFuse &af = AdamFuse{}) {
+static void launch_pair_f32_inst(const TileLaunch &A, const Tri3ConstsF &kf, const LagSum &lag, const AdamFuse &af = AdamFuse{}) {
     const int cap_n = CAPN > 0 ? CAPN : ((A.max_nodes + 1) & ~1), cap_o = CAPO > 0 ? CAPO : ((A.max_owned + 1) & ~1);
     const size_t lds = (size_t)cap_n * 16 + (size_t)cap_o * 32 + 8 * (BLK / 64);
     hipLaunchKernelGGL((tri3_energy_pair_f32_kernel<BLK, NPT, EPT, CAPO, CAPN, SP, HASB, ADAM>), dim3(A.grid), dim3(BLK), lds, A.s, A.pd,
@@ -281,7 +281,7 @@ static void launch_pair_f32_inst(const PairLaunch &A, const Tri3ConstsF &kf, con
 
 // Launch on a paired plan without chained records; 1 = launched, 0 = no instance holds the plan's tile shape.
 // adam != NULL: the fused optimiser step (instances of the plain shapes; a body force takes the generic one).
-int launch_tri3_pair_f32(const hfem_plan *plan, PairLaunch A, bool hasb, const LagSum &lag, const AdamFuse *adam) {
+int launch_tri3_pair_f32(const hfem_plan *plan, TileLaunch A, bool hasb, const LagSum &lag, const AdamFuse *adam) {
     const HostPlan &h = plan->host;
     if (!h.paired || !plan->d_elem_pack_hi || h.n_chained > 0 || lag.pg_blocks) return 0;
     A.pd = plan_dev(plan);

@@ -328,7 +328,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_lab_kernel(
 
 constexpr int kPairLabCapN = 656, kPairLabCapO = 560;          // compile-time LDS strides of the default tile shape (557 owned nodes)
 template <int BLK, int NPT, int EPT, int CAPO, bool HASB, bool PHYS, typename V2, bool ADAM, bool CHAIN>
-static void launch_pair_lab_inst2(const PairLaunch &A, const LagSum &lag, const AdamFuse &af) {
+static void launch_pair_lab_inst2(const TileLaunch &A, const LagSum &lag, const AdamFuse &af) {
     constexpr int CAPN = CAPO > 0 ? kPairLabCapN : 0;
     const size_t lds = CAPO > 0 ? (size_t)(CAPN * 32 + CAPO * 32 + 128) : A.lds;
     hipLaunchKernelGGL((tri3_energy_pair_lab_kernel<BLK, NPT, EPT, 4, CAPO, HASB, PHYS, V2, ADAM, CHAIN, CAPN>), dim3(A.grid), dim3(BLK), lds, A.s,
@@ -337,7 +337,7 @@ static void launch_pair_lab_inst2(const PairLaunch &A, const LagSum &lag, const 
                        CAPO > 0 ? CAPO : A.max_owned, A.skip_edges, lag, af, A.col_stride, A.lab_bits);
 }
 template <int BLK, int NPT, int EPT, int CAPO, bool HASB, bool PHYS, typename V2, bool ADAM>
-static void launch_pair_lab_inst(const PairLaunch &A, const LagSum &lag, const AdamFuse &af) {
+static void launch_pair_lab_inst(const TileLaunch &A, const LagSum &lag, const AdamFuse &af) {
     if (A.chain) launch_pair_lab_inst2<BLK, NPT, EPT, CAPO, HASB, PHYS, V2, ADAM, true>(A, lag, af);
     else launch_pair_lab_inst2<BLK, NPT, EPT, CAPO, HASB, PHYS, V2, ADAM, false>(A, lag, af);
 }
@@ -345,7 +345,7 @@ static void launch_pair_lab_inst(const PairLaunch &A, const LagSum &lag, const A
 // Launch on a paired plan: picks the instance that holds the plan's tile shape.  1 = launched, 0 = none does.
 // mode: 0 fp64 reference convention (zero body force), 1 general fp64 (body force and / or physical convention),
 //       2 fp32 rows, 3 fused Adam write-out on fp64 rows, 4 the same on fp32 rows (3, 4: hasb selects the body-force instance).
-int launch_tri3_pair_lab(const hfem_plan *plan, PairLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
+int launch_tri3_pair_lab(const hfem_plan *plan, TileLaunch A, int mode, bool hasb, bool phys, const LagSum &lag,
                          const AdamFuse &af) {
     const HostPlan &h = plan->host;
     if (!h.paired || !plan->d_elem_pack_hi) return 0;

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void tri3_energy_pair_pipe_kernel(
 }
 
 template <int NPT, int EPT, int WPS>
-static void launch_pipe_inst(const PairLaunch &A, const LagSum &lag, int n_tiles, int tpw, int grid) {
+static void launch_pipe_inst(const TileLaunch &A, const LagSum &lag, int n_tiles, int tpw, int grid) {
     const size_t lds = (size_t)A.max_nodes * 64 + (size_t)A.max_owned * 32 + 64 + 32 * kPipeMaxTiles;
     hipLaunchKernelGGL((tri3_energy_pair_pipe_kernel<256, NPT, EPT, WPS>), dim3(grid), dim3(256), lds, A.s, A.pd, A.tile_begin,
                        n_tiles, tpw, (const double2 *)A.x_free, (const double2 *)A.x_fixed, (const double2 *)A.u_free,
@@ -243,7 +243,7 @@ static void launch_pipe_inst(const PairLaunch &A, const LagSum &lag, int n_tiles
 
 // Pipelined launch over n_tiles tiles starting at A.tile_begin, tpw tiles per workgroup.  fp64, reference convention, zero
 // body force, plain (unchained) paired plans.  1 = launched, 0 = the plan's tile shape has no instance.
-int launch_tri3_pair_pipe(const hfem_plan *plan, PairLaunch A, int n_tiles, int tpw, const LagSum &lag) {
+int launch_tri3_pair_pipe(const hfem_plan *plan, TileLaunch A, int n_tiles, int tpw, const LagSum &lag) {
     const HostPlan &h = plan->host;
     if (!h.paired || h.n_chained > 0 || !plan->d_elem_pack_hi || tpw < 1 || tpw > kPipeMaxTiles || n_tiles < 1) return 0;
     A.pd = plan_dev(plan);
