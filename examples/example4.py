@@ -131,7 +131,7 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
 
 
 def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3, newton=False,
-                    precond="block_jacobi"):
+                    precond="block_jacobi", quad=False):
     """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
     clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
     of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
@@ -142,20 +142,30 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     ``newton=True`` (``--newton``): the same ramp, predictor and halving rule, each increment solved to equilibrium by
     ``hidenn_fem_amd.newton.NewtonKrylovSolver`` (inexact Newton, truncated PCG on the tangent, preconditioner ``precond``)
     instead of ``FusedLBFGS``; the line then also shows the Newton and CG iterations.  An increment whose Newton solve does
-    not converge is taken back and halved like an inverted one."""
-    from hidenn_fem_amd.loss import NeoHookeanLoss2D
+    not converge is taken back and halved like an inverted one.
+    ``quad=True`` (``--quad``): the same ramp on the plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
+    (``structured_quad_mesh``), with ``Quad4NeoHookeanLoss2D``; ``FusedLBFGS`` only -- there is no QUAD4 tangent yet, so
+    ``newton=True`` raises ``NotImplementedError``."""
+    from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
     from hidenn_fem_amd.solve import solve_displacement_
     dev = torch.device("cuda")
     length, height = 2.0, 1.0
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
-    nodes, conn, geom, bc, mn, edges = generate_mesh(length, height, holes, sides, nx, ny)
+    if quad and newton:
+        raise NotImplementedError("example 4: --neo-hookean --quad runs with FusedLBFGS only (NewtonKrylovSolver needs the "
+                                  "tangent, which exists for TRI3 models only); drop --newton or --quad")
+    if quad:
+        from hidenn_fem_amd.mesh import structured_quad_mesh
+        nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
+    else:
+        nodes, conn, geom, bc, mn, edges = generate_mesh(length, height, holes, sides, nx, ny)
     print(f"nodes {tuple(nodes.shape)} elements {tuple(conn.shape)} dirichlet {int(bc.sum())} neumann edges {tuple(edges.shape)}")
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     model.node_coords_free.requires_grad_(False)                   # frozen mesh: the launch skips the coordinate gradient
-    loss_fn = NeoHookeanLoss2D(E=E, nu=nu, length=length, height=height, device=dev, dtype=dtype)
+    loss_fn = (Quad4NeoHookeanLoss2D if quad else NeoHookeanLoss2D)(E=E, nu=nu, length=length, height=height, device=dev, dtype=dtype)
     tau = E / 500.0
     tip = torch.nonzero(model.from_caller_order(nodes[~bc][:, 0:1].to(dev), "u")[:, 0] > length - 1e-6)[:, 0]
 
@@ -270,7 +280,8 @@ if __name__ == "__main__":
     ap.add_argument("--r-adapt", action="store_true",
                     help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS")
     ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
-    ap.add_argument("--quad", action="store_true", help="with --r-adapt: the plate as nx x ny nodes of QUAD4 cells (no holes)")
+    ap.add_argument("--quad", action="store_true",
+                    help="with --r-adapt or --neo-hookean: the plate as nx x ny nodes of QUAD4 cells (no holes)")
     ap.add_argument("--precond", choices=["block_jacobi", "amg"], default="block_jacobi",
                     help="CG preconditioner of --solve-first and --r-adapt")
     ap.add_argument("--error-estimate", action="store_true",
@@ -283,7 +294,10 @@ if __name__ == "__main__":
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver instead of FusedLBFGS")
     a = ap.parse_args()
     if a.neo_hookean:
-        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond)
+        if a.quad and a.newton:
+            raise SystemExit("example 4: --neo-hookean --quad minimises with FusedLBFGS; --newton needs the Neo-Hookean tangent, "
+                             "which exists for TRI3 models only -- drop --newton or --quad")
+        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,

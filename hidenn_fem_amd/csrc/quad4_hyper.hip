@@ -1,33 +1,35 @@
-// Compressible Neo-Hookean total potential of a TRI3 model on the owner-computes tile plan, gfx950.
+// Compressible Neo-Hookean total potential of a QUAD4 model on the owner-computes tile plan, gfx950.
 // No reference counterpart: every energy of the reference is small-strain linear elasticity.
 //
-// One element per slot (plan_elem_order 3, the records tri3_energy_fast_kernel reads: three local ids + home and skip bits).
-// Phases as in that kernel: row maps and slot records requested up front (NPT / EPT of them into registers, unguarded loads
-// into the plan's padding), rows gathered to LDS, the slot loop accumulating with LDS atomics into the four owned-row
-// accumulators, edges (dead loads, edge2_element unchanged) on boundary tiles, every owned row written exactly once, the
-// tile partials summed in wave order.  NPT x BLOCK covers the 1024 local nodes a tile can have; a tile with more than
-// EPT x BLOCK slots goes on in a plain loop (tri3_energy_tiled_kernel's), so every plan shape runs through the one kernel.
-// The register budget is the compiler's: an fp64 log1p, two reciprocals and twice the live values of the linear element do
-// not fit eight waves per SIMD.
+// The model's own QUAD4 plan: one cell per slot, two words per record ({l0 | l1<<10 | l2<<20 | home | skip} in elem_pack,
+// {l3} in elem_pack_hi), uniform node and slot strides.  Phases as in tri3_hyper_kernel and quad4_energy_fast_kernel: row maps
+// and slot records requested up front from the tile index alone (NPT / EPT of them into registers, unguarded clamped loads into
+// the plan's padding), rows gathered to LDS (float rows widened), the four owned-row accumulators cleared, the slot loop
+// accumulating the owned corners with LDS atomics, edges (dead loads, edge2_element unchanged) on boundary tiles, every owned
+// row written exactly once, the tile partials summed in wave order.  NPT x BLOCK covers the 1024 local nodes a tile can have; a
+// tile with more than EPT x BLOCK slots goes on in a plain loop behind the prefetched records, so every plan shape within
+// 64 KiB of LDS runs through the one kernel (the linear QUAD4 kernel refuses such tiles).  The register budget is the
+// compiler's (DESIGN 19 quotes it).
 //
-// Three partials per tile -- energy, min J, number of inverted elements, over HOME elements -- go to a caller-provided
-// workspace work[3][n_tiles]; hyper_finish_kernel (one block) sums the energies in sum_partials_kernel's order and reduces
-// the other two.  The plan's partials banks and bank state are not touched.  The entry point only launches.
+// Three partials per tile -- energy, min J over the Gauss points, number of inverted cells, over HOME cells -- go to a
+// caller-provided workspace work[3][n_tiles]; quad4_hyper_finish_kernel (one block) sums the energies in
+// hyper_finish_thread's order and reduces the other two.  The plan's partials banks and bank state are not touched.  The entry
+// point only launches.
 #include <hip/hip_runtime.h>
 
 #include "hfem_device.h"
-#include "hfem_hyper_dev.h"
 #include "hfem_plan_dev.h"
+#include "hfem_quad4_hyper_dev.h"
 
 namespace hfem {
 
-constexpr int kHyperBlock = 512, kHyperNpt = 2, kHyperEpt = 4, kHyperFinish = 256;
+constexpr int kQHyperBlock = 256, kQHyperNpt = 4, kQHyperEpt = 3, kQHyperFinish = 256;
 
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | acc[4][cap_owned] double | red[3][BLOCK/64]
-template <int BLOCK, int NPT, int EPT, typename V2>
-__global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(
+template <int BLOCK, int NPT, int EPT, typename V2, bool HASB>
+__global__ __launch_bounds__(BLOCK) void quad4_hyper_kernel(
     PlanDev pd, const V2 *__restrict__ x_free, const V2 *__restrict__ x_fixed, const V2 *__restrict__ u_free,
-    const V2 *__restrict__ u_fixed, HyperConsts k, const double4 *__restrict__ T_edge, double4 Tconst,
+    const V2 *__restrict__ u_fixed, Quad4HyperConsts k, const double4 *__restrict__ T_edge, double4 Tconst,
     double *__restrict__ work, int n_tiles, V2 *__restrict__ gx_free, V2 *__restrict__ gu_free, int cap_nodes,
     int cap_owned, int skip_edges) {
     static_assert(NPT * BLOCK >= kMaxLocal, "the row maps of a whole tile (<= 1024 local nodes) are held in registers");
@@ -42,13 +44,18 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(
     const int slot = xcd_tile((int)blockIdx.x, n_tiles);
     // ---- row maps and slot records from the tile index alone (uniform strides; lanes past a stride repeat its last record)
     int2 s[NPT];
-    uint32_t pk[EPT];
+    uint32_t pk[EPT], pk3[EPT];
     const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
     const uint32_t *ep = pd.elem_pack + (size_t)slot * pd.elem_stride;
+    const uint32_t *ep3 = pd.elem_pack_hi + (size_t)slot * pd.elem_stride;
 #pragma unroll
     for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
 #pragma unroll
-    for (int j = 0; j < EPT; ++j) pk[j] = ep[min(tid + j * BLOCK, pd.elem_stride - 1)];
+    for (int j = 0; j < EPT; ++j) {
+        const int i = min(tid + j * BLOCK, pd.elem_stride - 1);
+        pk[j] = ep[i];
+        pk3[j] = ep3[i];
+    }
     const TileDesc d = pd.tiles[slot];
     const int n_owned = d.n_owned;
 #pragma unroll
@@ -70,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(
     for (int j = 0; j < NPT; ++j) gather(tid + j * BLOCK, s[j]);
     __syncthreads();
 
-    // ---- elements (home + halo): registers + LDS only
+    // ---- cells (home + halo): registers + LDS only
     double e_loc = 0.0, j_min = (double)INFINITY, n_inv = 0.0;
     auto add_row = [&](int l, const double2 gx, const double2 gu) {
         if (l < n_owned) {
@@ -78,25 +85,29 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(
             unsafeAtomicAdd(&acc2[l], gu.x); unsafeAtomicAdd(&acc3[l], gu.y);
         }
     };
-    auto element = [&](uint32_t p) {
+    auto element = [&](uint32_t p, uint32_t p3) {
         if (p & kSkipBit) return;
         const int l0 = (int)(p & kLocalMask), l1 = (int)((p >> kLocalBits) & kLocalMask),
-                  l2 = (int)((p >> (2 * kLocalBits)) & kLocalMask);
-        double2 gx[3], gu[3];
+                  l2 = (int)((p >> (2 * kLocalBits)) & kLocalMask), l3 = (int)(p3 & kLocalMask);
+        const double2 Xn[4] = {nd_xy[l0], nd_xy[l1], nd_xy[l2], nd_xy[l3]};
+        const double2 Un[4] = {nd_uv[l0], nd_uv[l1], nd_uv[l2], nd_uv[l3]};
+        double2 gx[4], gu[4];
         double jm1;
-        const double e = neo_hookean_element(nd_xy[l0], nd_xy[l1], nd_xy[l2], nd_uv[l0], nd_uv[l1], nd_uv[l2], k, gx, gu, jm1);
+        bool inv;
+        const double e = quad4_neo_hookean_element<HASB>(Xn, Un, k, gx, gu, jm1, inv);
         if (p & kHomeBit) {
             e_loc += e;
             j_min = fmin(j_min, 1.0 + jm1);
-            n_inv += jm1 > -1.0 ? 0.0 : 1.0;
+            n_inv += inv ? 1.0 : 0.0;
         }
         add_row(l0, gx[0], gu[0]);
         add_row(l1, gx[1], gu[1]);
         add_row(l2, gx[2], gu[2]);
+        add_row(l3, gx[3], gu[3]);
     };
 #pragma unroll
-    for (int j = 0; j < EPT; ++j) element(pk[j]);
-    for (int i = tid + EPT * BLOCK; i < d.n_elem; i += BLOCK) element(ep[i]);
+    for (int j = 0; j < EPT; ++j) element(pk[j], pk3[j]);
+    for (int i = tid + EPT * BLOCK; i < d.n_elem; i += BLOCK) element(ep[i], ep3[i]);
     const int n_edge = skip_edges ? 0 : d.n_edge;
     for (int i = tid; i < n_edge; i += BLOCK) {          // boundary tiles only
         const uint32_t p = pd.edge_pack[d.edge_off + i];
@@ -149,13 +160,14 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_kernel(
     }
 }
 
-// loss = sum of the tile energies in sum_partials_kernel's order (256 adders, shuffle tree, wave sums in wave order);
-// info = {min J, inverted count} (may be NULL)
-__global__ __launch_bounds__(kHyperFinish) void hyper_finish_kernel(const double *__restrict__ work, int n,
-                                                                     double *__restrict__ loss_out, double *__restrict__ info_out) {
-    __shared__ double red_e[kHyperFinish / 64], red_j[kHyperFinish / 64], red_c[kHyperFinish / 64];
+// loss = sum of the tile energies in hyper_finish_thread's order (256 adders, shuffle tree, wave sums in wave order);
+// info = {min J, inverted count} (may be NULL).  tri3_hyper.hip's finishing launch, restated over the shared per-thread part.
+__global__ __launch_bounds__(kQHyperFinish) void quad4_hyper_finish_kernel(const double *__restrict__ work, int n,
+                                                                            double *__restrict__ loss_out,
+                                                                            double *__restrict__ info_out) {
+    __shared__ double red_e[kQHyperFinish / 64], red_j[kQHyperFinish / 64], red_c[kQHyperFinish / 64];
     double e, mj, cnt;
-    hyper_finish_thread(work, n, (int)threadIdx.x, kHyperFinish, e, mj, cnt);
+    hyper_finish_thread(work, n, (int)threadIdx.x, kQHyperFinish, e, mj, cnt);
     mj = wave_min(mj);
     if ((threadIdx.x & 63) == 0) red_j[threadIdx.x >> 6] = mj;
     const double tot = block_sum(e, red_e), tc = block_sum(cnt, red_c);
@@ -163,20 +175,20 @@ __global__ __launch_bounds__(kHyperFinish) void hyper_finish_kernel(const double
         loss_out[0] = tot;
         if (info_out) {
             double tj = red_j[0];
-            for (int w = 1; w < kHyperFinish / 64; ++w) tj = fmin(tj, red_j[w]);
+            for (int w = 1; w < kQHyperFinish / 64; ++w) tj = fmin(tj, red_j[w]);
             info_out[0] = tj;
             info_out[1] = tc;
         }
     }
 }
 
-template <typename V2>
-static void launch_hyper(const hfem_plan *plan, const void *x_free, const void *x_fixed, const void *u_free, const void *u_fixed,
-                         const HyperConsts &k, const double4 *T_edge, double4 tc, double *work, void *gx, void *gu,
-                         int skip_edges, size_t lds, hipStream_t s) {
+template <typename V2, bool HASB>
+static void launch_quad4_hyper(const hfem_plan *plan, const void *x_free, const void *x_fixed, const void *u_free,
+                               const void *u_fixed, const Quad4HyperConsts &k, const double4 *T_edge, double4 tc, double *work,
+                               void *gx, void *gu, int skip_edges, size_t lds, hipStream_t s) {
     const HostPlan &h = plan->host;
     const int nt = (int)h.tiles.size();
-    hipLaunchKernelGGL((tri3_hyper_kernel<kHyperBlock, kHyperNpt, kHyperEpt, V2>), dim3(nt), dim3(kHyperBlock), lds, s,
+    hipLaunchKernelGGL((quad4_hyper_kernel<kQHyperBlock, kQHyperNpt, kQHyperEpt, V2, HASB>), dim3(nt), dim3(kQHyperBlock), lds, s,
                        plan_dev(plan), (const V2 *)x_free, (const V2 *)x_fixed, (const V2 *)u_free, (const V2 *)u_fixed, k,
                        T_edge, tc, work, nt, (V2 *)gx, (V2 *)gu, h.max_nodes, h.max_owned, skip_edges);
 }
@@ -185,39 +197,45 @@ static void launch_hyper(const hfem_plan *plan, const void *x_free, const void *
 
 using namespace hfem;
 
-extern "C" int hfem_tri3_hyper_energy_plan(hfem_plan *plan, int32_t dtype, const void *x_free, const void *x_fixed,
-                                           const void *u_free, const void *u_fixed, const double lame[2], double W,
-                                           const double Bk[6], const double *T_edge, const double Tconst[4],
-                                           double *loss_out, double *info_out, double *work, void *gx_free, void *gu_free,
-                                           int32_t flags, void *stream) {
+extern "C" int hfem_quad4_hyper_energy_plan(hfem_plan *plan, int32_t dtype, const void *x_free, const void *x_fixed,
+                                            const void *u_free, const void *u_fixed, const double lame[2], const double Bq[8],
+                                            const double *T_edge, const double Tconst[4], double *loss_out, double *info_out,
+                                            double *work, void *gx_free, void *gu_free, int32_t flags, void *stream) {
     HFEM_ARG_CHECK(plan && lame && loss_out && work, "null pointer");
     HFEM_ARG_CHECK(dtype == 0 || dtype == 1, "dtype must be 0 (fp64 rows) or 1 (fp32 rows)");
     HFEM_ARG_CHECK(!(flags & ~(HFEM_FLAG_NO_GX | HFEM_FLAG_NO_GU | HFEM_FLAG_NO_EDGES)),
                    "flags: HFEM_FLAG_NO_GX, HFEM_FLAG_NO_GU and HFEM_FLAG_NO_EDGES only");
     HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
-    HFEM_ARG_CHECK(plan->host.npe == 3, "this plan was built for QUAD4: use hfem_quad4_hyper_energy_plan");
-    HFEM_ARG_CHECK(!plan->host.paired, "paired plan: the Neo-Hookean kernel reads one element per slot (plan_elem_order 3)");
+    HFEM_ARG_CHECK(plan->host.npe == 4, "this plan was built for TRI3: use hfem_tri3_hyper_energy_plan");
     HFEM_ARG_CHECK(x_free && u_free, "x_free / u_free must be given");
     HFEM_ARG_CHECK(gx_free || (flags & HFEM_FLAG_NO_GX), "gx_free is NULL without HFEM_FLAG_NO_GX");
     HFEM_ARG_CHECK(gu_free || (flags & HFEM_FLAG_NO_GU), "gu_free is NULL without HFEM_FLAG_NO_GU");
     const HostPlan &h = plan->host;
     const bool skip_edges = (flags & HFEM_FLAG_NO_EDGES) != 0;
     HFEM_ARG_CHECK(h.ned == 0 || skip_edges || T_edge || Tconst, "plan has Neumann edges: need a traction table");
-    const size_t lds = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 32 + 3 * (kHyperBlock / 64) * sizeof(double);
+    HFEM_ARG_CHECK(h.max_nodes <= kQHyperNpt * kQHyperBlock, "tile has more local nodes than the kernel's row-map registers hold");
+    const size_t lds = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 32 + 3 * (kQHyperBlock / 64) * sizeof(double);
     HFEM_ARG_CHECK(lds <= 64 * 1024, "tile needs more than 64 KiB of LDS");
     const int nt = (int)h.tiles.size();
     if (int rc = use_device(plan->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    HyperConsts k;
-    k.lambda = lame[0]; k.mu = lame[1]; k.W = W;
-    for (int i = 0; i < 6; ++i) k.Bk[i] = Bk ? Bk[i] : 0.0;
+    Quad4HyperConsts k;
+    k.lambda = lame[0]; k.mu = lame[1];
+    bool hasb = false;
+    for (int q = 0; q < 4; ++q) {
+        k.b[q] = Bq ? make_double2(Bq[2 * q], Bq[2 * q + 1]) : make_double2(0.0, 0.0);
+        hasb = hasb || k.b[q].x != 0.0 || k.b[q].y != 0.0;
+    }
     const double4 tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
     if (nt > 0) {
         void *gx = (flags & HFEM_FLAG_NO_GX) ? nullptr : gx_free, *gu = (flags & HFEM_FLAG_NO_GU) ? nullptr : gu_free;
-        if (dtype == 1) launch_hyper<float2>(plan, x_free, x_fixed, u_free, u_fixed, k, (const double4 *)T_edge, tc, work, gx, gu, skip_edges, lds, s);
-        else launch_hyper<double2>(plan, x_free, x_fixed, u_free, u_fixed, k, (const double4 *)T_edge, tc, work, gx, gu, skip_edges, lds, s);
-        if (int rc = launch_status("hfem_tri3_hyper_energy_plan")) return rc;
+#define HFEM_QHYPER(V, B) \
+    launch_quad4_hyper<V, B>(plan, x_free, x_fixed, u_free, u_fixed, k, (const double4 *)T_edge, tc, work, gx, gu, skip_edges, lds, s)
+        if (dtype == 1) { if (hasb) HFEM_QHYPER(float2, true); else HFEM_QHYPER(float2, false); }
+        else { if (hasb) HFEM_QHYPER(double2, true); else HFEM_QHYPER(double2, false); }
+#undef HFEM_QHYPER
+        if (int rc = launch_status("hfem_quad4_hyper_energy_plan")) return rc;
     }
-    hipLaunchKernelGGL(hyper_finish_kernel, dim3(1), dim3(kHyperFinish), 0, s, work, nt, loss_out, info_out);
-    return launch_status("hfem_tri3_hyper_energy_plan(finish)");
+    hipLaunchKernelGGL(quad4_hyper_finish_kernel, dim3(1), dim3(kQHyperFinish), 0, s, work, nt, loss_out, info_out);
+    return launch_status("hfem_quad4_hyper_energy_plan(finish)");
 }

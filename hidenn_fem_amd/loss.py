@@ -276,7 +276,7 @@ class NeoHookeanLoss2D(EnergyLoss2D):
     the last launch wrote, ``{min J, number of elements with J <= 0}``: the same tensor on every call, no host sync.
 
     fp32 models: float rows widened on load, fp64 arithmetic, one rounding on store.  Not available: ``deterministic=True``,
-    ``arithmetic="fp32"``, QUAD4 models, ``FrozenMeshSolver`` / ``StressRecovery`` (they are linear)."""
+    ``arithmetic="fp32"``, QUAD4 models (they take ``Quad4NeoHookeanLoss2D``), ``FrozenMeshSolver`` / ``StressRecovery`` (they are linear)."""
 
     def __init__(self, E: float = 10e9, nu: float = 0.3, length: float = 1.0, height: float = 1.0,
                  gauss_order: int = 4, gauss_order_1d: int = 2, device: Optional[torch.device] = None,
@@ -306,7 +306,7 @@ class NeoHookeanLoss2D(EnergyLoss2D):
     def _launch_state(self, model):
         """(one-element-per-slot plan, info, workspace) for a launch on the model's device."""
         if getattr(model, "nodes_per_element", 3) != 3:
-            raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only")
+            raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only (QUAD4 models: Quad4NeoHookeanLoss2D)")
         from .plan import model_plan
         plan = model_plan(model, self.tile_elems, paired=False)
         dev = model.node_coords_free.device
@@ -324,7 +324,7 @@ class NeoHookeanLoss2D(EnergyLoss2D):
                                            Tconst, flags, info, work)
 
     def _quad4(self, model, b_force, t_force):
-        raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only")
+        raise NotImplementedError("NeoHookeanLoss2D: TRI3 models only (QUAD4 models: Quad4NeoHookeanLoss2D)")
 
     def domain_energy(self, model, b_force: Optional[Callable] = None) -> torch.Tensor:
         """Strain energy minus body work (the edges off), fused."""
@@ -359,6 +359,86 @@ class NeoHookeanLoss2D(EnergyLoss2D):
             uf.data_ptr(), ufix.data_ptr() if ufix.numel() else None, lame, self._W, Bk, None, Tc, loss.data_ptr(),
             info.data_ptr(), work.data_ptr(), xf.grad.data_ptr(), uf.grad.data_ptr(), 0 if model.N_edges else HFEM_FLAG_NO_EDGES,
             _lib.stream_ptr(xf.device)), "hfem_tri3_hyper_energy_plan")
+        return loss
+
+
+class Quad4NeoHookeanLoss2D(NeoHookeanLoss2D):
+    """The compressible Neo-Hookean total potential of a QUAD4 model: ``NeoHookeanLoss2D``'s constructor, material
+    (``lame``), ``info`` and call contracts -- ``loss_fn(model, b_force=None, t_force=None)``, ``domain_energy``,
+    ``value_and_grad_`` --, on the model's own QUAD4 tile plan.  One launch of ``csrc/quad4_hyper.hip`` (+ a one-block reduction).
+
+    2x2 Gauss points (``gauss_order`` is a triangle-rule setting and does not apply to cells, as in ``EnergyLoss2D``); at each,
+    ``H = G J^-1`` is the true displacement gradient and ``psi`` the cancellation-free form of the TRI3 loss.  The body force
+    is tabulated at the reference Gauss points, tractions as ``EnergyLoss2D`` does for QUAD4 models (constant table, per-edge
+    table, or autograd through ``edge_energy`` when a traction callable is evaluated at points that move); both are dead loads.
+
+    A cell is inverted when ``det F <= 0`` (or NaN) at any of its four points: it contributes ``+inf`` to the loss and zero to
+    both gradients and is counted once; ``info = {min det F over all points, number of inverted cells}``.
+
+    Not available: ``deterministic=True``, ``arithmetic="fp32"``, TRI3 models (``NeoHookeanLoss2D``), the linear tools
+    (``Quad4FrozenMeshSolver``, ``assemble_stiffness``, ``StressRecovery``) and ``NewtonKrylovSolver`` (no QUAD4 tangent yet)."""
+
+    def _launch_state(self, model):
+        """(the model's QUAD4 plan, info, workspace) for a launch on the model's device."""
+        if getattr(model, "nodes_per_element", 3) != 4:
+            raise NotImplementedError("Quad4NeoHookeanLoss2D: QUAD4 models only (TRI3 models: NeoHookeanLoss2D)")
+        plan = model.tile_plan(self.tile_elems)
+        dev = model.node_coords_free.device
+        if self._info is None or self._info.device != dev:
+            self._info = torch.zeros(2, dtype=torch.float64, device=dev)
+        hit = self._work.get(id(plan))
+        if hit is None or hit[0] is not plan or hit[1].device != dev:
+            hit = self._work[id(plan)] = (plan, torch.empty(3 * max(plan.n_tiles, 1), dtype=torch.float64, device=dev))
+        return plan, self._info, hit[1]
+
+    def _fused(self, model, b_force, T_edge, Tconst, flags, tile_range=(0, -1)):
+        plan, info, work = self._launch_state(model)
+        return ops.Quad4HyperEnergyFn.apply(model.node_coords_free, model.u_free, model.node_coords_fixed.to(model.dtype),
+                                            model.u_fixed_rows(), plan, self.lame, self._quad4_body(b_force), T_edge, Tconst,
+                                            flags, info, work)
+
+    def _quad4(self, model, b_force, t_force):
+        if model.neumann_edges is None or model.N_edges == 0:
+            return self._fused(model, b_force, None, [0.0] * 4, HFEM_FLAG_NO_EDGES)
+        if t_force is not None and model.node_coords_free.requires_grad and self._edge_nodes_free(model):
+            return self._fused(model, b_force, None, [0.0] * 4, HFEM_FLAG_NO_EDGES) - self.edge_energy(model, t_force)
+        T_edge, Tconst = self._traction(model, t_force)
+        return self._fused(model, b_force, T_edge, Tconst, 0)
+
+    def __call__(self, model, b_force=None, t_force=None) -> torch.Tensor:
+        """Total potential = domain - edge, one fused launch."""
+        self._launch_state(model)                    # refuses a TRI3 model before anything is tabulated
+        return self._quad4(model, b_force, t_force)
+
+    def value_and_grad_(self, model) -> torch.Tensor:
+        """As ``NeoHookeanLoss2D.value_and_grad_``: ONE launch writes both gradients straight into ``.grad`` (overwritten) and
+        returns the loss (0-d, fp64; the same tensor every call).  Default forces; fp64 or fp32 rows.  Only launches:
+        capturable into a graph."""
+        import ctypes as C
+        import weakref
+        from . import _lib
+        plan, info, work = self._launch_state(model)
+        xf, uf = model.node_coords_free, model.u_free
+        if xf.dtype != uf.dtype or xf.dtype not in (torch.float64, torch.float32):
+            raise RuntimeError("value_and_grad_: parameters must both be fp64 or both fp32")
+        for p in (xf, uf):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        cache = getattr(self, "_direct_cache", None)
+        key = (xf.dtype, xf.device)
+        if cache is None or cache[0][0]() is not model or cache[0][1:] != key:
+            _, Tconst = self._traction(model, None)
+            dv = lambda v: (C.c_double * len(v))(*v)
+            cache = self._direct_cache = ((weakref.ref(model),) + key, dv(self.lame), dv(Tconst),
+                                          torch.zeros((), dtype=torch.float64, device=xf.device))
+        _, lame, Tc, loss = cache
+        xfix = model.node_coords_fixed.to(device=xf.device, dtype=xf.dtype).contiguous()
+        ufix = model.u_fixed_rows().to(device=xf.device, dtype=xf.dtype).contiguous()
+        _lib.check(_lib.lib().hfem_quad4_hyper_energy_plan(
+            plan.handle, 1 if xf.dtype == torch.float32 else 0, xf.data_ptr(), xfix.data_ptr() if xfix.numel() else None,
+            uf.data_ptr(), ufix.data_ptr() if ufix.numel() else None, lame, None, None, Tc, loss.data_ptr(),
+            info.data_ptr(), work.data_ptr(), xf.grad.data_ptr(), uf.grad.data_ptr(), 0 if model.N_edges else HFEM_FLAG_NO_EDGES,
+            _lib.stream_ptr(xf.device)), "hfem_quad4_hyper_energy_plan")
         return loss
 
 

@@ -168,6 +168,42 @@ class Tri3HyperEnergyFn(torch.autograd.Function):
         return (out_x, out_u) + (None,) * 11
 
 
+class Quad4HyperEnergyFn(torch.autograd.Function):
+    """The same potential of a QUAD4 model (csrc/quad4_hyper.hip), the mirror of ``Tri3HyperEnergyFn``: ``plan`` is the model's
+    QUAD4 tile plan, ``Bq`` the body force at the 2x2 Gauss points (8 numbers) or ``None``; ``info`` / ``work`` as there."""
+
+    @staticmethod
+    def forward(ctx, x_free, u_free, x_fixed, u_fixed, plan, lame, Bq, T_edge, Tconst, flags, info, work):
+        dev = x_free.device
+        need_gx = ctx.needs_input_grad[0] and not (flags & 1)
+        need_gu = ctx.needs_input_grad[1] and not (flags & 2)
+        fl = (flags & ~3) | (0 if need_gx else 1) | (0 if need_gu else 2)
+        f32 = x_free.dtype == F32 and u_free.dtype == F32
+        dt = F32 if f32 else F64
+        xf, uf = _as(x_free, "node_coords_free", dt), _as(u_free, "u_free", dt)
+        xfix, ufix = _as(x_fixed, "node_coords_fixed", dt), _as(u_fixed, "u_fixed", dt)
+        loss = torch.empty((), dtype=F64, device=dev)
+        gx = torch.empty_like(xf) if need_gx else None
+        gu = torch.empty_like(uf) if need_gu else None
+        te = _f64(T_edge, "T_edge")
+        check(_lib.lib().hfem_quad4_hyper_energy_plan(
+            plan.handle, 1 if f32 else 0, ptr(xf), ptr(xfix) if xfix is not None and xfix.numel() else None, ptr(uf),
+            ptr(ufix) if ufix is not None and ufix.numel() else None, _dvec(lame), None if Bq is None else _dvec(Bq), ptr(te),
+            None if Tconst is None else _dvec(Tconst), ptr(loss), ptr(info), ptr(work), ptr(gx), ptr(gu), int(fl),
+            stream_ptr(dev)), "hfem_quad4_hyper_energy_plan")
+        ctx.unit = (gx, gu)
+        ctx.dtypes = (x_free.dtype, u_free.dtype)
+        return loss.to(x_free.dtype) if x_free.dtype != F64 else loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gx, gu = ctx.unit
+        out_x = None if gx is None else (gx * g.to(gx.dtype)).to(ctx.dtypes[0])
+        out_u = None if gu is None else (gu * g.to(gu.dtype)).to(ctx.dtypes[1])
+        return (out_x, out_u) + (None,) * 10
+
+
 # ---------------------------------------------------------------- free/fixed row assembly
 class AssembleRowsFn(torch.autograd.Function):
     """full[idx_free] = free ; full[idx_fixed] = fixed   (reference src/models.py:292-305,

@@ -476,6 +476,22 @@ int hfem_tri3_hyper_energy_plan(hfem_plan *plan, int32_t dtype, const void *x_fr
                                 const double Bk[6], const double *T_edge, const double Tconst[4], double *loss_out,
                                 double *info_out, double *work, void *gx_free, void *gu_free, int32_t flags, void *stream);
 
+/* ------------------------------------------------------------------ Neo-Hookean finite-strain energy (QUAD4)
+ * The same potential on a QUAD4 plan (one cell per slot, the plan every QUAD4 entry point uses), 2x2 Gauss points
+ * (+-1/sqrt(3), weights 1, order (-,-) (+,-) (-,+) (+,+)).  Per point, with J = sum_k X_k (x) dN_k/dxi and
+ * G = sum_k U_k (x) dN_k/dxi:  H = G J^-1 (the true displacement gradient, always), j = tr H + det H, L = log1p(j),
+ * psi = mu (tr H + H:H / 2 - L) + lambda L^2 / 2, e = sum_q |det J_q| (psi_q - b_q . u_h(xi_q)); Bq[8] (HOST, may be NULL = 0)
+ * is the body force at the four points (reference coordinates), lame[2], T_edge / Tconst, dtype, loss_out, info_out, work
+ * (3 * n_tiles doubles), gx_free / gu_free and flags exactly as hfem_tri3_hyper_energy_plan.  A cell with j_q <= -1 (or NaN)
+ * at any of its points contributes +inf to the loss and ZERO to both gradients and is counted once; info_out[0] is the minimum
+ * of 1 + j_q over all points.  Tiles with more than 768 slots run (a plain loop behind the prefetched records); a TRI3 or
+ * host-only plan, a missing pointer, any other flag, or a tile that needs more than 64 KiB of LDS (32 bytes per local node +
+ * 32 per owned row + 96) is an argument error.  Launch-only (capturable).                                               */
+int hfem_quad4_hyper_energy_plan(hfem_plan *plan, int32_t dtype, const void *x_free, const void *x_fixed,
+                                 const void *u_free, const void *u_fixed, const double lame[2], const double Bq[8],
+                                 const double *T_edge, const double Tconst[4], double *loss_out, double *info_out,
+                                 double *work, void *gx_free, void *gu_free, int32_t flags, void *stream);
+
 /* ------------------------------------------------------------------ multi-GPU interface exchange
  * Owner-sharded mode (no reference counterpart): one all_gather per step of a fixed-size
  * payload per rank, in double2 units:  [x rows | u rows | padding][loss partial, 0].
