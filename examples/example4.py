@@ -144,8 +144,8 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     instead of ``FusedLBFGS``; the line then also shows the Newton and CG iterations.  An increment whose Newton solve does
     not converge is taken back and halved like an inverted one.
     ``quad=True`` (``--quad``): the same ramp on the plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
-    (``structured_quad_mesh``), with ``Quad4NeoHookeanLoss2D``; ``FusedLBFGS`` only -- there is no QUAD4 tangent yet, so
-    ``newton=True`` raises ``NotImplementedError``."""
+    (``structured_quad_mesh``), with ``Quad4NeoHookeanLoss2D``; with ``newton=True`` every increment is solved by
+    ``Quad4NewtonKrylovSolver``."""
     from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
     from hidenn_fem_amd.solve import solve_displacement_
@@ -153,9 +153,6 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     length, height = 2.0, 1.0
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
-    if quad and newton:
-        raise NotImplementedError("example 4: --neo-hookean --quad runs with FusedLBFGS only (NewtonKrylovSolver needs the "
-                                  "tangent, which exists for TRI3 models only); drop --newton or --quad")
     if quad:
         from hidenn_fem_amd.mesh import structured_quad_mesh
         nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
@@ -189,8 +186,9 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
         return value.item(), float(loss_fn.info[0]), int(loss_fn.info[1]), model.u_free.grad.abs().max().item()
 
     def equilibrium(scale):
-        from hidenn_fem_amd.newton import NewtonKrylovSolver
-        info = NewtonKrylovSolver(model, loss_fn, t_force=traction(scale), precond=precond).solve()
+        from hidenn_fem_amd.newton import NewtonKrylovSolver, Quad4NewtonKrylovSolver
+        solver = Quad4NewtonKrylovSolver if quad else NewtonKrylovSolver
+        info = solver(model, loss_fn, t_force=traction(scale), precond=precond).solve()
         ginf = float("inf") if not info.converged else info.grad_norm       # an unconverged increment is taken back
         return info.energy, info.min_J, 0 if info.converged else 1, ginf, info
 
@@ -291,12 +289,10 @@ if __name__ == "__main__":
                     help="the plate at finite strain: Neo-Hookean material, load ramped in steps, FusedLBFGS on u_free (fp64)")
     ap.add_argument("--load-steps", type=int, default=8, help="load increments of --neo-hookean")
     ap.add_argument("--newton", action="store_true",
-                    help="with --neo-hookean: solve every load increment with NewtonKrylovSolver instead of FusedLBFGS")
+                    help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
+                         "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
     a = ap.parse_args()
     if a.neo_hookean:
-        if a.quad and a.newton:
-            raise SystemExit("example 4: --neo-hookean --quad minimises with FusedLBFGS; --newton needs the Neo-Hookean tangent, "
-                             "which exists for TRI3 models only -- drop --newton or --quad")
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,

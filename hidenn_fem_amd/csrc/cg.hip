@@ -1,9 +1,9 @@
 // PCG driver of the frozen-mesh displacement solve, gfx950 (MI355X) (hidenn_fem_amd/solve.py): everything above the element
 // level -- the vector kernels, the status record, the halt logic and the hfem_cg_* entry points.  Nothing here knows the
 // element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
-// (the model's own QUAD4 plan) or tri3_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point, one-element-per-slot
-// TRI3 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in cg_apply and cg_diag; the residual r = -dE/du comes from
-// the graded energy kernel, called by the host once per solve.
+// (the model's own QUAD4 plan), tri3_hyper_cg.hip or quad4_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point,
+// on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
+// cg_apply and cg_diag; the residual r = -dE/du comes from the graded energy kernel, called by the host once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
 //                   order, forms beta, and applies the stopping test (START: r = -g0, z = D^-1 r, |f|).
 //   cg_rz_kernel    rho = r^T z in block order, then beta (precond = AMG only).
@@ -162,7 +162,8 @@ struct hfem_cg {
     int64_t n_u = 0;
     int n_tiles = 0, block = 256, vec_blocks = 1;
     bool phys = false, quad = false;   // quad: a QUAD4 plan (one element per slot; kernels of quad4_cg.hip)
-    bool hyper = false;                // the Neo-Hookean tangent (unpaired TRI3 plan; kernels of tri3_hyper_cg.hip)
+    bool hyper = false;                // the Neo-Hookean tangent (unpaired TRI3 plan; kernels of tri3_hyper_cg.hip); with quad:
+                                       // on the QUAD4 plan (kernels of quad4_hyper_cg.hip)
     size_t lds_apply = 0, lds_diag = 0;
     // device memory, one allocation: p[2], r, z, q (double2 rows), dinv (3 doubles per row), tile partials, vector partials,
     // status record, tickets
@@ -170,6 +171,7 @@ struct hfem_cg {
     double2 *p[2] = {nullptr, nullptr}, *r = nullptr, *z = nullptr, *q = nullptr;
     double *dinv = nullptr, *tile_part = nullptr, *vec_part = nullptr, *st = nullptr;
     double *work = nullptr;            // hyper: the diag launch's tile partials [3][n_tiles]
+    double *cq = nullptr;              // hyper && quad: c = mu - lambda L of the last linearisation, [n_tiles][4][elem_stride]
     unsigned *tickets = nullptr;       // [0] apply, [1] vector kernels, [2] standalone apply
     double *host = nullptr;            // pinned mirror of the status record
     // bound by hfem_cg_setup
@@ -186,7 +188,7 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     hfem::CgElemArgs A;
     A.plan = c->plan; A.n_tiles = c->n_tiles; A.block = c->block; A.phys = c->phys; A.x_free = c->x_free; A.x_fixed = c->x_fixed;
     A.k = c->k; A.lds = lds; A.s = s;
-    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk;
+    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq;
     return A;
 }
 
@@ -194,14 +196,16 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
 void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, double *st, double *host, double *pq_out,
               hipStream_t s) {
     const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
-    if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
 
 void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStream_t s) {
     const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
-    if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }
@@ -302,7 +306,9 @@ static int cg_alloc(std::unique_ptr<hfem_cg> &c, hfem_cg **out) {
     const size_t off_vp = off_tp + 4 * (size_t)std::max(c->n_tiles, 1) * 8;   // tile partials, then hyper's [3][n_tiles]
     const size_t off_st = off_vp + 3 * (size_t)hfem::kVecMaxBlocks * 8;
     const size_t off_tk = off_st + hfem::kStatusN * 8;
-    const size_t bytes = off_tk + 64;
+    const size_t off_cq = off_tk + 64;                                // QUAD4 tangent: four doubles per slot of the plan
+    const size_t n_cq = c->hyper && c->quad ? 4 * (size_t)std::max(c->n_tiles, 1) * (size_t)c->plan->host.elem_stride : 0;
+    const size_t bytes = off_cq + n_cq * 8;
     HFEM_HIP_CHECK(hipMalloc((void **)&c->mem, bytes));
     if (hipHostMalloc((void **)&c->host, hfem::kStatusN * sizeof(double)) != hipSuccess) {
         (void)hipFree(c->mem);
@@ -315,6 +321,7 @@ static int cg_alloc(std::unique_ptr<hfem_cg> &c, hfem_cg **out) {
     c->dinv = (double *)(c->mem + off_d); c->tile_part = (double *)(c->mem + off_tp); c->vec_part = (double *)(c->mem + off_vp);
     c->st = (double *)(c->mem + off_st); c->tickets = (unsigned *)(c->mem + off_tk);
     c->work = c->tile_part + std::max(c->n_tiles, 1);
+    c->cq = n_cq ? (double *)(c->mem + off_cq) : nullptr;
     const hipError_t e = hipMemset(c->mem, 0, bytes);                 // tickets zero, p buffers zero (0 * p_old is 0)
     if (e != hipSuccess) {
         (void)hipFree(c->mem); (void)hipHostFree(c->host);
@@ -325,23 +332,28 @@ static int cg_alloc(std::unique_ptr<hfem_cg> &c, hfem_cg **out) {
     return 0;
 }
 
-// The Neo-Hookean tangent: the plan hfem_tri3_hyper_energy_plan takes (TRI3, one element per slot), tri3_hyper_cg.hip's LDS
+// The Neo-Hookean tangent: the plan hfem_tri3_hyper_energy_plan takes (TRI3, one element per slot), tri3_hyper_cg.hip's LDS;
+// or, by h.npe as in hfem_cg_create, the plan hfem_quad4_hyper_energy_plan takes (the model's own QUAD4 plan),
+// quad4_hyper_cg.hip's LDS
 extern "C" int hfem_cg_create_hyper(hfem_plan *plan, int64_t n_u, hfem_cg **out) {
     HFEM_ARG_CHECK(plan && out, "null pointer");
     *out = nullptr;
     HFEM_ARG_CHECK(plan->device >= 0, "host-only plan (created with device < 0) cannot launch");
     const hfem::HostPlan &h = plan->host;
-    HFEM_ARG_CHECK(h.npe == 3, "this plan was built for QUAD4: the Neo-Hookean tangent exists for TRI3 only");
+    const bool quad = h.npe == 4;
+    HFEM_ARG_CHECK(quad || h.npe == 3, "the Neo-Hookean tangent exists for TRI3 and QUAD4 plans");
+    HFEM_ARG_CHECK(!quad || plan->d_elem_pack_hi, "QUAD4 plan without its fourth-corner records");
     HFEM_ARG_CHECK(!h.paired, "paired plan: the Neo-Hookean tangent kernels read one element per slot (plan_elem_order 3)");
     HFEM_ARG_CHECK(h.max_nodes <= hfem::kMaxLocal && h.max_owned <= h.max_nodes, "tile shape outside the tangent kernels' instance");
-    const size_t lds_apply = (size_t)h.max_nodes * 48 + (size_t)h.max_owned * 16 + (512 / 64 + 2) * 8;
-    const size_t lds_diag = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 24 + 2 * (512 / 64) * 8;
+    const int block = quad ? hfem::kQuad4HyperCgBlock : 512;
+    const size_t lds_apply = (size_t)h.max_nodes * 48 + (size_t)h.max_owned * 16 + (block / 64 + 2) * 8;
+    const size_t lds_diag = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 24 + 2 * (block / 64) * 8;
     HFEM_ARG_CHECK(lds_apply <= 64 * 1024 && lds_diag <= 64 * 1024, "tile needs more than 64 KiB of LDS");
     HFEM_ARG_CHECK(n_u >= plan_u_rows(h), "n_u is smaller than the plan's free u rows");
     HFEM_ARG_CHECK(n_u < ((int64_t)1 << 31), "n_u too large");
     std::unique_ptr<hfem_cg> c(new hfem_cg);
-    c->plan = plan; c->device = plan->device; c->n_u = n_u; c->phys = true; c->hyper = true;
-    c->n_tiles = (int)h.tiles.size(); c->block = 512;
+    c->plan = plan; c->device = plan->device; c->n_u = n_u; c->phys = true; c->hyper = true; c->quad = quad;
+    c->n_tiles = (int)h.tiles.size(); c->block = block;
     c->vec_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(hfem::kVecMaxBlocks, (n_u + hfem::kVecBlock - 1) / hfem::kVecBlock));
     c->lds_apply = lds_apply; c->lds_diag = lds_diag;
     return cg_alloc(c, out);
@@ -395,7 +407,7 @@ extern "C" int hfem_cg_setup_hyper(hfem_cg *c, const double *x_free, const doubl
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->u_lin = (const double2 *)u_lin_free; c->u_fixed = (const double2 *)u_fixed;
     c->hk = hfem::HyperConsts{};
-    c->hk.lambda = lame[0]; c->hk.mu = lame[1]; c->hk.W = W;
+    c->hk.lambda = lame[0]; c->hk.mu = lame[1]; c->hk.W = c->quad ? 1.0 : W;   // QUAD4: the 2x2 rule's weights are 1, W is not read
     cg_diag(c, diag_out, precond, info_out, s);
     if (int rc = hfem::launch_status("hfem_cg_setup_hyper")) return rc;
     c->ready = true;

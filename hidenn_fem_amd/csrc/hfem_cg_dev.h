@@ -1,6 +1,6 @@
 // Device-side pieces the frozen-mesh solve's kernels share.  For every kernel with a last workgroup (cg.hip, tri3_cg.hip,
-// quad4_cg.hip, tri3_hyper_cg.hip): the status publication, the hand-off and the fixed-order partial sum.  For the element
-// kernels (apply and block diagonal of tri3_cg.hip, quad4_cg.hip and tri3_hyper_cg.hip) the phases that do not depend on
+// quad4_cg.hip, tri3_hyper_cg.hip, quad4_hyper_cg.hip): the status publication, the hand-off and the fixed-order partial sum.
+// For the element kernels (apply and block diagonal of tri3_cg.hip, quad4_cg.hip, tri3_hyper_cg.hip and quad4_hyper_cg.hip) the phases that do not depend on
 // the element: the iteration state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
 // block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
 // element, 3 or 4 corners, and the x row code.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
@@ -190,9 +190,12 @@ struct CgElemArgs {
     Tri3Consts k{};
     size_t lds = 0;
     hipStream_t s = nullptr;
-    // the Neo-Hookean tangent (tri3_hyper_cg.hip): the linearisation point's rows and the material
+    // the Neo-Hookean tangent (tri3_hyper_cg.hip, quad4_hyper_cg.hip): the linearisation point's rows and the material
     const double2 *u_lin_free = nullptr, *u_fixed = nullptr;
     HyperConsts hk{};
+    // quad4_hyper_cg.hip: c = mu - lambda L per slot and Gauss point, [n_tiles][4][elem_stride]; the diag launch of a
+    // linearisation writes it, its apply launches read it instead of calling log1p
+    double *cq = nullptr;
 };
 // q = K p (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
@@ -207,5 +210,13 @@ void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int p
 void launch_tri3_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
                                 double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_tri3_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
+// info[2] = {min J, inverted count} from a diag launch's tile partials work[3][n] (one block; tri3_hyper_cg.hip)
+void launch_hyper_info(const double *work, int n, double *info, hipStream_t s);
+// The same two on the QUAD4 Neo-Hookean tangent (quad4_hyper_cg.hip, the model's own QUAD4 plan; A.hk carries lambda and mu,
+// W is not read).  Threads per tile of both kernels: the driver sizes their LDS with it.
+constexpr int kQuad4HyperCgBlock = 256;
+void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                                 double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
 
 }  // namespace hfem

@@ -203,7 +203,11 @@ void launch_tri3_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, 
         hipLaunchKernelGGL((tri3_hyper_cg_diag_kernel<kBlock, kNpt>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s, plan_dev(A.plan),
                            A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, A.hk, diag, dinv, precond, work, h.max_nodes,
                            h.max_owned);
-    if (info) hipLaunchKernelGGL(hyper_info_kernel, dim3(1), dim3(kInfoBlock), 0, A.s, work, A.n_tiles, info);
+    if (info) launch_hyper_info(work, A.n_tiles, info, A.s);
+}
+
+void launch_hyper_info(const double *work, int n, double *info, hipStream_t s) {
+    hipLaunchKernelGGL(hyper_info_kernel, dim3(1), dim3(kInfoBlock), 0, s, work, n, info);
 }
 
 }  // namespace hfem

@@ -375,8 +375,9 @@ class Quad4NeoHookeanLoss2D(NeoHookeanLoss2D):
     A cell is inverted when ``det F <= 0`` (or NaN) at any of its four points: it contributes ``+inf`` to the loss and zero to
     both gradients and is counted once; ``info = {min det F over all points, number of inverted cells}``.
 
+    Its equilibrium over ``u_free``: ``hidenn_fem_amd.newton.Quad4NewtonKrylovSolver`` / ``quad4_newton_solve_``.
     Not available: ``deterministic=True``, ``arithmetic="fp32"``, TRI3 models (``NeoHookeanLoss2D``), the linear tools
-    (``Quad4FrozenMeshSolver``, ``assemble_stiffness``, ``StressRecovery``) and ``NewtonKrylovSolver`` (no QUAD4 tangent yet)."""
+    (``Quad4FrozenMeshSolver``, ``assemble_stiffness``, ``StressRecovery``) and the TRI3 class ``NewtonKrylovSolver``."""
 
     def _launch_state(self, model):
         """(the model's QUAD4 plan, info, workspace) for a launch on the model's device."""
@@ -448,7 +449,8 @@ def require_linear(loss_fn, who: str):
     if isinstance(loss_fn, NeoHookeanLoss2D):
         raise NotImplementedError(f"{who}: small-strain linear elasticity only; a NeoHookeanLoss2D would be linearised "
                                   "silently -- its equilibrium is hidenn_fem_amd.newton.NewtonKrylovSolver / newton_solve_ "
-                                  "(Newton-Krylov on the tangent); or pass an EnergyLoss2D")
+                                  "(Newton-Krylov on the tangent; QUAD4 models: Quad4NewtonKrylovSolver / quad4_newton_solve_); "
+                                  "or pass an EnergyLoss2D")
 
 
 # ---------------------------------------------------------------- inline losses of examples 1-3

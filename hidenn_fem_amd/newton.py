@@ -1,10 +1,11 @@
-"""Newton-Krylov equilibrium solve of a Neo-Hookean TRI3 model at its CURRENT coordinates.
+"""Newton-Krylov equilibrium solve of a Neo-Hookean TRI3 or QUAD4 model at its CURRENT coordinates.
 
 ``NeoHookeanLoss2D`` is not quadratic in the displacements, so its minimum over ``u_free`` is a nonlinear system
 ``g(u) = dPi/du_free = 0``.  ``NewtonKrylovSolver`` solves it by inexact Newton: every iteration solves ``K_T(u) d = -g(u)`` on
 the tangent ``K_T = d2Pi/du2`` by matrix-free preconditioned CG on the GPU -- the PCG driver of the frozen-mesh solve
 (``csrc/cg.hip``: vector kernels, device-side scalars, halt, graph replay) with the tangent as its third element kind
-(``csrc/tri3_hyper_cg.hip``) -- to the relative tolerance ``eta_k`` of Eisenstat-Walker choice 2, then backtracks on the energy.
+(``csrc/tri3_hyper_cg.hip``; ``Quad4NewtonKrylovSolver``: the fourth, ``csrc/quad4_hyper_cg.hip``) -- to the relative
+tolerance ``eta_k`` of Eisenstat-Walker choice 2, then backtracks on the energy.
 Residual and energy come from ONE launch of the Neo-Hookean energy kernel on the solver's buffers, on the plan the tangent
 kernels run on; the launch that evaluates an accepted trial point also delivers the next iteration's gradient.
 
@@ -26,7 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .loss import NeoHookeanLoss2D
+from .loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
 from .solve import (F64, HFEM_FLAG_NO_EDGES, HFEM_FLAG_NO_GX, ST_HALTED, ST_ITER, ST_REASON, _AmgDevice, _Frozen, _REASONS,
                     amg_host)
 
@@ -54,9 +55,10 @@ class NewtonInfo:
     history: List[dict] = field(default_factory=list)
 
 
-class NewtonKrylovSolver:
-    """Inexact Newton with truncated PCG for ``model.u_free`` under a ``NeoHookeanLoss2D`` (see the module docstring); TRI3
-    models only, anything else raises ``NotImplementedError``.
+class _NewtonSolverBase:
+    """What ``NewtonKrylovSolver`` (TRI3) and ``Quad4NewtonKrylovSolver`` share: everything but the model/loss check, the plan,
+    the body-force table and the energy launch (``_check_model``, ``_make_plan``, ``_body``, ``_energy``) -- the Newton loop,
+    refresh, graph replay, the preconditioners, ``apply``, ``info`` and the meaning of every keyword.
 
     ``b_force`` / ``t_force``: the callables ``loss_fn(model, b_force, t_force)`` would take (default forces when None),
     tabulated as the loss does and frozen at the current coordinates.  ``precond``: ``"block_jacobi"`` (the tangent's 2x2
@@ -81,11 +83,7 @@ class NewtonKrylovSolver:
                  precond: str = "block_jacobi", rtol: float = 1e-8, atol: float = 0.0, max_newton: int = 50,
                  cg_max_iter: Optional[int] = None, iters_per_graph: int = 16, eta_max: float = 0.1, armijo: float = 1e-4,
                  max_backtracks: int = 30):
-        if not isinstance(loss_fn, NeoHookeanLoss2D):
-            raise NotImplementedError("NewtonKrylovSolver: NeoHookeanLoss2D only (an EnergyLoss2D is quadratic in u_free: "
-                                      "FrozenMeshSolver / solve_displacement_ solve it in one linear solve)")
-        if getattr(model, "nodes_per_element", 3) != 3:
-            raise NotImplementedError("NewtonKrylovSolver: TRI3 models only (the Neo-Hookean energy exists for TRI3)")
+        self._check_model(model, loss_fn)
         if precond not in ("block_jacobi", "none", "amg"):
             raise ValueError("precond must be 'block_jacobi', 'none' or 'amg'")
         if precond == "amg" and int(model._idx_udir.shape[0]) == 0:
@@ -98,13 +96,12 @@ class NewtonKrylovSolver:
             raise ValueError("eta_max must be in (0, 1)")
         for name, t in (("node_coords_free", model.node_coords_free), ("u_free", model.u_free)):
             _lib.require_gpu_tensor(t, name, dtype=None)
-        from .plan import model_plan
         self.model, self.loss_fn = model, loss_fn
         self.b_force, self.t_force = b_force, t_force
         self.precond, self.rtol, self.atol = precond, float(rtol), float(atol)
         self.max_newton, self.iters_per_graph = int(max_newton), int(iters_per_graph)
         self.eta_max, self.armijo, self.max_backtracks = float(eta_max), float(armijo), int(max_backtracks)
-        self.plan = model_plan(model, loss_fn.tile_elems, paired=False)     # the energy launch's plan: shared row maps
+        self.plan = self._make_plan(model, loss_fn)      # the energy launch's plan: shared row maps
         dev = model.u_free.device
         self.device = dev
         self.n_u = int(model.u_free.shape[0])
@@ -159,7 +156,7 @@ class NewtonKrylovSolver:
             else:
                 te, tc = lf._traction(_Frozen(m, self._xf, self._xfix), self.t_force)
                 te = None if te is None else te.to(device=dev, dtype=F64).contiguous()
-            self._tables = ((C.c_double * 6)(*lf._body_table(self.b_force)), te, None if tc is None else (C.c_double * 4)(*tc), flags)
+            self._tables = (self._body(), te, None if tc is None else (C.c_double * 4)(*tc), flags)
             if self._amg is not None:
                 lam, mu = lf.lame
                 self._amg.setup(self._xf, self._xfix, (C.c_double * 4)(lam + 2 * mu, lam, lam + 2 * mu, mu), float(lf._W))
@@ -171,16 +168,8 @@ class NewtonKrylovSolver:
         if self._key is None or self._key != self._state_key():
             self.refresh()
 
-    # ---- launches
-    def _energy(self, u, g):
-        """self._out = {Pi, min J, inverted count} and g = dPi/du_free at u: one launch of the energy kernel (+ its finish)."""
-        bk, te, tc, flags = self._tables
-        check(_lib.lib().hfem_tri3_hyper_energy_plan(
-            self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
-            ptr(self._ufix) if self._ufix.numel() else None, self._lame, float(self.loss_fn._W), bk, ptr(te), tc,
-            self._out.data_ptr(), self._out.data_ptr() + 8, ptr(self._work), None, ptr(g), flags, stream_ptr(self.device)),
-            "hfem_tri3_hyper_energy_plan")
-
+    # ---- launches (``_energy(u, g)`` is the element's: self._out = {Pi, min J, inverted count} and g = dPi/du_free at u, one
+    # launch of the energy kernel + its finish)
     def _linearise(self):
         """Bind the driver to ``self._u`` and build the preconditioner there (one diag launch + the info reduction)."""
         check(_lib.lib().hfem_cg_setup_hyper(
@@ -313,7 +302,78 @@ class NewtonKrylovSolver:
         return self._info
 
 
+class NewtonKrylovSolver(_NewtonSolverBase):
+    """Inexact Newton with truncated PCG for ``model.u_free`` under a ``NeoHookeanLoss2D`` (see the module docstring and
+    ``_NewtonSolverBase`` for the arguments and the contract); TRI3 models only, anything else raises ``NotImplementedError``
+    (QUAD4 models under a ``Quad4NeoHookeanLoss2D``: ``Quad4NewtonKrylovSolver``)."""
+
+    @staticmethod
+    def _check_model(model, loss_fn):
+        if not isinstance(loss_fn, NeoHookeanLoss2D):
+            raise NotImplementedError("NewtonKrylovSolver: NeoHookeanLoss2D only (an EnergyLoss2D is quadratic in u_free: "
+                                      "FrozenMeshSolver / solve_displacement_ solve it in one linear solve)")
+        if getattr(model, "nodes_per_element", 3) != 3 or isinstance(loss_fn, Quad4NeoHookeanLoss2D):
+            raise NotImplementedError("NewtonKrylovSolver: TRI3 models under a NeoHookeanLoss2D only (QUAD4 models under a "
+                                      "Quad4NeoHookeanLoss2D: Quad4NewtonKrylovSolver / quad4_newton_solve_)")
+
+    @staticmethod
+    def _make_plan(model, loss_fn):
+        from .plan import model_plan
+        return model_plan(model, loss_fn.tile_elems, paired=False)
+
+    def _body(self):
+        return (C.c_double * 6)(*self.loss_fn._body_table(self.b_force))
+
+    def _energy(self, u, g):
+        bk, te, tc, flags = self._tables
+        check(_lib.lib().hfem_tri3_hyper_energy_plan(
+            self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
+            ptr(self._ufix) if self._ufix.numel() else None, self._lame, float(self.loss_fn._W), bk, ptr(te), tc,
+            self._out.data_ptr(), self._out.data_ptr() + 8, ptr(self._work), None, ptr(g), flags, stream_ptr(self.device)),
+            "hfem_tri3_hyper_energy_plan")
+
+
+class Quad4NewtonKrylovSolver(_NewtonSolverBase):
+    """``NewtonKrylovSolver`` for QUAD4 models (``QuadShapeNN2D``) under a ``Quad4NeoHookeanLoss2D``: the same
+    arguments, the same contract, the same ``NewtonInfo``.  ``K_T p`` and the block-Jacobi blocks come from
+    ``csrc/quad4_hyper_cg.hip`` on the model's own QUAD4 tile plan, residual and energy from the QUAD4 Neo-Hookean energy
+    launch on that plan (``hfem_quad4_hyper_energy_plan``; the body force at the 2x2 reference Gauss points, as the loss
+    tabulates it), ``precond="amg"`` from the QUAD4 hierarchy of the small-strain operator.  A cell is inverted when
+    ``det F <= 0`` at any of its four Gauss points; ``min_J`` is taken over all points.  Anything but a QUAD4 model with a
+    ``Quad4NeoHookeanLoss2D`` raises ``NotImplementedError``."""
+
+    @staticmethod
+    def _check_model(model, loss_fn):
+        if not isinstance(loss_fn, Quad4NeoHookeanLoss2D):
+            raise NotImplementedError("Quad4NewtonKrylovSolver: Quad4NeoHookeanLoss2D only (a NeoHookeanLoss2D on a TRI3 model: "
+                                      "NewtonKrylovSolver; an EnergyLoss2D is quadratic in u_free: Quad4FrozenMeshSolver / "
+                                      "solve_displacement_ solve it in one linear solve)")
+        if getattr(model, "nodes_per_element", 3) != 4:
+            raise NotImplementedError("Quad4NewtonKrylovSolver: QUAD4 models only (TRI3 models: NewtonKrylovSolver)")
+
+    @staticmethod
+    def _make_plan(model, loss_fn):
+        return model.tile_plan(loss_fn.tile_elems)
+
+    def _body(self):
+        bq = self.loss_fn._quad4_body(self.b_force)
+        return None if bq is None else (C.c_double * 8)(*bq)
+
+    def _energy(self, u, g):
+        bq, te, tc, flags = self._tables
+        check(_lib.lib().hfem_quad4_hyper_energy_plan(
+            self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
+            ptr(self._ufix) if self._ufix.numel() else None, self._lame, bq, ptr(te), tc, self._out.data_ptr(),
+            self._out.data_ptr() + 8, ptr(self._work), None, ptr(g), flags, stream_ptr(self.device)),
+            "hfem_quad4_hyper_energy_plan")
+
+
 def newton_solve_(model, loss_fn, **kw) -> NewtonInfo:
     """One-shot ``NewtonKrylovSolver(model, loss_fn, **kw).solve()``: ``model.u_free`` becomes the equilibrium of the
     Neo-Hookean potential at the current coordinates (in place)."""
     return NewtonKrylovSolver(model, loss_fn, **kw).solve()
+
+
+def quad4_newton_solve_(model, loss_fn, **kw) -> NewtonInfo:
+    """One-shot ``Quad4NewtonKrylovSolver(model, loss_fn, **kw).solve()`` for a QUAD4 model under a ``Quad4NeoHookeanLoss2D``."""
+    return Quad4NewtonKrylovSolver(model, loss_fn, **kw).solve()

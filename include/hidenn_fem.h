@@ -740,7 +740,7 @@ int hfem_cg_iterate(hfem_cg *cg, double *u_free, int32_t n_iter, void *stream);
 int hfem_cg_status(hfem_cg *cg, double *status_host, void *stream);
 int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void *stream);
 
-/* ------------------------------------------------------------------ Newton-Krylov on the Neo-Hookean tangent (TRI3)
+/* ------------------------------------------------------------------ Newton-Krylov on the Neo-Hookean tangent (TRI3, QUAD4)
  * The same driver with a third element kind (csrc/tri3_hyper_cg.hip; hidenn_fem_amd/newton.py): K is the tangent
  * K_T = d2Pi/du2 of hfem_tri3_hyper_energy_plan's potential at a linearisation point u_lin, on that entry point's plan (TRI3,
  * ONE element per slot), so the residual launch and the operator share a plan and its row maps.  Per element, with T = F^-T,
@@ -748,10 +748,18 @@ int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void 
  * loads do not enter.  An element with J <= 0 contributes a ZERO block and is counted.  K_T may be indefinite: the driver's
  * breakdown halt (p^T K p <= 0, before u moves) is then the truncation rule of truncated Newton, and a diagonal block that is
  * not positive definite is the identity in the block-Jacobi preconditioner.
- *   create_hyper  a QUAD4, paired or host-only plan, or a tile that needs more than 64 KiB of LDS (48 bytes per local node +
- *                 16 per owned row), is an argument error.
+ * A QUAD4 plan (the model's own, the one hfem_quad4_hyper_energy_plan takes) selects the fourth element kind
+ * (csrc/quad4_hyper_cg.hip): the tangent of that entry point's potential, the same dP at each of the 2x2 Gauss points with
+ * A = |det J_q|, spread through grad_xi N_k(xi_q).  A cell with j_q <= -1 at ANY point contributes a zero block and is counted
+ * once; min J is taken over all points.  For a QUAD4 plan setup_hyper's block launch also stores mu - lambda log1p(j_q) of
+ * every slot and point in the solver's own allocation (32 bytes per slot of the plan); apply and iterate read it, so they
+ * evaluate the tangent at the point setup_hyper last saw.
+ *   create_hyper  a paired or host-only plan, a QUAD4 plan without its fourth-corner records, or a tile that needs more than
+ *                 64 KiB of LDS in either kernel (apply: 48 bytes per local node + 16 per owned row; blocks: 32 + 24), is an
+ *                 argument error.
  *   setup_hyper   binds the coordinate rows, the linearisation point's rows (u_lin_free [n_u][2], u_fixed; fp64, they must
- *                 stay allocated and unchanged while iterating) and lame[2] = (lambda, mu) (host), W, and builds the
+ *                 stay allocated and unchanged while iterating) and lame[2] = (lambda, mu) (host), W (the sum of the triangle
+ *                 weights; not read for a QUAD4 plan, whose 2x2 weights are 1, as in hfem_cg_setup), and builds the
  *                 preconditioner at u_lin: precond 1 = block Jacobi, 0 = none.  diag_out [n_u][3] (may be NULL): the blocks;
  *                 info_out[2] (device, may be NULL) = {min J, number of elements with J <= 0} at u_lin.  Pointers are bound,
  *                 not copied: writing a new point into the same buffers and calling setup_hyper again re-linearises, and a

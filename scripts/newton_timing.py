@@ -15,7 +15,15 @@ the linear frozen-mesh solution): per preconditioner the Newton iterations, CG i
 ``NewtonKrylovSolver.solve()`` (host clock, synchronised; the first solve of a solver includes its graph capture), beside the
 increment as the example minimises it without ``--newton``: 100 outer ``FusedLBFGS`` steps, their seconds and the |g|inf reached.
 
-    python scripts/newton_timing.py [--reps 2000] [--out-dir profiles/newton] [--small]
+``--quad``: the same two records for QUAD4.  Launches at DESIGN 19's Q1M (1001 x 1001 nodes, 10^6 QUAD4 cells on
+[0, 2]^2, fp64, jitter 0.2, every row free, the field on every row), all three on the model's own QUAD4 plan and the same
+buffers: hfem_cg_apply on the QUAD4 tangent (csrc/quad4_hyper_cg.hip), hfem_quad4_hyper_energy_plan with HFEM_FLAG_NO_GX, and
+``Quad4FrozenMeshSolver``'s linear hfem_cg_apply (csrc/quad4_cg.hip).  The increment: ``example4 --neo-hookean --quad``'s plate
+(no holes) with ``Quad4NewtonKrylovSolver``.  Written to newton_timing_Q1M.json.  ``--lib-tag recompute --launches-only`` runs
+the launches on ``csrc/build.py --tag recompute --define HFEM_QUAD4_TANGENT_RECOMPUTE``'s library (the apply that calls log1p
+instead of reading the c_q its diag launch stored) and writes newton_timing_Q1M_recompute.json: the A/B pair of DESIGN 20.
+
+    python scripts/newton_timing.py [--quad] [--reps 2000] [--out-dir profiles/newton] [--small] [--lib-tag TAG] [--launches-only]
 """
 import argparse
 import json
@@ -27,11 +35,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from hidenn_fem_amd import _lib
-from hidenn_fem_amd.loss import EnergyLoss2D, NeoHookeanLoss2D
-from hidenn_fem_amd.mesh import generate_mesh, structured_tri_mesh
+from hidenn_fem_amd.loss import EnergyLoss2D, NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
+from hidenn_fem_amd.mesh import generate_mesh, structured_quad_mesh, structured_tri_mesh
 from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
-from hidenn_fem_amd.newton import NewtonKrylovSolver
-from hidenn_fem_amd.solve import FrozenMeshSolver, solve_displacement_
+from hidenn_fem_amd.newton import NewtonKrylovSolver, Quad4NewtonKrylovSolver
+from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver, solve_displacement_
 
 F64 = torch.float64
 
@@ -51,16 +59,25 @@ def field(x):
                         0.15 * torch.cos(1.7 * x[:, 0] + 0.3) * torch.sin(2.4 * x[:, 1])], dim=1)
 
 
-def launches(nx, ny, reps):
+def launches(nx, ny, reps, quad=False):
     dev = torch.device("cuda:0")
-    coords, conn, geom, bc, _, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
-    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=field(coords)[bc],
-                                 neumann_edges=edges)                # the field on the Dirichlet rows too: no jump, no inversion
-    with torch.no_grad():
-        m.u_free.copy_(m.from_caller_order(field(coords)[~bc], "u"))
-    m = m.to(dev)
-    nk = NewtonKrylovSolver(m, NeoHookeanLoss2D(device=dev, dtype=F64))
-    lin = FrozenMeshSolver(m, EnergyLoss2D(device=dev, dtype=F64))
+    if quad:
+        coords, conn, *_ = structured_quad_mesh(nx, ny, length=2.0, height=2.0, jitter=0.2, seed=0, dtype=F64)
+        m = PiecewiseLinearShapeNN2D(coords, conn)                   # DESIGN 19's Q1M: every row free
+        with torch.no_grad():
+            m.u_free.copy_(m.from_caller_order(field(coords), "u"))
+        m = m.to(dev)
+        nk = Quad4NewtonKrylovSolver(m, Quad4NeoHookeanLoss2D(device=dev, dtype=F64))
+        lin = Quad4FrozenMeshSolver(m, EnergyLoss2D(device=dev, dtype=F64))
+    else:
+        coords, conn, geom, bc, _, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+        m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=field(coords)[bc],
+                                     neumann_edges=edges)            # the field on the Dirichlet rows too: no jump, no inversion
+        with torch.no_grad():
+            m.u_free.copy_(m.from_caller_order(field(coords)[~bc], "u"))
+        m = m.to(dev)
+        nk = NewtonKrylovSolver(m, NeoHookeanLoss2D(device=dev, dtype=F64))
+        lin = FrozenMeshSolver(m, EnergyLoss2D(device=dev, dtype=F64))
     lin.refresh()
     p = torch.randn(m.u_free.shape, dtype=F64, device=dev) * 1e-4
     nk.apply(p)                                                     # refresh + linearise at the field
@@ -87,10 +104,11 @@ def launches(nx, ny, reps):
             t[k].append(window_us(f, reps))
     med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
     s = nk.plan.stats
-    rec = dict(mesh=f"{nx}x{ny} structured TRI3, jitter 0.2, left edge clamped", n_elems=m.Nelems, n_nodes=m.Nnodes,
+    rec = dict(mesh=f"{nx}x{ny} structured QUAD4 on [0, 2]^2, jitter 0.2, every row free" if quad
+               else f"{nx}x{ny} structured TRI3, jitter 0.2, left edge clamped", n_elems=m.Nelems, n_nodes=m.Nnodes,
                n_u_rows=int(m.u_free.shape[0]), min_J=nk.info[0].item(), inverted=nk.info[1].item(),
                plan_tangent=dict(paired=bool(s["paired"]), n_tiles=s["n_tiles"], max_tile_nodes=s["max_tile_nodes"],
-                                 max_tile_elems=s["max_tile_elems"], threads_per_tile=512),
+                                 max_tile_elems=s["max_tile_elems"], threads_per_tile=256 if quad else 512),
                plan_linear=dict(paired=bool(lin.plan.stats["paired"]), n_tiles=lin.plan.stats["n_tiles"]),
                regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)",
                reps_per_window=reps, windows=7)
@@ -101,24 +119,28 @@ def launches(nx, ny, reps):
     return rec
 
 
-def increment(nx, ny, load_steps=8, lbfgs_steps=100, E=10e9, nu=0.3):
+def increment(nx, ny, load_steps=8, lbfgs_steps=100, E=10e9, nu=0.3, quad=False):
     from hidenn_fem_amd.optim import FusedLBFGS
     dev = torch.device("cuda:0")
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
-    nodes, conn, geom, bc, _, edges = generate_mesh(2.0, 1.0, holes, sides, nx, ny)
+    if quad:
+        nodes, conn, geom, bc, _, edges = structured_quad_mesh(nx, ny, length=2.0, height=1.0, boundaries=sides)
+    else:
+        nodes, conn, geom, bc, _, edges = generate_mesh(2.0, 1.0, holes, sides, nx, ny)
     m = PiecewiseLinearShapeNN2D(nodes.to(F64), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
     m.node_coords_free.requires_grad_(False)
-    lf = NeoHookeanLoss2D(E=E, nu=nu, length=2.0, height=1.0, device=dev, dtype=F64)
+    lf = (Quad4NeoHookeanLoss2D if quad else NeoHookeanLoss2D)(E=E, nu=nu, length=2.0, height=1.0, device=dev, dtype=F64)
+    solver = Quad4NewtonKrylovSolver if quad else NewtonKrylovSolver
     scale = 1.0 / load_steps
     tr = lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -scale * E / 500.0)], dim=1)
     solve_displacement_(m, EnergyLoss2D(E=E, nu=nu, device=dev, dtype=F64, grad_convention="physical"), t_force=tr, rtol=1e-10)
     u_lin = m.u_free.detach().clone()
-    rec = dict(mesh=f"example 4 plate with holes, {nx}x{ny}", n_elems=m.Nelems, n_nodes=m.Nnodes, load=scale, newton={})
+    rec = dict(mesh=f"example 4 QUAD4 plate (no holes), {nx}x{ny} nodes" if quad else f"example 4 plate with holes, {nx}x{ny}", n_elems=m.Nelems, n_nodes=m.Nnodes, load=scale, newton={})
     for pc in ("block_jacobi", "amg", "none"):
         with torch.no_grad():
             m.u_free.copy_(u_lin)
-        s = NewtonKrylovSolver(m, lf, t_force=tr, precond=pc)
+        s = solver(m, lf, t_force=tr, precond=pc)
         s.refresh()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -160,15 +182,29 @@ def main():
     ap.add_argument("--reps", type=int, default=2000)
     ap.add_argument("--out-dir", default="")
     ap.add_argument("--small", action="store_true", help="101x51 / 60x30 nodes (a check that the script runs)")
+    ap.add_argument("--quad", action="store_true", help="Q1M and example 4's QUAD4 plate: the QUAD4 tangent (DESIGN 20)")
+    ap.add_argument("--lib-tag", default="", help="run on csrc/libhidenn_hip_<tag>.so (csrc/build.py --tag: an A/B build)")
+    ap.add_argument("--launches-only", action="store_true", help="skip the load increment")
     a = ap.parse_args()
     big = not a.small
-    rec = dict(launches=launches(*((1001, 501) if big else (101, 51)), a.reps),
-               increment=increment(*((200, 100) if big else (60, 30))))
+    if a.lib_tag:
+        _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libhidenn_hip_{a.lib_tag}.so")
+    if a.launches_only:
+        rec = dict(launches=launches(*(((1001, 1001) if a.quad else (1001, 501)) if big else ((101, 101) if a.quad else (101, 51))),
+                                     a.reps, quad=a.quad))
+    elif a.quad:
+        rec = dict(launches=launches(*((1001, 1001) if big else (101, 101)), a.reps, quad=True),
+                   increment=increment(*((200, 100) if big else (60, 30)), quad=True))
+    else:
+        rec = dict(launches=launches(*((1001, 501) if big else (101, 51)), a.reps),
+                   increment=increment(*((200, 100) if big else (60, 30))))
+    rec["library"] = a.lib_tag or "product"
     line = json.dumps(rec)
     print(line)
     if a.out_dir:
         os.makedirs(a.out_dir, exist_ok=True)
-        with open(os.path.join(a.out_dir, "newton_timing_T1M.json" if big else "newton_timing_small.json"), "w") as f:
+        name = ("newton_timing_Q1M" if a.quad else "newton_timing_T1M") if big else "newton_timing_small"
+        with open(os.path.join(a.out_dir, name + (f"_{a.lib_tag}" if a.lib_tag else "") + ".json"), "w") as f:
             f.write(line + "\n")
 
 
