@@ -141,8 +141,10 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     smallest load, the gap to the linear solution.  Returns ``(model, energy)``.
     ``newton=True`` (``--newton``): the same ramp, predictor and halving rule, each increment solved to equilibrium by
     ``hidenn_fem_amd.newton.NewtonKrylovSolver`` (inexact Newton, truncated PCG on the tangent, preconditioner ``precond``)
-    instead of ``FusedLBFGS``; the line then also shows the Newton and CG iterations.  An increment whose Newton solve does
-    not converge is taken back and halved like an inverted one.
+    instead of ``FusedLBFGS``; the line then also shows the Newton and CG iterations (``precond="amg_tangent"``, the AMG
+    hierarchy of the assembled tangent rebuilt at every linearisation: also the number of tangent setups and of fallbacks
+    to the small-strain hierarchy, coarse / descent).  An increment whose Newton solve does not converge is taken back and
+    halved like an inverted one.
     ``quad=True`` (``--quad``): the same ramp on the plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
     (``structured_quad_mesh``), with ``Quad4NeoHookeanLoss2D``; with ``newton=True`` every increment is solved by
     ``Quad4NewtonKrylovSolver``."""
@@ -188,9 +190,10 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     def equilibrium(scale):
         from hidenn_fem_amd.newton import NewtonKrylovSolver, Quad4NewtonKrylovSolver
         solver = Quad4NewtonKrylovSolver if quad else NewtonKrylovSolver
-        info = solver(model, loss_fn, t_force=traction(scale), precond=precond).solve()
+        s = solver(model, loss_fn, t_force=traction(scale), precond=precond)
+        info = s.solve()
         ginf = float("inf") if not info.converged else info.grad_norm       # an unconverged increment is taken back
-        return info.energy, info.min_J, 0 if info.converged else 1, ginf, info
+        return info.energy, info.min_J, 0 if info.converged else 1, ginf, info, s.amg if precond == "amg_tangent" else None
 
     done, inc, first = 0.0, 1.0 / load_steps, True
     energy = float("nan")
@@ -206,7 +209,7 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
             else:                                                  # along the secant through the last two accepted states
                 model.u_free.add_((keep - prev) * ((target - done) / (done - prev_load)))
         if newton:
-            value, min_j, inverted, ginf, ninfo = equilibrium(target)
+            value, min_j, inverted, ginf, ninfo, amg = equilibrium(target)
         else:
             value, min_j, inverted, ginf = minimise(target)
         if inverted > 0 or value != value or value in (float("inf"), float("-inf")):
@@ -221,7 +224,9 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
         defl = model.u_free.detach()[tip, 1].mean().item()
         if newton:
             print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|2 {ginf:.3e} "
-                  f"Newton {ninfo.newton_iterations} CG {ninfo.cg_iterations}")
+                  f"Newton {ninfo.newton_iterations} CG {ninfo.cg_iterations}"
+                  + ("" if amg is None else f" tangent setups {amg['tangent_setups']} fallbacks coarse "
+                     f"{amg['fallbacks_coarse']} descent {amg['fallbacks_descent']}"))
         else:
             print(f"load {target:.4f}: energy {value:.9e} min J {min_j:.4f} tip deflection {defl:+.4f} |g|inf {ginf:.3e}")
         if first:
@@ -280,8 +285,8 @@ if __name__ == "__main__":
     ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
     ap.add_argument("--quad", action="store_true",
                     help="with --r-adapt or --neo-hookean: the plate as nx x ny nodes of QUAD4 cells (no holes)")
-    ap.add_argument("--precond", choices=["block_jacobi", "amg"], default="block_jacobi",
-                    help="CG preconditioner of --solve-first and --r-adapt")
+    ap.add_argument("--precond", choices=["block_jacobi", "amg", "amg_tangent"], default="block_jacobi",
+                    help="CG preconditioner of --solve-first, --r-adapt and --neo-hookean --newton (amg_tangent: the latter only)")
     ap.add_argument("--error-estimate", action="store_true",
                     help="print the relative ZZ error estimate after the solve (with --r-adapt: before and after adaptation); "
                          "builds the loss with grad_convention='physical'")
@@ -292,6 +297,8 @@ if __name__ == "__main__":
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
     a = ap.parse_args()
+    if a.precond == "amg_tangent" and not (a.neo_hookean and a.newton):
+        ap.error("--precond amg_tangent needs --neo-hookean --newton (with or without --quad)")
     if a.neo_hookean:
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad)
         raise SystemExit(0)

@@ -173,6 +173,8 @@ PROTOTYPES = {
     "hfem_amg_destroy": (C.c_int, [_vp]),
     "hfem_amg_assemble": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp]),
     "hfem_amg_setup": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_amg_assemble_hyper": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp]),
+    "hfem_amg_setup_hyper": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_amg_set_coarse": (C.c_int, [_vp, _vp]),
     "hfem_amg_vcycle": (C.c_int, [_vp, _vp, _vp, _vp]),
     "hfem_amg_values": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),

@@ -145,11 +145,13 @@ int build(const int32_t *conn, int64_t ne, int npe, int64_t nn, const int32_t *x
     h.row_x.resize((size_t)n_u);
     for (int32_t r = 0; r < n_u; ++r) h.row_x[r] = x_src[row_node[r]];
     h.conn_x.resize((size_t)ne * npe);
+    h.conn_u.resize((size_t)ne * npe);
     for (int64_t e = 0; e < ne; ++e)
         for (int a = 0; a < npe; ++a) {
             const int32_t v = conn[npe * e + a];
             if (v < 0 || v >= nn) { hfem::set_error("hfem_amg_host_create: connectivity out of range"); return -1; }
             h.conn_x[npe * e + a] = x_src[v];
+            h.conn_u[npe * e + a] = u_src[v];
         }
     // node -> element fan of every free row (element ascending)
     h.fan_ptr.assign((size_t)n_u + 1, 0);
@@ -220,6 +222,7 @@ const std::vector<int32_t> *array_of(const hfem_amg_host *h, int32_t level, int3
             case 1: return &h->fan_elem;
             case 2: return &h->fan_corner;
             case 3: return &h->fan_slot;
+            case 4: return &h->conn_u;
             default: return nullptr;
         }
     }

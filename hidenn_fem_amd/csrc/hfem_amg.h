@@ -31,6 +31,8 @@ struct hfem_amg_host {
     int64_t ne = 0, nn = 0;
     int32_t n_u = 0, npe = 3;                          // npe: corners per element, 3 (TRI3) or 4 (QUAD4)
     std::vector<int32_t> conn_x;                       // [ne][npe] x row code of every corner (x_src of the node)
+    std::vector<int32_t> conn_u;                       // [ne][npe] u row code of every corner (u_src of the node: a free
+                                                       // row index, or -1 - k for fixed row k)
     std::vector<int32_t> row_x;                        // [n_u] x row code of every free u row
     // node -> element fan of every free u row, fixed order (element id ascending); per entry: element, corner, and the
     // block slot of row (corner) that each of the npe corners' columns writes to (-1: a Dirichlet corner, dropped)

@@ -15,6 +15,15 @@
 //   amg_ap_kernel, amg_rap_kernel   A_c = R (A P): row-wise numeric products into the precomputed patterns (slot by binary
 //                         search), each output row summed in a fixed order.
 //   amg_coarse_scatter_kernel       the coarsest A into a dense matrix for the host-side inverse.
+// Tangent setup (hfem_amg_setup_hyper, at a Newton linearisation): the same numeric setup on the assembled
+// Neo-Hookean tangent K_T,ff at (x, u):
+//   amg_assemble_hyper_kernel   amg_assemble_kernel's walk with the element tangent (hfem_amg_hyper_dev.h: U gathered through
+//                         conn_u, the two unit directions at the corner by selects, state + two applies for TRI3, two fused
+//                         applies for QUAD4).  An inverted element or cell contributes zeros, so the matrix is exactly the
+//                         operator hfem_cg_apply applies on a hyper handle.  No atomics: bit-deterministic.
+//   amg_ns0_kernel        with u_free: the rotation column at the deformed position, (-(y + v), x + u).
+// Everything from setup_level down is shared.  One handle may be set up by either entry point, in any order: pointers and
+// patterns never change, only values do, so a captured hfem_cg_iterate_amg graph stays valid across re-setups of either kind.
 // V-cycle (amg_cycle): Chebyshev degree 2 on D^-1 A over [lambda_hat / 30, lambda_hat], the same polynomial before and after
 // the coarse correction (a symmetric positive-definite M), block SpMV with the recurrence fused (amg_cheb_kernel), R and P
 // products, and a dense GEMV with the coarsest inverse.  Every cycle launch returns at once when the CG status record says
@@ -27,6 +36,7 @@
 #include <string>
 
 #include "hfem_amg.h"
+#include "hfem_amg_hyper_dev.h"
 #include "hfem_cg_dev.h"
 #include "hfem_device.h"
 #include "hfem_plan_dev.h"
@@ -81,6 +91,26 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
             *p = v;
         }
     }
+}
+
+// K_T,ff of the Neo-Hookean energy at (x, u): one thread per free row runs amg_hyper_row (hfem_amg_hyper_dev.h)
+template <int NPE>
+__global__ __launch_bounds__(kBlock) void amg_assemble_hyper_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
+                                                                    const int32_t *__restrict__ fan_elem,
+                                                                    const int32_t *__restrict__ fan_corner,
+                                                                    const int32_t *__restrict__ fan_slot,
+                                                                    const int32_t *__restrict__ conn_x,
+                                                                    const int32_t *__restrict__ conn_u,
+                                                                    const double2 *__restrict__ x_free,
+                                                                    const double2 *__restrict__ x_fixed,
+                                                                    const double2 *__restrict__ u_free,
+                                                                    const double2 *__restrict__ u_fixed,
+                                                                    const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
+                                                                    double lambda, double mu, double W) {
+    const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (r >= n) return;
+    amg_hyper_row<NPE>(r, fan_ptr, fan_elem, fan_corner, fan_slot, conn_x, conn_u, x_free, x_fixed, u_free, u_fixed, a_ptr, a_val,
+                       lambda, mu, W);
 }
 
 // ---------------------------------------------------------------- diagonal block inverses
@@ -200,13 +230,18 @@ __global__ __launch_bounds__(kBlock) void amg_power_finish_kernel(const double *
 }
 
 // ---------------------------------------------------------------- near-null space and tentative prolongator
-// fine level: rows [[1, 0, -y], [0, 1, x]] of every free u row at the current coordinates
+// fine level: rows [[1, 0, -y], [0, 1, x]] of every free u row at the current coordinates; with u_free (the tangent setup)
+// at the deformed position, [[1, 0, -(y + v)], [0, 1, x + u]]
 __global__ __launch_bounds__(kBlock) void amg_ns0_kernel(int32_t n, const int32_t *__restrict__ row_x,
                                                          const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-                                                         double *__restrict__ ns) {
+                                                         const double2 *__restrict__ u_free, double *__restrict__ ns) {
     const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (i >= n) return;
-    const double2 X = x_row(x_free, x_fixed, row_x[i]);
+    double2 X = x_row(x_free, x_fixed, row_x[i]);
+    if (u_free) {
+        const double2 U = u_free[i];
+        X.x += U.x; X.y += U.y;
+    }
     double *o = ns + (size_t)i * 6;
     o[0] = 1.0; o[1] = 0.0; o[2] = -X.y;
     o[3] = 0.0; o[4] = 1.0; o[5] = X.x;
@@ -556,14 +591,15 @@ struct hfem_amg {
     int device = -1;
     bool phys = false;
     int32_t n_u = 0, npe = 3;              // npe: corners per element of the fine level's fan (3 TRI3, 4 QUAD4)
+    int64_t conn_x_fixed = 0, conn_u_fixed = 0;   // corners that read a fixed x / u row (the hyper entry points' null checks)
     int32_t *fan_ptr = nullptr, *fan_elem = nullptr, *fan_corner = nullptr, *fan_slot = nullptr, *conn_x = nullptr,
-            *row_x = nullptr;
+            *conn_u = nullptr, *row_x = nullptr;
     std::vector<DevLevel> lv;
     int64_t n_coarse = 0;                  // dofs of the coarsest level
     const double *coarse_inv = nullptr;    // caller-owned N x N inverse (hfem_amg_set_coarse)
     double *part = nullptr;
     std::vector<void *> allocs;
-    bool built = false, ready = false;     // hfem_amg_setup ran / and a coarse inverse is bound
+    bool built = false, ready = false;     // hfem_amg_setup[_hyper] ran / and a coarse inverse is bound
 };
 
 namespace {
@@ -673,9 +709,41 @@ void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const do
 #undef HFEM_AMG_ASM
 }
 
+void assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
+                    const double lame[2], double W, hipStream_t s) {
+    const DevLevel &L = a->lv[0];
+#define HFEM_AMG_ASM_HYPER(NPE)                                                                                               \
+    hipLaunchKernelGGL((hfem::amg_assemble_hyper_kernel<NPE>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr, a->fan_elem, \
+                       a->fan_corner, a->fan_slot, a->conn_x, a->conn_u, (const double2 *)x_free, (const double2 *)x_fixed,    \
+                       (const double2 *)u_free, (const double2 *)u_fixed, L.a_ptr, L.a_val, lame[0], lame[1], W)
+    if (a->npe == 4) HFEM_AMG_ASM_HYPER(4);                   // QUAD4: the 2x2 rule's weights are 1, W is not read
+    else HFEM_AMG_ASM_HYPER(3);
+#undef HFEM_AMG_ASM_HYPER
+}
+
+// the numeric hierarchy on the fine level's assembled values and near-null space, and the dense coarsest matrix
+int setup_levels(hfem_amg *a, double *coarse_out, hipStream_t s, const char *what) {
+    for (size_t l = 0; l < a->lv.size(); ++l) {
+        if (a->lv[l].bs == 2) setup_level<2>(a, l, s);
+        else setup_level<3>(a, l, s);
+    }
+    const DevLevel &Lc = a->lv.back();
+    HFEM_HIP_CHECK(hipMemsetAsync(coarse_out, 0, (size_t)a->n_coarse * a->n_coarse * sizeof(double), s));
+    if (Lc.bs == 2)
+        hipLaunchKernelGGL(hfem::amg_coarse_scatter_kernel<2>, grid_of(Lc.n), dim3(kBlock), 0, s, Lc.n, Lc.a_ptr, Lc.a_col,
+                           Lc.a_val, coarse_out);
+    else
+        hipLaunchKernelGGL(hfem::amg_coarse_scatter_kernel<3>, grid_of(Lc.n), dim3(kBlock), 0, s, Lc.n, Lc.a_ptr, Lc.a_col,
+                           Lc.a_val, coarse_out);
+    if (int rc = hfem::launch_status(what)) return rc;
+    a->built = true;
+    return 0;
+}
+
 int create(hfem_amg *a, const hfem_amg_host *h) {
     if (upload(a, &a->fan_ptr, h->fan_ptr) || upload(a, &a->fan_elem, h->fan_elem) || upload(a, &a->fan_corner, h->fan_corner) ||
-        upload(a, &a->fan_slot, h->fan_slot) || upload(a, &a->conn_x, h->conn_x) || upload(a, &a->row_x, h->row_x))
+        upload(a, &a->fan_slot, h->fan_slot) || upload(a, &a->conn_x, h->conn_x) || upload(a, &a->conn_u, h->conn_u) ||
+        upload(a, &a->row_x, h->row_x))
         return -1;
     a->lv.resize(h->levels.size());
     for (size_t l = 0; l < h->levels.size(); ++l) {
@@ -722,6 +790,8 @@ extern "C" int hfem_amg_create(int device, const hfem_amg_host *host, int32_t fl
     if (int rc = hfem::use_device(device)) return rc;
     std::unique_ptr<hfem_amg> a(new hfem_amg);
     a->device = device; a->phys = (flags & HFEM_FLAG_PHYSICAL_GRAD) != 0; a->n_u = host->n_u; a->npe = host->npe;
+    for (int32_t c : host->conn_x) a->conn_x_fixed += c < 0;
+    for (int32_t c : host->conn_u) a->conn_u_fixed += c < 0;
     if (create(a.get(), host)) {
         release(a.get());
         return -1;
@@ -753,22 +823,31 @@ extern "C" int hfem_amg_setup(hfem_amg *a, const double *x_free, const double *x
     hipStream_t s = (hipStream_t)stream;
     assemble(a, x_free, x_fixed, mat, W, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
-                       (const double2 *)x_fixed, a->lv[0].ns);
-    for (size_t l = 0; l < a->lv.size(); ++l) {
-        if (a->lv[l].bs == 2) setup_level<2>(a, l, s);
-        else setup_level<3>(a, l, s);
-    }
-    const DevLevel &Lc = a->lv.back();
-    HFEM_HIP_CHECK(hipMemsetAsync(coarse_out, 0, (size_t)a->n_coarse * a->n_coarse * sizeof(double), s));
-    if (Lc.bs == 2)
-        hipLaunchKernelGGL(hfem::amg_coarse_scatter_kernel<2>, grid_of(Lc.n), dim3(kBlock), 0, s, Lc.n, Lc.a_ptr, Lc.a_col,
-                           Lc.a_val, coarse_out);
-    else
-        hipLaunchKernelGGL(hfem::amg_coarse_scatter_kernel<3>, grid_of(Lc.n), dim3(kBlock), 0, s, Lc.n, Lc.a_ptr, Lc.a_col,
-                           Lc.a_val, coarse_out);
-    if (int rc = hfem::launch_status("hfem_amg_setup")) return rc;
-    a->built = true;
-    return 0;
+                       (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
+    return setup_levels(a, coarse_out, s, "hfem_amg_setup");
+}
+
+extern "C" int hfem_amg_assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free,
+                                       const double *u_fixed, const double lame[2], double W, void *stream) {
+    HFEM_ARG_CHECK(a && x_free && u_free && lame, "null pointer");
+    HFEM_ARG_CHECK(a->conn_u_fixed == 0 || u_fixed, "the mesh has Dirichlet rows: u_fixed must be given");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    assemble_hyper(a, x_free, x_fixed, u_free, u_fixed, lame, W, (hipStream_t)stream);
+    return hfem::launch_status("hfem_amg_assemble_hyper");
+}
+
+extern "C" int hfem_amg_setup_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free,
+                                    const double *u_fixed, const double lame[2], double W, double *coarse_out, void *stream) {
+    HFEM_ARG_CHECK(a && x_free && u_free && lame && coarse_out, "null pointer");
+    HFEM_ARG_CHECK(a->conn_u_fixed == 0 || u_fixed, "the mesh has Dirichlet rows: u_fixed must be given");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    assemble_hyper(a, x_free, x_fixed, u_free, u_fixed, lame, W, s);
+    hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
+                       (const double2 *)x_fixed, (const double2 *)u_free, a->lv[0].ns);
+    return setup_levels(a, coarse_out, s, "hfem_amg_setup_hyper");
 }
 
 extern "C" int hfem_amg_set_coarse(hfem_amg *a, const double *coarse_inv) {

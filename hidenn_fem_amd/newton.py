@@ -14,6 +14,9 @@ the iterate moves -- is then the truncation rule of truncated Newton: the direct
 at its iteration 0, the preconditioned steepest-descent direction ``-M g``.  A CG ``max_iter`` halt also takes the direction
 reached.  Both are documented behaviour, not errors; with a positive definite preconditioner every such direction descends.
 
+``assemble_tangent`` returns K_T itself as a sparse matrix, and ``precond="amg_tangent"`` builds the AMG hierarchy on it
+(DESIGN 21), with fallbacks to the small-strain hierarchy where K_T is not positive definite.
+
 Not deterministic: the LDS atomics of the matrix-vector product make iterates differ in the last bits from run to run.
 """
 from __future__ import annotations
@@ -31,6 +34,8 @@ from .loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
 from .solve import (F64, HFEM_FLAG_NO_EDGES, HFEM_FLAG_NO_GX, ST_HALTED, ST_ITER, ST_REASON, _AmgDevice, _Frozen, _REASONS,
                     amg_host)
 
+_AMG_PRECONDS = ("amg", "amg_tangent")
+
 EPS = 2.2e-16
 
 
@@ -43,7 +48,9 @@ class NewtonInfo:
     ``"line_search"`` (no step length passed the sufficient-decrease test) or ``"inverted"`` (the starting state has an element
     with J <= 0: ``u_free`` was not touched).  ``history``: one dict per Newton iteration -- ``energy`` and ``grad_norm`` at
     its start, the forcing term ``eta``, ``cg_iterations`` and ``cg_reason`` (``"rtol"``, ``"max_iter"``, ``"breakdown"``) of its
-    inner solve, the accepted ``step`` t (0 when none was) and ``min_J`` of the accepted state."""
+    inner solve, the accepted ``step`` t (0 when none was) and ``min_J`` of the accepted state; with ``precond="amg_tangent"``
+    only, ``amg``: ``"tangent"`` or ``"small_strain"``, the hierarchy that preconditioned the inner solve whose direction
+    was taken."""
     newton_iterations: int
     cg_iterations: int
     grad_norm: float
@@ -65,7 +72,15 @@ class _NewtonSolverBase:
     diagonal blocks, rebuilt every Newton iteration; a block that is not positive definite is the identity), ``"none"``, or
     ``"amg"`` (the smoothed-aggregation hierarchy of the SMALL-STRAIN operator at the current coordinates, material
     ``(lambda + 2 mu, lambda, lambda + 2 mu, mu)``: set up once per refresh, a fixed SPD preconditioner for the varying
-    tangent; needs Dirichlet rows).  Newton stops at ``||g|| <= max(rtol ||g(u_free = 0)||, atol)``, tested first in every
+    tangent; needs Dirichlet rows), or ``"amg_tangent"`` (the same hierarchy, on the same handle, of the ASSEMBLED
+    tangent K_T(u_k) with the rigid modes at the deformed position; needs Dirichlet rows.  ``amg_rebuild="newton"``: a
+    numeric setup at every linearisation; ``"solve"``: at the first inner solve of each ``solve()`` only -- for load ramps
+    that start from the last equilibrium.  K_T can be indefinite, so two safeguards fall back to the small-strain numbers
+    of ``"amg"`` on the same handle: (a) when the Cholesky factorisation of the symmetrised coarsest matrix fails, the
+    small-strain setup replaces the tangent setup for this linearisation; (b) when an inner solve under the tangent
+    hierarchy ends with ``g.d >= 0`` or a non-finite value, the small-strain setup is made and that inner solve is repeated
+    once, its iterations added.  ``solver.amg`` reports ``tangent_setups``, ``fallbacks_coarse`` and
+    ``fallbacks_descent``).  Newton stops at ``||g|| <= max(rtol ||g(u_free = 0)||, atol)``, tested first in every
     iteration, or after ``max_newton`` iterations.  Inner solve: ``K_T d = -g`` from ``d = 0`` to ``||r|| <= eta_k ||g||``,
     ``eta_0 = eta_max``, ``eta_k = clamp(0.9 (||g_k|| / ||g_k-1||)^2, 1e-12, eta_max)``, at most ``cg_max_iter`` iterations
     (None = ``max(1000, 4 x free nodes)``), ``iters_per_graph`` per graph replay.  Line search: ``t = 1, 1/2, ...`` (at most
@@ -76,18 +91,20 @@ class _NewtonSolverBase:
     ``solve()`` starts from the current ``model.u_free``, writes the result into it in place and returns a ``NewtonInfo``.
     Coordinates, ``.grad`` of both parameters and the Dirichlet rows are never written.  Solver-owned fp64 buffers: an fp32
     model's rows are widened once per refresh and ``u_free`` is rounded once on write-back.  ``refresh()`` runs by itself
-    when the coordinate rows or ``u_fixed`` changed (``_version``, pointer, shape, dtype).  ``apply`` and ``diag`` are test
-    and measurement helpers."""
+    when the coordinate rows or ``u_fixed`` changed (``_version``, pointer, shape, dtype).  ``apply``, ``linear_solve`` and
+    ``diag`` are test and measurement helpers."""
 
     def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None,
                  precond: str = "block_jacobi", rtol: float = 1e-8, atol: float = 0.0, max_newton: int = 50,
                  cg_max_iter: Optional[int] = None, iters_per_graph: int = 16, eta_max: float = 0.1, armijo: float = 1e-4,
-                 max_backtracks: int = 30):
+                 max_backtracks: int = 30, amg_rebuild: str = "newton"):
         self._check_model(model, loss_fn)
-        if precond not in ("block_jacobi", "none", "amg"):
-            raise ValueError("precond must be 'block_jacobi', 'none' or 'amg'")
-        if precond == "amg" and int(model._idx_udir.shape[0]) == 0:
-            raise ValueError("precond='amg' needs Dirichlet rows: without them the small-strain operator is singular")
+        if precond not in ("block_jacobi", "none") + _AMG_PRECONDS:
+            raise ValueError("precond must be 'block_jacobi', 'none', 'amg' or 'amg_tangent'")
+        if precond in _AMG_PRECONDS and int(model._idx_udir.shape[0]) == 0:
+            raise ValueError(f"precond='{precond}' needs Dirichlet rows: without them the small-strain operator is singular")
+        if amg_rebuild not in ("newton", "solve"):
+            raise ValueError("amg_rebuild must be 'newton' or 'solve'")
         if int(iters_per_graph) < 1:
             raise ValueError("iters_per_graph must be >= 1")
         if rtol < 0 or atol < 0:
@@ -131,7 +148,11 @@ class _NewtonSolverBase:
         self._key = None
         self._tables = None
         self._rhs_norm = 0.0
-        self._amg = _AmgDevice(amg_host(model), dev, True) if precond == "amg" else None
+        self._amg = _AmgDevice(amg_host(model), dev, True) if precond in _AMG_PRECONDS else None
+        self.amg_rebuild = amg_rebuild
+        self._tangent = precond == "amg_tangent"
+        self._amg_kind = "small_strain"                # what the handle was last set up on ("tangent" / "small_strain")
+        self._tangent_setups = self._fallbacks_coarse = self._fallbacks_descent = 0
 
     def __del__(self):
         _lib.destroy_handle(self, "hfem_cg_destroy")
@@ -157,9 +178,8 @@ class _NewtonSolverBase:
                 te, tc = lf._traction(_Frozen(m, self._xf, self._xfix), self.t_force)
                 te = None if te is None else te.to(device=dev, dtype=F64).contiguous()
             self._tables = (self._body(), te, None if tc is None else (C.c_double * 4)(*tc), flags)
-            if self._amg is not None:
-                lam, mu = lf.lame
-                self._amg.setup(self._xf, self._xfix, (C.c_double * 4)(lam + 2 * mu, lam, lam + 2 * mu, mu), float(lf._W))
+            if self._amg is not None and not self._tangent:
+                self._small_strain_setup()
             self._energy(self._zero, self._gz)
             self._rhs_norm = float(torch.linalg.vector_norm(self._gz))
         self._key = self._state_key()
@@ -177,6 +197,22 @@ class _NewtonSolverBase:
             ptr(self._ufix) if self._ufix.numel() else None, self._lame, float(self.loss_fn._W),
             1 if self.precond == "block_jacobi" else 0, ptr(self.diag), ptr(self._info), stream_ptr(self.device)),
             "hfem_cg_setup_hyper")
+
+    def _small_strain_setup(self):
+        """The hierarchy of the small-strain operator at the current coordinates (physical convention): ``"amg"``'s numbers."""
+        lam, mu = self.loss_fn.lame
+        self._amg.setup(self._xf, self._xfix, (C.c_double * 4)(lam + 2 * mu, lam, lam + 2 * mu, mu), float(self.loss_fn._W))
+        self._amg_kind = "small_strain"
+
+    def _tangent_setup(self):
+        """The hierarchy of K_T at ``self._u``; safeguard (a): the small-strain one when its coarsest matrix is not positive
+        definite."""
+        self._tangent_setups += 1
+        if self._amg.setup_hyper(self._xf, self._xfix, self._u, self._ufix, self._lame, float(self.loss_fn._W)):
+            self._amg_kind = "tangent"
+        else:
+            self._fallbacks_coarse += 1
+            self._small_strain_setup()
 
     def _read_status(self):
         check(_lib.lib().hfem_cg_status(self._h, self._status, stream_ptr(self.device)), "hfem_cg_status")
@@ -213,20 +249,23 @@ class _NewtonSolverBase:
             torch.where(pd, a / det, torch.ones_like(a))
         return torch.stack([i00 * r[:, 0] + i01 * r[:, 1], i01 * r[:, 0] + i11 * r[:, 1]], dim=1)
 
-    def _inner(self, eta):
-        """self._delta = the truncated-PCG solution of K_T d = -g to the tolerance eta ||g||.  -> (iterations, reason)"""
+    def _pcg(self, eta, max_iter):
+        """The driver on K_T d = -self._g from d = 0 to ||r|| <= eta ||g||, into self._delta.  -> (iterations, reason)"""
         self._delta.zero_()
-        args = (ptr(self._g), ptr(self._g), float(eta), 0.0, self.cg_max_iter, stream_ptr(self.device))
+        args = (ptr(self._g), ptr(self._g), float(eta), 0.0, max_iter, stream_ptr(self.device))
         if self._amg is None:
             check(_lib.lib().hfem_cg_start(self._h, *args), "hfem_cg_start")
         else:
             check(_lib.lib().hfem_cg_start_amg(self._h, self._amg._h, *args), "hfem_cg_start_amg")
         st = self._read_status()
-        while not st[ST_HALTED] and st[ST_ITER] < self.cg_max_iter:
+        while not st[ST_HALTED] and st[ST_ITER] < max_iter:
             self._replay()
             st = self._read_status()
-        reason = _REASONS.get(int(st[ST_REASON]), "max_iter")
-        its = int(st[ST_ITER])
+        return int(st[ST_ITER]), _REASONS.get(int(st[ST_REASON]), "max_iter")
+
+    def _inner(self, eta):
+        """self._delta = the truncated-PCG solution of K_T d = -g to the tolerance eta ||g||.  -> (iterations, reason)"""
+        its, reason = self._pcg(eta, self.cg_max_iter)
         if reason == "breakdown" and its == 0:
             self._delta.copy_(-self._precondition(self._g))
         return its, reason
@@ -247,6 +286,7 @@ class _NewtonSolverBase:
                 return NewtonInfo(0, 0, gn, self._rhs_norm, energy, min_j, False, "inverted", hist)
             tol = max(self.rtol * self._rhs_norm, self.atol)
             k, cg_total, gn_prev, reason = 0, 0, None, ""
+            rebuild = self._tangent                          # amg_rebuild="solve": before the first inner solve only
             while True:
                 if gn <= tol:
                     reason = "rtol" if self.rtol * self._rhs_norm >= self.atol else "atol"
@@ -257,9 +297,18 @@ class _NewtonSolverBase:
                 if k > 0:
                     self._linearise()
                 eta = self.eta_max if gn_prev is None else min(max(0.9 * (gn / gn_prev) ** 2, 1e-12), self.eta_max)
+                if rebuild:
+                    self._tangent_setup()
+                    rebuild = self.amg_rebuild == "newton"
                 its, halt = self._inner(eta)
-                cg_total += its
                 gtd = float((self._g * self._delta).sum())
+                if self._tangent and self._amg_kind == "tangent" and not gtd < 0.0:
+                    self._fallbacks_descent += 1             # safeguard (b): an indefinite cycle gave no descent direction
+                    self._small_strain_setup()
+                    again, halt = self._inner(eta)
+                    its += again
+                    gtd = float((self._g * self._delta).sum())
+                cg_total += its
                 t, accepted = 1.0, False
                 for _ in range(self.max_backtracks + 1):
                     torch.add(self._u, self._delta, alpha=t, out=self._trial)
@@ -271,6 +320,8 @@ class _NewtonSolverBase:
                     t *= 0.5
                 hist.append(dict(energy=energy, grad_norm=gn, eta=eta, cg_iterations=its, cg_reason=halt,
                                  step=t if accepted else 0.0, min_J=mj_t if accepted else min_j))
+                if self._tangent:
+                    hist[-1]["amg"] = self._amg_kind
                 if not accepted:
                     reason = "line_search"
                     break
@@ -295,6 +346,34 @@ class _NewtonSolverBase:
         pq = torch.empty((), dtype=F64, device=self.device)
         check(_lib.lib().hfem_cg_apply(self._h, ptr(p), ptr(q), ptr(pq), stream_ptr(self.device)), "hfem_cg_apply")
         return q, pq
+
+    def linear_solve(self, b: torch.Tensor, rtol: float, max_iter: Optional[int] = None):
+        """``K_T d = b`` at the current ``model.u_free`` by the solver's own PCG from ``d = 0`` to ``||r|| <= rtol ||b||``:
+        re-linearises, builds the solver's preconditioner there (``"amg_tangent"``: a tangent setup with safeguard (a)) and
+        runs the driver.  ``b`` is fp64 ``[n_u, 2]`` in storage order.  -> ``(d, iterations, reason)``; a breakdown leaves
+        ``d`` where the driver stopped."""
+        self._fresh()
+        b = _lib.require_gpu_tensor(b.detach(), "b", F64)
+        with torch.no_grad():
+            self._u.copy_(self.model.u_free.detach())
+            self._linearise()
+            if self._tangent:
+                self._tangent_setup()
+            torch.neg(b, out=self._g)                        # the driver solves K d = -g0 with g0 = g_zero = -b
+            its, reason = self._pcg(rtol, self.cg_max_iter if max_iter is None else int(max_iter))
+            return self._delta.clone(), its, reason
+
+    @property
+    def amg(self):
+        """The AMG hierarchy's report (``_AmgDevice.report``; None without one); with ``precond="amg_tangent"`` also
+        ``tangent_setups`` (numeric setups on K_T), ``fallbacks_coarse`` and ``fallbacks_descent`` (safeguards (a), (b))."""
+        if self._amg is None:
+            return None
+        rep = self._amg.report()
+        if self._tangent:
+            rep.update(tangent_setups=self._tangent_setups, fallbacks_coarse=self._fallbacks_coarse,
+                       fallbacks_descent=self._fallbacks_descent, tangent_setup_seconds=self._amg.seconds_hyper)
+        return rep
 
     @property
     def info(self) -> torch.Tensor:
@@ -366,6 +445,32 @@ class Quad4NewtonKrylovSolver(_NewtonSolverBase):
             ptr(self._ufix) if self._ufix.numel() else None, self._lame, bq, ptr(te), tc, self._out.data_ptr(),
             self._out.data_ptr() + 8, ptr(self._work), None, ptr(g), flags, stream_ptr(self.device)),
             "hfem_quad4_hyper_energy_plan")
+
+
+def assemble_tangent(model, loss_fn) -> torch.Tensor:
+    """K_T,ff of the Neo-Hookean energy at the model's current ``u_free`` and coordinates: fp64 ``torch.sparse_bsr_tensor``
+    with 2x2 blocks over the free u rows in storage order (Dirichlet columns dropped; ``assemble_stiffness``'s pattern), from
+    the AMG tangent assembly kernel (one thread per row, bit-deterministic).  An inverted element or cell contributes zeros:
+    exactly the operator ``NewtonKrylovSolver.apply`` applies.  A TRI3 model under a ``NeoHookeanLoss2D`` or a QUAD4 model
+    under a ``Quad4NeoHookeanLoss2D``; fp32 models are widened on the way in."""
+    quad = getattr(model, "nodes_per_element", 3) == 4
+    if not isinstance(loss_fn, NeoHookeanLoss2D) or quad != isinstance(loss_fn, Quad4NeoHookeanLoss2D):
+        raise NotImplementedError("assemble_tangent: a TRI3 model under a NeoHookeanLoss2D or a QUAD4 model under a "
+                                  "Quad4NeoHookeanLoss2D (the stiffness of an EnergyLoss2D: assemble_stiffness)")
+    for name, t in (("node_coords_free", model.node_coords_free), ("u_free", model.u_free)):
+        _lib.require_gpu_tensor(t, name, dtype=None)
+    dev = model.u_free.device
+    host = amg_host(model)
+    a = _AmgDevice(host, dev, True)
+    rows = lambda t: t.detach().to(F64).contiguous()
+    a.assemble_hyper(rows(model.node_coords_free), rows(model.node_coords_fixed), rows(model.u_free), rows(model.u_fixed_rows()),
+                     (C.c_double * 2)(*loss_fn.lame), float(loss_fn._W))
+    vals = a.values(0, 0).view(-1, 2, 2).clone()
+    n = host.levels[0][0]
+    i64 = dict(dtype=torch.int64, device=dev)
+    crow = torch.as_tensor(host.array(0, 0), **i64)
+    col = torch.as_tensor(host.array(0, 1), **i64)
+    return torch.sparse_bsr_tensor(crow, col, vals, size=(2 * n, 2 * n))
 
 
 def newton_solve_(model, loss_fn, **kw) -> NewtonInfo:

@@ -364,6 +364,7 @@ class _AmgDevice:
         self.coarse = torch.empty((n * bs, n * bs), dtype=F64, device=device)
         self.coarse_inv = torch.empty_like(self.coarse)
         self.setups, self.seconds = 0, 0.0
+        self.setups_hyper, self.seconds_hyper = 0, 0.0   # setup_hyper: the tangent hierarchy on the same handle
 
     def __del__(self):
         _lib.destroy_handle(self, "hfem_amg_destroy")
@@ -384,6 +385,37 @@ class _AmgDevice:
         torch.cuda.synchronize(self.device)
         self.seconds = time.perf_counter() - t0
         self.setups += 1
+
+    def assemble_hyper(self, xf, xfix, u, ufix, lame, W):
+        """Level-0 A values = the Neo-Hookean tangent K_T,ff at the coordinates and the displacement rows."""
+        check(_lib.lib().hfem_amg_assemble_hyper(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, ptr(u),
+                                                 ptr(ufix) if ufix.numel() else None, lame, W, stream_ptr(self.device)),
+              "hfem_amg_assemble_hyper")
+
+    def setup_hyper(self, xf, xfix, u, ufix, lame, W) -> bool:
+        """``setup`` on the assembled Neo-Hookean tangent at ``u`` with the near-null space at the deformed position.  K_T can
+        be indefinite: the symmetrised coarsest matrix is Cholesky-factored, and when that fails (K_T has a non-positive
+        direction in the coarse space) no coarse inverse is bound and False is returned -- the caller sets the handle up again
+        (``setup``) before the next cycle."""
+        import time
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        check(_lib.lib().hfem_amg_setup_hyper(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, ptr(u),
+                                              ptr(ufix) if ufix.numel() else None, lame, W, ptr(self.coarse),
+                                              stream_ptr(self.device)), "hfem_amg_setup_hyper")
+        sym = 0.5 * (self.coarse + self.coarse.T)
+        ok = bool(torch.isfinite(sym).all())
+        if ok:
+            chol, info = torch.linalg.cholesky_ex(sym)
+            ok = int(info) == 0
+        if ok:
+            inv = torch.cholesky_inverse(chol)
+            self.coarse_inv.copy_(0.5 * (inv + inv.T))
+            check(_lib.lib().hfem_amg_set_coarse(self._h, ptr(self.coarse_inv)), "hfem_amg_set_coarse")
+        torch.cuda.synchronize(self.device)
+        self.seconds_hyper = time.perf_counter() - t0
+        self.setups_hyper += 1
+        return ok
 
     def values(self, level, which):
         """Device fp64 array ``which`` of a level (hfem_amg_values: 0 A blocks, 1 D^-1, 2 coefficients, 3 near-null space,

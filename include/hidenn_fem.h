@@ -848,7 +848,8 @@ int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, 
  *   host_info   level -1: {levels, n_u, ne, fan entries, host setup ns, npe, 0, 0}; level l: {block rows, block size, A block
  *               nnz, aggregates (0 on the coarsest), P block nnz, AP block nnz, 0, 0}
  *   host_copy   *n_out = length of an int32 array, copied into out when out != NULL.  level -1: which 0 fan_ptr, 1 fan
- *               element, 2 fan corner, 3 fan slots [.][npe]; level l: 0 A row_ptr, 1 A columns, 2 A diagonal slot, 3 aggregate
+ *               element, 2 fan corner, 3 fan slots [.][npe], 4 conn_u [ne][npe] (the u row code of every corner: u_src of the node);
+ *               level l: 0 A row_ptr, 1 A columns, 2 A diagonal slot, 3 aggregate
  *               of each row, 4 P row_ptr, 5 P columns, 6 R row_ptr, 7 R columns (fine rows), 8 R -> P block index,
  *               9 AP row_ptr, 10 AP columns
  * Device hierarchy (tri3_amg.hip, fp64), from a host setup (which may be destroyed afterwards):
@@ -863,6 +864,15 @@ int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, 
  *   values      *n_out = length of a device fp64 array of level `level`, copied (device to device) into out when out != NULL:
  *               which 0 A blocks, 1 D^-1 blocks, 2 coefficients {lambda_hat, 1/theta, c1, c2, omega, ., ., .}, 3 near-null
  *               space [rows][bs][3], 4 P_tent [rows][bs][3], 5 P blocks [bs][3]
+ * The same hierarchy on the assembled Neo-Hookean tangent K_T,ff at (x, u) (newton.py, precond="amg_tangent"):
+ *   assemble_hyper  level-0 A values = K_T,ff at the coordinates and the displacement rows u_free [n_u][2] / u_fixed (fp64;
+ *               lame, W as hfem_cg_setup_hyper; QUAD4: W is not read).  The same walk, the element tangent of the hyper CG
+ *               kernels; an inverted element or cell contributes zeros, so the matrix is exactly the operator hfem_cg_apply
+ *               applies on a hyper handle.  Bit-deterministic.
+ *   setup_hyper hfem_amg_setup with that assembly and with the fine near-null space at the deformed position (rotation
+ *               column (-(y + v), x + u)).  K_T may be indefinite: the caller checks the coarsest matrix before it inverts it.
+ * One handle may be set up by either entry point, in any order.  Pointers and patterns never change, only values: a captured
+ * hfem_cg_iterate_amg graph stays valid across re-setups of either kind.
  * PCG with the V-cycle: cg_start_amg / cg_iterate_amg replace hfem_cg_start / hfem_cg_iterate (same status record, same
  * halting; hfem_cg_setup still binds the coordinates).  Four launch groups per iteration: apply, vector update, V-cycle,
  * r^T z.                                                                                                                */
@@ -880,6 +890,10 @@ int hfem_amg_destroy(hfem_amg *amg);
 int hfem_amg_assemble(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W, void *stream);
 int hfem_amg_setup(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W,
                    double *coarse_out, void *stream);
+int hfem_amg_assemble_hyper(hfem_amg *amg, const double *x_free, const double *x_fixed, const double *u_free,
+                            const double *u_fixed, const double lame[2], double W, void *stream);
+int hfem_amg_setup_hyper(hfem_amg *amg, const double *x_free, const double *x_fixed, const double *u_free,
+                         const double *u_fixed, const double lame[2], double W, double *coarse_out, void *stream);
 int hfem_amg_set_coarse(hfem_amg *amg, const double *coarse_inv);
 int hfem_amg_vcycle(hfem_amg *amg, const double *r, double *z, void *stream);
 int hfem_amg_values(hfem_amg *amg, int32_t level, int32_t which, double *out, int64_t *n_out, void *stream);

@@ -23,7 +23,17 @@ buffers: hfem_cg_apply on the QUAD4 tangent (csrc/quad4_hyper_cg.hip), hfem_quad
 the launches on ``csrc/build.py --tag recompute --define HFEM_QUAD4_TANGENT_RECOMPUTE``'s library (the apply that calls log1p
 instead of reading the c_q its diag launch stored) and writes newton_timing_Q1M_recompute.json: the A/B pair of DESIGN 20.
 
+``--precond amg_tangent``: the AMG hierarchy of the assembled tangent instead of the two records above, written
+to newton_amg_tangent_{T1M,Q1M}.json.  `setup`: the numeric setup of the tangent hierarchy (hfem_amg_setup_hyper) against the
+small-strain one (hfem_amg_setup) on the SAME handle, alternating, device events around each call (launches only: the dense
+coarsest factorisation is the host's and is timed apart, as ``_AmgDevice`` reports it), median of 7, at T1M / at Q1M with the
+left edge clamped (the hierarchy needs Dirichlet rows), 0.3 x the test field.  `ramp`: the 8-step load ramp of example 4's
+plates from u = 0, every increment from the last equilibrium, for ``"amg"`` against ``"amg_tangent"`` with
+``amg_rebuild="newton"`` and ``"solve"`` (``--amg-rebuild`` picks one), up to the largest load that keeps min J > 0.3: Newton
+iterations, CG iterations, milliseconds (device events around ``solve()``) and the fallback counts per increment.
+
     python scripts/newton_timing.py [--quad] [--reps 2000] [--out-dir profiles/newton] [--small] [--lib-tag TAG] [--launches-only]
+                                    [--precond amg_tangent [--amg-rebuild newton|solve]]
 """
 import argparse
 import json
@@ -177,6 +187,98 @@ def increment(nx, ny, load_steps=8, lbfgs_steps=100, E=10e9, nu=0.3, quad=False)
     return rec
 
 
+def amg_setup_times(nx, ny, quad=False, windows=7):
+    """Device-event medians of hfem_amg_setup_hyper against hfem_amg_setup on one handle, alternating."""
+    import ctypes as C
+    from hidenn_fem_amd._lib import check, ptr, stream_ptr
+    dev = torch.device("cuda:0")
+    mesher = structured_quad_mesh if quad else structured_tri_mesh
+    coords, conn, geom, bc, _, edges = mesher(nx, ny, length=2.0, height=2.0 if quad else 1.0, jitter=0.2, seed=0, dtype=F64)
+    u = 0.3 * field(coords)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=u[bc], neumann_edges=edges)
+    with torch.no_grad():
+        m.u_free.copy_(m.from_caller_order(u[~bc], "u"))
+    m = m.to(dev)
+    lf = (Quad4NeoHookeanLoss2D if quad else NeoHookeanLoss2D)(device=dev, dtype=F64)
+    s = (Quad4NewtonKrylovSolver if quad else NewtonKrylovSolver)(m, lf, precond="amg_tangent")
+    s._fresh()
+    s._u.copy_(m.u_free.detach())
+    s._linearise()
+    a, L, st = s._amg, _lib.lib(), stream_ptr(dev)
+    lam, mu = lf.lame
+    mat, W = (C.c_double * 4)(lam + 2 * mu, lam, lam + 2 * mu, mu), float(lf._W)
+    fixed = lambda t: ptr(t) if t.numel() else None
+
+    def tangent():
+        check(L.hfem_amg_setup_hyper(a._h, ptr(s._xf), fixed(s._xfix), ptr(s._u), fixed(s._ufix), s._lame, W, ptr(a.coarse), st),
+              "hfem_amg_setup_hyper")
+
+    def small():
+        check(L.hfem_amg_setup(a._h, ptr(s._xf), fixed(s._xfix), mat, W, ptr(a.coarse), st), "hfem_amg_setup")
+
+    fns = dict(tangent=tangent, small_strain=small)
+    for f in fns.values():
+        f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, f in fns.items():
+            t[k].append(window_us(f, 3))
+    ok = s._amg.setup_hyper(s._xf, s._xfix, s._u, s._ufix, s._lame, W)      # with the host's Cholesky: wall seconds
+    s._small_strain_setup()
+    rep = s.amg
+    rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4 on [0, 2]^2' if quad else 'TRI3'}, jitter 0.2, left edge clamped, 0.3 x field",
+               n_elems=m.Nelems, n_u_rows=int(m.u_free.shape[0]), min_J=s.info[0].item(), levels=rep["levels"], rows=rep["rows"],
+               operator_complexity=rep["operator_complexity"], coarse_positive_definite=bool(ok), windows=windows,
+               calls_per_window=3, wall_seconds_with_coarse_factorisation=dict(tangent=a.seconds_hyper, small_strain=a.seconds))
+    for k in fns:
+        rec[k] = dict(us=sorted(t[k])[len(t[k]) // 2], windows_us=t[k])
+    rec["ratio_tangent_over_small_strain"] = rec["tangent"]["us"] / rec["small_strain"]["us"]
+    return rec
+
+
+def amg_ramp(nx, ny, quad=False, load_steps=8, E=10e9, nu=0.3, configs=None, min_j_floor=0.3):
+    """Example 4's Neo-Hookean ramp from u = 0, every increment from the last equilibrium, per preconditioner configuration."""
+    dev = torch.device("cuda:0")
+    holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
+    sides = {"up": 0, "down": 0, "right": 2, "left": 1}
+    if quad:
+        nodes, conn, geom, bc, _, edges = structured_quad_mesh(nx, ny, length=2.0, height=1.0, boundaries=sides)
+    else:
+        nodes, conn, geom, bc, _, edges = generate_mesh(2.0, 1.0, holes, sides, nx, ny)
+    lf = (Quad4NeoHookeanLoss2D if quad else NeoHookeanLoss2D)(E=E, nu=nu, length=2.0, height=1.0, device=dev, dtype=F64)
+    solver = Quad4NewtonKrylovSolver if quad else NewtonKrylovSolver
+    tr = lambda scale: (lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -scale * E / 500.0)], dim=1))
+    rec = dict(mesh=f"example 4 QUAD4 plate (no holes), {nx}x{ny} nodes" if quad else f"example 4 plate with holes, {nx}x{ny}",
+               load_steps=load_steps, min_J_floor=min_j_floor, runs={})
+    for pc, rebuild in configs or (("amg", None), ("amg_tangent", "newton"), ("amg_tangent", "solve")):
+        m = PiecewiseLinearShapeNN2D(nodes.to(F64), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
+                                     neumann_edges=edges).to(dev)
+        m.node_coords_free.requires_grad_(False)
+        s = solver(m, lf, precond=pc, **({} if rebuild is None else dict(amg_rebuild=rebuild)))
+        rows = []
+        for k in range(1, load_steps + 1):
+            s.t_force = tr(k / load_steps)
+            s.refresh()
+            before = dict(s.amg)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            info = s.solve()
+            b.record()
+            torch.cuda.synchronize()
+            if not info.converged or info.min_J <= min_j_floor:
+                rows.append(dict(load=k / load_steps, stopped=info.reason, min_J=info.min_J))
+                break
+            row = dict(load=k / load_steps, newton_iterations=info.newton_iterations, cg_iterations=info.cg_iterations,
+                       ms=a.elapsed_time(b), min_J=info.min_J, cg_per_newton=[h["cg_iterations"] for h in info.history])
+            if pc == "amg_tangent":
+                after = s.amg
+                row.update({key: after[key] - before[key] for key in ("tangent_setups", "fallbacks_coarse", "fallbacks_descent")})
+            rows.append(row)
+        rec["runs"][pc if rebuild is None else f"{pc}/{rebuild}"] = rows
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=2000)
@@ -185,11 +287,20 @@ def main():
     ap.add_argument("--quad", action="store_true", help="Q1M and example 4's QUAD4 plate: the QUAD4 tangent (DESIGN 20)")
     ap.add_argument("--lib-tag", default="", help="run on csrc/libhidenn_hip_<tag>.so (csrc/build.py --tag: an A/B build)")
     ap.add_argument("--launches-only", action="store_true", help="skip the load increment")
+    ap.add_argument("--precond", choices=["amg_tangent"], default=None,
+                    help="amg_tangent: measure the AMG hierarchy of the assembled tangent instead (DESIGN 21)")
+    ap.add_argument("--amg-rebuild", choices=["newton", "solve"], default=None,
+                    help="with --precond amg_tangent: only this rebuild setting in the ramp (default: both, beside 'amg')")
     a = ap.parse_args()
     big = not a.small
     if a.lib_tag:
         _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libhidenn_hip_{a.lib_tag}.so")
-    if a.launches_only:
+    if a.precond == "amg_tangent":
+        cfg = None if a.amg_rebuild is None else (("amg", None), ("amg_tangent", a.amg_rebuild))
+        rec = dict(setup=amg_setup_times(*(((1001, 1001) if a.quad else (1001, 501)) if big else ((101, 101) if a.quad else (101, 51))),
+                                         quad=a.quad),
+                   ramp=amg_ramp(*((200, 100) if big else (60, 30)), quad=a.quad, configs=cfg))
+    elif a.launches_only:
         rec = dict(launches=launches(*(((1001, 1001) if a.quad else (1001, 501)) if big else ((101, 101) if a.quad else (101, 51))),
                                      a.reps, quad=a.quad))
     elif a.quad:
@@ -204,6 +315,8 @@ def main():
     if a.out_dir:
         os.makedirs(a.out_dir, exist_ok=True)
         name = ("newton_timing_Q1M" if a.quad else "newton_timing_T1M") if big else "newton_timing_small"
+        if a.precond == "amg_tangent":
+            name = ("newton_amg_tangent_Q1M" if a.quad else "newton_amg_tangent_T1M") if big else "newton_amg_tangent_small"
         with open(os.path.join(a.out_dir, name + (f"_{a.lib_tag}" if a.lib_tag else "") + ".json"), "w") as f:
             f.write(line + "\n")
 
