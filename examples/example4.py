@@ -131,7 +131,7 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
 
 
 def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3, newton=False,
-                    precond="block_jacobi", quad=False):
+                    precond="block_jacobi", quad=False, r_adapt=False, outer=10):
     """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
     clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
     of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
@@ -147,7 +147,13 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     halved like an inverted one.
     ``quad=True`` (``--quad``): the same ramp on the plate without the holes as ``nx x ny`` nodes of bilinear QUAD4 cells
     (``structured_quad_mesh``), with ``Quad4NeoHookeanLoss2D``; with ``newton=True`` every increment is solved by
-    ``Quad4NewtonKrylovSolver``."""
+    ``Quad4NewtonKrylovSolver``.
+    ``r_adapt=True`` (``--r-adapt``): the Newton ramp to the full load as above (``newton`` is implied), then ``outer``
+    iterations of the finite-strain r-adaptive solve there (``hidenn_fem_amd.radapt.r_adapt_``: ``HyperRAdaptiveSolver`` /
+    ``Quad4HyperRAdaptiveSolver`` -- Newton-Krylov with ``precond`` for ``u``, coordinate steps bounded so that neither an
+    element nor its ``det F`` collapses); prints energy, min J, min q and the Newton / CG counts per outer iteration and the
+    energy gained over the frozen mesh, and returns the r-adapted energy."""
+    newton = newton or r_adapt
     from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
     from hidenn_fem_amd.solve import solve_displacement_
@@ -233,7 +239,34 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
             gap = (model.u_free.detach() - u_lin).abs().max().item() / u_lin.abs().max().item()
             print(f"load {target:.4f}: gap to the linear frozen-mesh solution max|u - u_lin| / max|u_lin| = {gap:.3e}")
             first = False
+    if r_adapt:
+        if done < 1.0 - 1e-12:
+            raise RuntimeError(f"example 4: the load ramp stopped at {done:.4f}; no r-adaptation below the full load")
+        return _r_adapt_neo_hookean(model, loss_fn, traction(1.0), outer, precond)
     return model, energy
+
+
+def _r_adapt_neo_hookean(model, loss_fn, t_force, outer, precond):
+    import time
+    from hidenn_fem_amd.radapt import mesh_quality, quad4_mesh_quality, r_adapt_
+    quality = quad4_mesh_quality if getattr(model, "nodes_per_element", 3) == 4 else mesh_quality
+    model.node_coords_free.requires_grad_(True)                    # the ramp froze the mesh
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = r_adapt_(model, loss_fn, t_force=t_force, max_outer=outer, precond=precond)     # (Quad4)HyperRAdaptiveSolver
+    torch.cuda.synchronize()
+    print(f"frozen-mesh energy {info.energy[0]:.9e} min J {info.min_J[0]:.4f} min q {info.min_q[0]:.4f} "
+          f"(Newton {info.newton_iterations[0]} CG {info.cg_iterations[0]})")
+    for k in range(1, info.iterations + 1):
+        print(f"outer {k:3d}: energy {info.energy[k]:.9e} min J {info.min_J[k]:.4f} min q {info.min_q[k]:.4f} "
+              f"|g_x|inf {info.grad_inf[k]:.3e} alpha {info.alpha[k]:.3e} (max {info.alpha_max[k]:.3e}) "
+              f"Newton {info.newton_iterations[k]} CG {info.cg_iterations[k]}")
+    mq = quality(model)
+    gain = info.energy[0] - info.energy[-1]
+    print(f"r-adapted energy {info.energy[-1]:.9e} after {info.iterations} outer iterations ({info.reason}), "
+          f"min J {info.min_J[-1]:.4f}, min q {mq.min_q:.4f}, inverted elements {mq.n_inverted}, {time.perf_counter() - t0:.3f} s")
+    print(f"energy gained over the frozen mesh {gain:.6e} ({gain / abs(info.energy[0]):.3e} of |Pi*|)")
+    return model, info.energy[-1]
 
 
 def _print_error(model, loss_fn, when, recovery=None):
@@ -281,8 +314,9 @@ if __name__ == "__main__":
     ap.add_argument("--sharded", action="store_true", help="owner-sharded energy + node-sharded L-BFGS (one process per GPU)")
     ap.add_argument("--solve-first", action="store_true", help="start L-BFGS from the frozen-mesh displacement solve (CG)")
     ap.add_argument("--r-adapt", action="store_true",
-                    help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS")
-    ap.add_argument("--outer", type=int, default=20, help="outer iterations of --r-adapt")
+                    help="alternating r-adaptive solve (frozen-mesh CG, inversion-safe coordinate steps) instead of L-BFGS; "
+                         "with --neo-hookean: the finite-strain one at the full load (Newton-Krylov, det F-safe steps)")
+    ap.add_argument("--outer", type=int, default=None, help="outer iterations of --r-adapt (default 20; with --neo-hookean: 10)")
     ap.add_argument("--quad", action="store_true",
                     help="with --r-adapt or --neo-hookean: the plate as nx x ny nodes of QUAD4 cells (no holes)")
     ap.add_argument("--precond", choices=["block_jacobi", "amg", "amg_tangent"], default="block_jacobi",
@@ -297,11 +331,12 @@ if __name__ == "__main__":
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
     a = ap.parse_args()
-    if a.precond == "amg_tangent" and not (a.neo_hookean and a.newton):
-        ap.error("--precond amg_tangent needs --neo-hookean --newton (with or without --quad)")
+    if a.precond == "amg_tangent" and not (a.neo_hookean and (a.newton or a.r_adapt)):
+        ap.error("--precond amg_tangent needs --neo-hookean with --newton or --r-adapt (with or without --quad)")
     if a.neo_hookean:
-        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad)
+        run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad,
+                        r_adapt=a.r_adapt, outer=a.outer or 10)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
-        solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer,
+        solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,
         precond=a.precond, quad=a.quad, error_estimate=a.error_estimate)

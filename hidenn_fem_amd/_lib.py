@@ -164,6 +164,10 @@ PROTOTYPES = {
     "hfem_quad4_mesh_measure": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_quad4_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_quad4_quality_barrier": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp]),
+    "hfem_tri3_hyper_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_tri3_deformation_measure": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hfem_quad4_hyper_step_bound": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_quad4_deformation_measure": (C.c_int, [C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_amg_host_create": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.POINTER(_vp)]),
     "hfem_amg_host_create_ex": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, C.POINTER(_vp)]),
     "hfem_amg_host_destroy": (C.c_int, [_vp]),
@@ -187,7 +191,9 @@ PROTOTYPES = {
 _F32_TWINS = ["hfem_grid_param_fwd", "hfem_grid_param_bwd", "hfem_grid_param_fwd_ws", "hfem_grid_param_bwd_ws",
               "hfem_line2_eval_fwd", "hfem_line2_eval_bwd", "hfem_bar_energy", "hfem_line2_mse", "hfem_rectq4_eval_fwd",
               "hfem_rectq4_eval_bwd", "hfem_rectq4_mse", "hfem_tri3_mesh_measure", "hfem_tri3_step_bound",
-              "hfem_tri3_quality_barrier", "hfem_quad4_mesh_measure", "hfem_quad4_step_bound", "hfem_quad4_quality_barrier"]
+              "hfem_tri3_quality_barrier", "hfem_quad4_mesh_measure", "hfem_quad4_step_bound", "hfem_quad4_quality_barrier",
+              "hfem_tri3_hyper_step_bound", "hfem_tri3_deformation_measure", "hfem_quad4_hyper_step_bound",
+              "hfem_quad4_deformation_measure"]
 PROTOTYPES.update({name + "_f32": PROTOTYPES[name] for name in _F32_TWINS})
 
 _lib = None

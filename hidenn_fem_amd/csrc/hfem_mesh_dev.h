@@ -1,13 +1,15 @@
-// What the mesh-validity kernels of the two element kinds share (tri3_mesh.hip, quad4_mesh.hip): coordinate rows through the
-// x row map, the monotone keys and the filtered atomic min of the deterministic reductions, the closed form of the step
-// bound's first crossing, and the one-thread init / finish launches around a reduction.  Everything has internal linkage:
-// each of the two translation units carries its own instance.
+// What the mesh-validity kernels of the two element kinds share (tri3_mesh.hip, quad4_mesh.hip and their finite-strain
+// siblings tri3_hyper_mesh.hip, quad4_hyper_mesh.hip): coordinate rows through the x row map, the monotone keys and the
+// filtered atomic min of the deterministic reductions, the closed form of the step bound's first crossing
+// (hfem_crossing_dev.h), and the one-thread init / finish launches around a reduction.  Everything has internal linkage:
+// each translation unit carries its own instance.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "hfem_crossing_dev.h"
 #include "hfem_device.h"
 
 namespace hfem {
@@ -92,23 +94,32 @@ __device__ __forceinline__ void mesh_measure_reduce(unsigned long long kq, unsig
     }
 }
 
-// ---------------------------------------------------------------- step bound
-// Smallest a > 0 with c + b a + a2 a^2 = 0, where c = (1 - eta) A0 > 0 after normalising by sign(A0) (+inf: none).  p(0) = c
-// > 0, so a positive root exists iff b < 0 (then the smaller positive root is c / qq, qq = (-b + sqrt(disc)) / 2, stable for
-// any a2 including 0 -- the linear case -c / b) or a2 < 0 (b >= 0: the positive root is qq / a2, qq = -(b + sqrt(disc)) / 2).
-// disc < 0 (only with a2 > 0): p never reaches 0.  The double root (disc = 0) is returned: there detJ touches eta detJ(0).
-__device__ __forceinline__ double first_crossing(double A0, double A1, double A2, double eta) {
-    if (A0 == 0.0) return 0.0;                               // degenerate already: no step keeps a share of nothing
-    const double sg = A0 > 0.0 ? 1.0 : -1.0;
-    const double c = (1.0 - eta) * A0 * sg, b = A1 * sg, a2 = A2 * sg;
-    const double disc = b * b - 4.0 * a2 * c;
-    if (disc < 0.0) return INFINITY;
-    const double sq = sqrt(disc);
-    if (b < 0.0) return c / (0.5 * (sq - b));
-    if (a2 < 0.0) return (-0.5 * (b + sq)) / a2;
-    return INFINITY;
+// summary of the deformation measure (tri3_hyper_mesh.hip, quad4_hyper_mesh.hip; u64 words while it runs): {key(min J),
+// count of elements with J <= 0 or NaN}
+__global__ void deformation_measure_init_kernel(unsigned long long *summary) {
+    summary[0] = ~0ull;
+    summary[1] = 0ull;
 }
 
+__global__ void deformation_measure_finish_kernel(unsigned long long *summary) {
+    double *out = reinterpret_cast<double *>(summary);
+    const double j = dkey_value(summary[0]);
+    const double n = (double)summary[1];
+    out[0] = j;
+    out[1] = n;
+}
+
+__device__ __forceinline__ void deformation_measure_reduce(unsigned long long kj, unsigned inv, unsigned long long *red,
+                                                           unsigned long long *summary) {
+    const unsigned long long bj = block_min_u64(kj, red);
+    const unsigned long long binv = (unsigned long long)__syncthreads_count(inv);
+    if (threadIdx.x == 0) {
+        atomic_min_filtered(summary, bj);
+        if (binv) __hip_atomic_fetch_add(summary + 1, binv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---------------------------------------------------------------- step bound (first_crossing(): hfem_crossing_dev.h)
 __global__ void step_bound_init_kernel(double *alpha) { alpha[0] = INFINITY; }
 
 inline unsigned mesh_blocks(int64_t ne) { return (unsigned)((ne + kMeshBlock - 1) / kMeshBlock); }

@@ -23,6 +23,15 @@ Each function and class takes one element kind: ``RAdaptiveSolver``, ``mesh_qual
 TRI3 models, ``Quad4RAdaptiveSolver``, ``quad4_mesh_quality``, ``quad4_max_feasible_step``, ``quad4_quality_barrier`` QUAD4
 models; ``r_adapt_`` takes either.  The outer loop, the line search and the stopping rules are one piece of code
 (``_RAdaptBase``).  Coordinate rows fp64 or fp32 (fp64 inside the kernels), any storage row order (``reorder``).
+
+Finite strain (``NeoHookeanLoss2D`` / ``Quad4NeoHookeanLoss2D``): ``HyperRAdaptiveSolver`` and
+``Quad4HyperRAdaptiveSolver`` run the same loop with ``newton.NewtonKrylovSolver`` / ``Quad4NewtonKrylovSolver`` as the
+displacement solve.  There the quantity that must not collapse is ``det F = detJ(X + u) / detJ(X)``, and a coordinate step at
+fixed nodal ``u`` moves numerator and denominator: a trial that keeps the reference area can still drive ``det F`` to zero
+and the energy to ``+inf``.  ``csrc/tri3_hyper_mesh.hip`` / ``csrc/quad4_hyper_mesh.hip`` hold the guard: the step bound that
+also stops at the first step with ``det F(a) = eta det F(0)`` (an exact quadratic as well; ``hyper_max_feasible_step``,
+``quad4_hyper_max_feasible_step``) and the deformation measure ``J`` (``deformation_measure``,
+``quad4_deformation_measure``).
 """
 from __future__ import annotations
 
@@ -34,6 +43,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dev_index, ptr, stream_ptr
+from .loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
 
 F64 = torch.float64
 
@@ -135,6 +145,64 @@ class _QuadMesh(_Mesh):
     measure_f32_trials = True
 
 
+class _HyperRows:
+    """What the finite-strain mesh kernels read besides the coordinates (``csrc/tri3_hyper_mesh.hip``,
+    ``csrc/quad4_hyper_mesh.hip``): the u row map and the model's CURRENT ``u_free`` and ``u_fixed_rows()``.  Mixed into a mesh
+    class, it replaces the step bound by the det F-safe one and adds the deformation measure; fp32 trials are measured for both
+    element kinds."""
+
+    measure_f32_trials = True
+
+    def __init__(self, model):
+        super().__init__(model)
+        if model.u_free.dtype != self.dtype or model.u_free.device != self.device:
+            raise RuntimeError(f"hidenn_fem_amd.radapt: u_free must have the dtype and device of node_coords_free "
+                               f"({self.dtype}, {self.device}), got {model.u_free.dtype}, {model.u_free.device}")
+        self.u_src = torch.from_numpy(model._u_src).to(self.device)
+
+    def _u_rows(self):
+        uf = self.model.u_free.detach().contiguous()
+        ufix = self.model.u_fixed_rows().detach().to(device=self.device, dtype=self.dtype).contiguous()
+        return (uf if uf.numel() else None), (ufix if ufix.numel() else None)
+
+    def step_bound(self, d, eta, out=None):
+        """0-d fp64 device tensor: the largest step along ``d`` (fp64 [n_x, 2], storage order) at fixed ``u`` that keeps every
+        element's (QUAD4: corner's) ``detJ`` and ``det F`` at or above ``eta`` times their current values."""
+        dev = self.device
+        out = torch.empty((), dtype=F64, device=dev) if out is None else out
+        xf = self.model.node_coords_free.detach()
+        xfix = self.fixed()
+        uf, ufix = self._u_rows()
+        self._call("hyper_step_bound", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
+                   ptr(self.u_src), ptr(uf), ptr(ufix), ptr(d), float(eta), ptr(out), stream_ptr(dev))
+        return out
+
+    def deformation(self, per_element=True):
+        """(J [Ne] or None, summary [2] fp64 device = {min J, number of elements with J <= 0 or NaN}) at the current rows."""
+        dev = self.device
+        j = torch.empty(self.ne, dtype=F64, device=dev) if per_element else None
+        summary = torch.empty(2, dtype=F64, device=dev)
+        xf = self.model.node_coords_free.detach()
+        xfix = self.fixed()
+        uf, ufix = self._u_rows()
+        self._call("deformation_measure", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
+                   ptr(self.u_src), ptr(uf), ptr(ufix), ptr(j), ptr(summary), stream_ptr(dev))
+        return j, summary
+
+    def deformation_measure(self):
+        j, s = self.deformation()
+        s = s.tolist()
+        return DeformationMeasure(J=j, min_J=s[0], n_inverted=int(s[1]))
+
+
+class _HyperMesh(_HyperRows, _Mesh):
+    other = "QUAD4 models: quad4_hyper_max_feasible_step, quad4_deformation_measure, Quad4HyperRAdaptiveSolver"
+
+
+class _QuadHyperMesh(_HyperRows, _QuadMesh):
+    other = "TRI3 models: hyper_max_feasible_step, deformation_measure, HyperRAdaptiveSolver"
+
+
 @dataclass
 class MeshQuality:
     """Element measure against the model's ``initial_node_coords``.  ``q`` [Ne]: signed mean-ratio quality (1 = equilateral,
@@ -197,6 +265,50 @@ def quad4_quality_barrier(model, weight: float = 1.0):
 
 
 @dataclass
+class DeformationMeasure:
+    """Deformation measure of the model's current coordinates and displacements.  ``J`` [Ne] fp64 on the device, elements in
+    the caller's order: ``det F = detJ(X + u) / detJ(X)`` of a TRI3 element, the smallest corner ratio ``c_k^def / c_k`` of a
+    QUAD4 cell (``det F`` at any point of the cell is a positively weighted mean of the four).  ``min_J``: its minimum;
+    ``n_inverted``: the number of elements with ``J <= 0`` or NaN."""
+    J: torch.Tensor
+    min_J: float
+    n_inverted: int
+
+
+def hyper_max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool = False):
+    """``max_feasible_step`` at finite strain: the largest ``alpha`` such that moving the free coordinate rows by ``alpha * d``
+    AT FIXED NODAL ``u`` (the model's current ``u_free`` and ``u_fixed_rows()``) keeps every element's ``detJ`` and its
+    ``det F = detJ(X + u) / detJ(X)`` at or above ``eta`` times their current values (``+inf`` if no step along ``d`` gets
+    there, 0 if an element is invalid already).  No Neo-Hookean energy is ``+inf`` below it.  Same arguments and return types."""
+    _HyperMesh.require(model, "hyper_max_feasible_step")
+    _check_eta(eta)
+    return _HyperMesh(model).feasible_step(d, eta, as_tensor)
+
+
+def quad4_hyper_max_feasible_step(model, d: torch.Tensor, eta: float = 0.25, as_tensor: bool = False):
+    """``hyper_max_feasible_step`` for a QUAD4 model, per corner: below it every corner cross product of the reference cell and
+    every corner ratio ``c_k^def / c_k`` keep ``eta`` of their values, so ``det F`` at every point of a cell -- every Gauss
+    point -- stays at or above ``eta`` times the cell's smallest corner ratio before the step."""
+    _QuadHyperMesh.require(model, "quad4_hyper_max_feasible_step")
+    _check_eta(eta)
+    return _QuadHyperMesh(model).feasible_step(d, eta, as_tensor)
+
+
+def deformation_measure(model) -> DeformationMeasure:
+    """Per-element ``det F`` of a TRI3 model's current state, its minimum and the number of elements with ``det F <= 0`` (one
+    measure launch; the summary is reduced on the device, deterministically)."""
+    _HyperMesh.require(model, "deformation_measure")
+    return _HyperMesh(model).deformation_measure()
+
+
+def quad4_deformation_measure(model) -> DeformationMeasure:
+    """``deformation_measure`` for a QUAD4 model: per cell the smallest corner ratio.  (``Quad4NeoHookeanLoss2D.info`` reports
+    the minimum over the Gauss points instead, which is never below it.)"""
+    _QuadHyperMesh.require(model, "quad4_deformation_measure")
+    return _QuadHyperMesh(model).deformation_measure()
+
+
+@dataclass
 class RAdaptInfo:
     """Outcome of ``RAdaptiveSolver.run()`` / ``Quad4RAdaptiveSolver.run()``, one entry per outer iteration (entry 0: the
     frozen-mesh solve at the start).
@@ -226,9 +338,12 @@ class RAdaptInfo:
 class _RAdaptBase:
     """The alternating loop both element kinds share: argument checks, the pieces of an outer iteration, the L-BFGS direction,
     the line search and ``run``.  A subclass names its mesh class (``_mesh_cls``: which models it takes and which mesh kernels
-    run) and its displacement solver (``_solver_cls()``), and may refuse more in ``_check``."""
+    run) and its displacement solver (``_solver_cls()``), and may refuse more in ``_check``.  The finite-strain classes
+    (``_HyperRAdaptBase``) also replace ``solve_and_grad`` and the small hooks ``_step_start`` / ``_trial_share`` /
+    ``_step_extra`` / ``_record_extra`` / ``_solve_failed``, which do nothing more here than the loop always did."""
 
     _mesh_cls = None
+    _info_cls = RAdaptInfo
 
     @staticmethod
     def _solver_cls():
@@ -237,6 +352,10 @@ class _RAdaptBase:
     @classmethod
     def _check(cls, model, loss_fn):
         cls._mesh_cls.require(model, cls.__name__)
+        if isinstance(loss_fn, NeoHookeanLoss2D):
+            raise NotImplementedError(f"{cls.__name__}: small-strain linear elasticity only (its frozen-mesh solve would "
+                                      "linearise a NeoHookeanLoss2D silently); finite strain: HyperRAdaptiveSolver (TRI3) / "
+                                      "Quad4HyperRAdaptiveSolver (QUAD4), or r_adapt_, which picks the class")
         if getattr(loss_fn, "deterministic", False):
             raise NotImplementedError(f"{cls.__name__}: EnergyLoss2D(deterministic=True) has no solver counterpart "
                                       "(the CG matrix-vector product accumulates with LDS atomics)")
@@ -246,9 +365,18 @@ class _RAdaptBase:
                  gtol: float = 1e-9, ftol: float = 1e-12, max_outer: int = 50, max_ls: int = 20, c1: float = 1e-4,
                  max_restarts: int = 5, cg_precond: str = "block_jacobi"):
         self._check(model, loss_fn)
+        if int(max_restarts) < 0:
+            raise ValueError("max_restarts must be >= 0")
+        self._setup(model, loss_fn, b_force, t_force, history, eta, quality_weight, gtol, ftol, max_outer, max_ls, c1)
+        self.max_restarts = int(max_restarts)
+        self.solver = self._solver_cls()(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol,
+                                         precond=cg_precond)
+
+    def _setup(self, model, loss_fn, b_force, t_force, history, eta, quality_weight, gtol, ftol, max_outer, max_ls, c1):
+        """Everything of ``__init__`` after ``_check`` but the displacement solver."""
         _check_eta(eta)
-        if int(history) < 0 or int(max_outer) < 0 or int(max_ls) < 1 or int(max_restarts) < 0:
-            raise ValueError("history, max_outer and max_restarts must be >= 0, max_ls >= 1")
+        if int(history) < 0 or int(max_outer) < 0 or int(max_ls) < 1:
+            raise ValueError("history and max_outer must be >= 0, max_ls >= 1")
         if not (0.0 < c1 < 1.0):
             raise ValueError("c1 must be in (0, 1)")
         if not (quality_weight >= 0.0 and math.isfinite(quality_weight)):
@@ -259,9 +387,6 @@ class _RAdaptBase:
         self.model, self.loss_fn, self.b_force, self.t_force = model, loss_fn, b_force, t_force
         self.history, self.eta, self.quality_weight = int(history), float(eta), float(quality_weight)
         self.gtol, self.ftol, self.max_outer, self.max_ls, self.c1 = float(gtol), float(ftol), int(max_outer), int(max_ls), float(c1)
-        self.max_restarts = int(max_restarts)
-        self.solver = self._solver_cls()(model, loss_fn, b_force=b_force, t_force=t_force, rtol=cg_rtol,
-                                         precond=cg_precond)
         self.last_solve = None                                 # SolveInfo of the latest displacement solve
         x0 = model.initial_node_coords.detach().double()
         self.length = float((x0.max(dim=0).values - x0.min(dim=0).values).norm()) if x0.numel() else 1.0
@@ -329,10 +454,29 @@ class _RAdaptBase:
             q = q + (a - b) * s
         return q
 
-    def _line_search(self, x0, d, f0, gd, alpha_init, coords0=None):
+    def _step_start(self):
+        """What ``_trial_share`` and ``_step_extra`` need of ``x_k`` besides its coordinates (taken before the rows move)."""
+        return None
+
+    def _trial_share(self, coords0, start) -> float:
+        """The smallest share the rows as stored keep of what the step bound protects, against ``x_k`` (``coords0``)."""
+        return float(self.mesh.measure(x_ref=coords0, per_element=False)[2][1].item())
+
+    def _step_extra(self, start):
+        """What a subclass records of an accepted step besides ``step_ratio`` (before ``u`` is solved again)."""
+        return None
+
+    def _record_extra(self, info, extra):
+        pass
+
+    def _solve_failed(self) -> bool:
+        """The latest displacement solve left a state the outer loop must not continue from."""
+        return False
+
+    def _line_search(self, x0, d, f0, gd, alpha_init, coords0=None, start=None):
         """Backtracking Armijo along ``d`` from the rows ``x0`` (fp64 flat).  Returns (accepted alpha or None, alpha_max, f, trials);
-        on failure ``node_coords_free`` holds ``x0`` again.  fp32 rows of a mesh class with ``measure_f32_trials`` (QUAD4;
-        ``coords0`` is ``x0`` by node id): the step bound
+        on failure ``node_coords_free`` holds ``x0`` again.  fp32 rows of a mesh class with ``measure_f32_trials`` (QUAD4 and
+        the finite-strain classes; ``coords0`` is ``x0`` by node id, ``start`` is ``_step_start()`` there): the step bound
         holds for ``x0 + alpha d``, the rows hold that rounded, and on an element that earlier steps shrank to the spacing of
         the float grid the rounding moves ``detJ`` by more than the 0.9 margin leaves.  So each trial is measured against
         ``coords0`` first, and one that keeps less than ``eta`` is halved like one that fails the Armijo test (it counts as
@@ -347,7 +491,7 @@ class _RAdaptBase:
         for t in range(self.max_ls):
             with torch.no_grad():
                 xf.copy_((x0 + alpha * d).reshape(xf.shape))   # rounds once for fp32 rows
-            kept = not measured or float(self.mesh.measure(x_ref=coords0, per_element=False)[2][1].item()) >= self.eta
+            kept = not measured or self._trial_share(coords0, start) >= self.eta
             f = self.objective() if kept else math.inf
             if math.isfinite(f) and f <= f0 + self.c1 * alpha * gd:
                 return alpha, amax, f, t + 1
@@ -357,12 +501,12 @@ class _RAdaptBase:
         return None, amax, f0, self.max_ls
 
     def run(self) -> RAdaptInfo:
-        m, info = self.model, RAdaptInfo()
+        m, info = self.model, self._info_cls()
         xf = m.node_coords_free
         e, f, g, cg_iters = self.solve_and_grad()
         gscale = max(abs(f), 1e-300) / self.length
 
-        def record(e, f, g, alpha, amax, cg_iters, step_ratio, trials):
+        def record(e, f, g, alpha, amax, cg_iters, step_ratio, trials, extra=None):
             _, _, s = self.mesh.measure(per_element=False)
             info.energy.append(e)
             info.objective.append(f)
@@ -373,10 +517,14 @@ class _RAdaptBase:
             info.min_q.append(float(s[0].item()))
             info.step_ratio.append(step_ratio)
             info.trials.append(trials)
+            self._record_extra(info, extra)
 
         record(e, f, g, 0.0, math.nan, cg_iters, math.nan, 0)
         pairs, last = [], None                                 # curvature pairs (s, y, 1 / s^T y); the latest pair for BB
         while True:
+            if self._solve_failed():
+                info.reason = "newton"
+                break
             if info.grad_inf[-1] <= self.gtol * gscale:
                 info.reason = "gtol"
                 break
@@ -386,6 +534,7 @@ class _RAdaptBase:
             x0 = xf.detach().to(F64).reshape(-1).clone()
             with torch.no_grad():
                 coords0 = m.coords.to(self.mesh.dtype).contiguous()     # x_k by node id: the reference of the step ratio
+            start = self._step_start()
             step = None
             for use_pairs in ([True, False] if pairs else [False]):   # L-BFGS direction, then once the steepest descent
                 d = self._direction(g, pairs if use_pairs else [])
@@ -399,7 +548,7 @@ class _RAdaptBase:
                     alpha_init = float(torch.dot(last[0], last[0]).item()) / sy if sy > 0.0 else math.inf
                 else:
                     alpha_init = math.inf
-                alpha, amax, _, trials = self._line_search(x0, d, f, gd, alpha_init, coords0)
+                alpha, amax, _, trials = self._line_search(x0, d, f, gd, alpha_init, coords0, start)
                 if alpha is not None:
                     step = (alpha, amax, trials)
                     break
@@ -415,6 +564,7 @@ class _RAdaptBase:
                 break
             _, ratio, _ = self.mesh.measure(x_ref=coords0)
             step_ratio = float(ratio.min().item()) if ratio.numel() else math.nan
+            extra = self._step_extra(start)
             e1, f1, g1, cg_iters = self.solve_and_grad()
             s, y = x1 - x0, g1 - g
             sy = float(torch.dot(s, y).item())
@@ -423,7 +573,7 @@ class _RAdaptBase:
                 if self.history > 0:
                     pairs.append((s, y, 1.0 / sy))
                     pairs = pairs[-self.history:]
-            record(e1, f1, g1, step[0], step[1], cg_iters, step_ratio, step[2])
+            record(e1, f1, g1, step[0], step[1], cg_iters, step_ratio, step[2], extra)
             f_old, f, g = f, f1, g1
             if f_old - f1 <= self.ftol * max(abs(f_old), abs(f1), 1.0):
                 info.reason = "ftol"
@@ -485,8 +635,135 @@ class Quad4RAdaptiveSolver(_RAdaptBase):
                                       "on the tile plan)")
 
 
+@dataclass
+class HyperRAdaptInfo(RAdaptInfo):
+    """``RAdaptInfo`` of ``HyperRAdaptiveSolver.run()`` / ``Quad4HyperRAdaptiveSolver.run()``.  ``cg_iterations`` is the CG total
+    of the entry's Newton solve; added per entry: ``newton_iterations``; ``min_J``, the smallest ``det F`` of the solved state
+    as the Newton solve reports it (QUAD4: over the Gauss points); ``J_step_ratio``, the smallest ``J(x_k) / J(x_k-1)`` over
+    the elements at the ``u`` the step was taken at, ``J`` from the deformation measure (>= ``eta`` by construction; nan at
+    entry 0).  One more ``reason``: ``"newton"`` -- a Newton solve ended unconverged; the state is kept (it is valid, and its
+    energy is not above the line search's)."""
+    newton_iterations: List[int] = field(default_factory=list)
+    min_J: List[float] = field(default_factory=list)
+    J_step_ratio: List[float] = field(default_factory=list)
+
+
+class _HyperRAdaptBase(_RAdaptBase):
+    """``_RAdaptBase``'s loop at finite strain: what differs is the displacement solve (Newton-Krylov, no restart
+    loop: Newton tests the true gradient), the step bound (the mesh class's det F-safe one), what an fp32 trial is measured
+    for (the reference ratio AND the ``J`` ratio against ``x_k``) and the record (``HyperRAdaptInfo``)."""
+
+    _info_cls = HyperRAdaptInfo
+    _loss_cls, _wrong_loss, _sibling = NeoHookeanLoss2D, (), ""
+
+    @classmethod
+    def _check(cls, model, loss_fn):
+        name, npe = cls.__name__, cls._mesh_cls.npe
+        if not isinstance(loss_fn, NeoHookeanLoss2D):
+            linear = "Quad4RAdaptiveSolver" if npe == 4 else "RAdaptiveSolver"
+            raise NotImplementedError(f"{name}: {cls._loss_cls.__name__} only (an EnergyLoss2D is quadratic in u_free: "
+                                      f"{linear} alternates with the frozen-mesh PCG solve; r_adapt_ picks the class)")
+        if getattr(model, "nodes_per_element", 3) != npe or not isinstance(loss_fn, cls._loss_cls) \
+                or isinstance(loss_fn, cls._wrong_loss):
+            raise NotImplementedError(f"{name}: {cls._mesh_cls.kind} models under a {cls._loss_cls.__name__} only "
+                                      f"({cls._sibling}; r_adapt_ picks the class)")
+
+    def __init__(self, model, loss_fn, b_force: Optional[Callable] = None, t_force: Optional[Callable] = None, *,
+                 history: int = 10, eta: float = 0.25, quality_weight: float = 0.0, precond: str = "block_jacobi",
+                 newton_rtol: float = 1e-8, newton_kw: Optional[dict] = None, gtol: float = 1e-9, ftol: float = 1e-12,
+                 max_outer: int = 50, max_ls: int = 20, c1: float = 1e-4):
+        self._check(model, loss_fn)
+        self._setup(model, loss_fn, b_force, t_force, history, eta, quality_weight, gtol, ftol, max_outer, max_ls, c1)
+        self.solver = self._solver_cls()(model, loss_fn, b_force=b_force, t_force=t_force, precond=precond, rtol=newton_rtol,
+                                         **(newton_kw or {}))
+
+    def solve_and_grad(self):
+        """Newton-Krylov from the current ``u`` at the current coordinates (the solver refreshes itself when they moved), then
+        ``objective_and_grad()``.  Returns (E, E + Q, g, CG iterations of the Newton solve)."""
+        sol = self.last_solve = self.solver.solve()
+        if sol.reason == "inverted":
+            raise RuntimeError(f"{type(self).__name__}: the starting state is inverted (min_J = {sol.min_J!r}): no coordinate "
+                               "step is safe from it -- ramp the load to a valid equilibrium first")
+        e, f, g = self.objective_and_grad()
+        return e, f, g, sol.cg_iterations
+
+    def _solve_failed(self):
+        return not self.last_solve.converged
+
+    def _step_start(self):
+        return self.mesh.deformation()[0]                       # J per element at (x_k, u_k)
+
+    def _j_ratio(self, start) -> float:
+        j = self.mesh.deformation()[0]
+        return float((j / start).min().item()) if j.numel() else math.inf
+
+    def _trial_share(self, coords0, start):
+        return min(super()._trial_share(coords0, start), self._j_ratio(start))
+
+    def _step_extra(self, start):
+        return self._j_ratio(start)
+
+    def _record_extra(self, info, extra):
+        info.newton_iterations.append(self.last_solve.newton_iterations)
+        info.min_J.append(self.last_solve.min_J)
+        info.J_step_ratio.append(math.nan if extra is None else extra)
+
+
+class HyperRAdaptiveSolver(_HyperRAdaptBase):
+    """Alternating r-adaptive minimisation of the Neo-Hookean potential of a TRI3 model over ``u_free`` and
+    ``node_coords_free``: ``RAdaptiveSolver``'s outer loop, L-BFGS direction, line search and stopping rules (one piece of
+    code), with four differences.
+
+    (1) The displacement solve is ``NewtonKrylovSolver``, warm-started from ``u_k``; it refreshes itself when the coordinates
+    moved.  ``precond`` is its ``precond`` (``"block_jacobi"``, ``"none"``, ``"amg"``, ``"amg_tangent"``), ``newton_rtol`` its
+    ``rtol``, ``newton_kw`` further keywords.  There is no restart loop: Newton tests the true gradient.  (2) The step bound is
+    the finite-strain one (``hyper_max_feasible_step``): below it every element keeps ``eta`` of its ``detJ`` and of its
+    ``det F`` at the fixed ``u_k``, so no trial energy is ``+inf``.  (3) fp32 rows: each rounded trial is measured against
+    ``x_k`` with the mesh measure and the deformation measure and halved while either ratio is below ``eta``.  (4) ``run()``
+    returns a ``HyperRAdaptInfo``.
+
+    Every accepted Newton step passes an Armijo test on the energy, so the descent argument of the small-strain loop holds
+    and the recorded objectives fall monotonically even where the tangent is indefinite; ``Pi*`` is then the energy of the
+    LOCAL minimum Newton reaches from ``u_k``, no more.  A start with ``det F <= 0`` somewhere raises ``RuntimeError`` (it names
+    ``min_J``); a Newton solve that ends unconverged after an accepted step stops the run with ``reason="newton"`` and keeps
+    that state.  Only ``node_coords_free`` and ``u_free`` change.  Refuses an ``EnergyLoss2D`` (``RAdaptiveSolver``) and QUAD4
+    models or losses (``Quad4HyperRAdaptiveSolver``)."""
+
+    _mesh_cls = _HyperMesh
+    _wrong_loss = Quad4NeoHookeanLoss2D
+    _sibling = "QUAD4 models under a Quad4NeoHookeanLoss2D: Quad4HyperRAdaptiveSolver"
+
+    @staticmethod
+    def _solver_cls():
+        from .newton import NewtonKrylovSolver
+        return NewtonKrylovSolver
+
+
+class Quad4HyperRAdaptiveSolver(_HyperRAdaptBase):
+    """``HyperRAdaptiveSolver`` for QUAD4 models under a ``Quad4NeoHookeanLoss2D``: the same arguments, loop and
+    ``HyperRAdaptInfo``.  The displacement solve is ``Quad4NewtonKrylovSolver``; the step bound and the deformation measure are
+    the corner-wise kernels of ``csrc/quad4_hyper_mesh.hip``: a step keeps ``eta`` of every corner cross product and of every
+    corner ratio ``c_k^def / c_k``, so ``det F`` at every Gauss point stays at or above ``eta`` times the cell's smallest corner
+    ratio before the step; ``J_step_ratio`` is taken on the cells' smallest corner ratios.  Refuses an ``EnergyLoss2D``
+    (``Quad4RAdaptiveSolver``) and TRI3 models or losses (``HyperRAdaptiveSolver``)."""
+
+    _mesh_cls = _QuadHyperMesh
+    _loss_cls = Quad4NeoHookeanLoss2D
+    _sibling = "TRI3 models under a NeoHookeanLoss2D: HyperRAdaptiveSolver"
+
+    @staticmethod
+    def _solver_cls():
+        from .newton import Quad4NewtonKrylovSolver
+        return Quad4NewtonKrylovSolver
+
+
 def r_adapt_(model, loss_fn, **kw) -> RAdaptInfo:
-    """One-shot ``RAdaptiveSolver(model, loss_fn, **kw).run()`` -- ``Quad4RAdaptiveSolver`` for a QUAD4 model:
+    """One-shot ``RAdaptiveSolver(model, loss_fn, **kw).run()`` -- ``Quad4RAdaptiveSolver`` for a QUAD4 model, and for a
+    ``NeoHookeanLoss2D`` the finite-strain classes ``HyperRAdaptiveSolver`` / ``Quad4HyperRAdaptiveSolver``:
     ``model.node_coords_free`` and ``model.u_free`` are r-adapted in place."""
-    cls = Quad4RAdaptiveSolver if getattr(model, "nodes_per_element", 3) == 4 else RAdaptiveSolver
+    quad = getattr(model, "nodes_per_element", 3) == 4
+    if isinstance(loss_fn, NeoHookeanLoss2D):
+        cls = Quad4HyperRAdaptiveSolver if quad else HyperRAdaptiveSolver
+    else:
+        cls = Quad4RAdaptiveSolver if quad else RAdaptiveSolver
     return cls(model, loss_fn, **kw).run()

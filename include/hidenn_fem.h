@@ -837,6 +837,46 @@ int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, 
                                    const float *x_fixed, const float *x_ref, double weight, double *value_acc,
                                    double *grad_acc, void *stream);
 
+/* ------------------------------------------------------------------ mesh validity for r-adaptivity at finite strain
+ * The det F-safe step bound and the deformation measure (csrc/tri3_hyper_mesh.hip, csrc/quad4_hyper_mesh.hip;
+ * HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver in hidenn_fem_amd/radapt.py).  The argument lists of the step_bound entry
+ * points above plus the displacement rows after the coordinate rows: u_src [nn] the u row map (>= 0: row of u_free, < 0: row
+ * -1 - u_src of u_fixed, the Dirichlet rows), u_free, u_fixed in the row type of the coordinates (either may be NULL when no
+ * node maps to it, not both).  A coordinate step at fixed nodal u moves R(a) = detJ(X + a d) and D(a) = detJ(X + u + a d), and
+ * det F(a) = D(a) / R(a).
+ *   hyper_step_bound      alpha_out [1] (device) = the smallest alpha > 0 at which some element has R(alpha) = eta R(0) or
+ *                         det F(alpha) = eta det F(0) (exact quadratics; +inf if there is none, 0 when some element has
+ *                         R(0) D(0) <= 0 or NaN).  QUAD4: per corner, on the cross products c_k and c_k^def; below the bound
+ *                         det F at every point of a cell stays at or above eta times the cell's smallest corner ratio
+ *                         r_k = c_k^def / c_k before the step.  Deterministic; launch-only.
+ *   deformation_measure   j_out [ne] (may be NULL) = det F of the element (QUAD4: min_k r_k); summary_out [2] (device) =
+ *                         {min J, number of elements with J <= 0 or NaN}.  Deterministic.
+ * Errors as for the entry points above: null pointers, ne outside [0, 2^31), eta outside (0, 1).                          */
+int hfem_tri3_hyper_step_bound(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                               const double *x_fixed, const int32_t *u_src, const double *u_free, const double *u_fixed,
+                               const double *d, double eta, double *alpha_out, void *stream);
+int hfem_tri3_hyper_step_bound_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                   const float *x_fixed, const int32_t *u_src, const float *u_free, const float *u_fixed,
+                                   const double *d, double eta, double *alpha_out, void *stream);
+int hfem_tri3_deformation_measure(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                                  const double *x_fixed, const int32_t *u_src, const double *u_free, const double *u_fixed,
+                                  double *j_out, double *summary_out, void *stream);
+int hfem_tri3_deformation_measure_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                      const float *x_fixed, const int32_t *u_src, const float *u_free, const float *u_fixed,
+                                      double *j_out, double *summary_out, void *stream);
+int hfem_quad4_hyper_step_bound(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                                const double *x_fixed, const int32_t *u_src, const double *u_free, const double *u_fixed,
+                                const double *d, double eta, double *alpha_out, void *stream);
+int hfem_quad4_hyper_step_bound_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                    const float *x_fixed, const int32_t *u_src, const float *u_free, const float *u_fixed,
+                                    const double *d, double eta, double *alpha_out, void *stream);
+int hfem_quad4_deformation_measure(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const double *x_free,
+                                   const double *x_fixed, const int32_t *u_src, const double *u_free, const double *u_fixed,
+                                   double *j_out, double *summary_out, void *stream);
+int hfem_quad4_deformation_measure_f32(int device, const int32_t *conn, int64_t ne, const int32_t *x_src, const float *x_free,
+                                       const float *x_fixed, const int32_t *u_src, const float *u_free, const float *u_fixed,
+                                       double *j_out, double *summary_out, void *stream);
+
 /* ------------------------------------------------------------------ smoothed-aggregation AMG for the frozen-mesh solve
  * A symmetric V-cycle of smoothed aggregation over K_ff in 2x2 node blocks (hidenn_fem_amd/solve.py, precond="amg").
  * Host setup (amg.cpp, no GPU), once per mesh topology: conn [ne][npe] int32 (host_create: npe = 3, TRI3; host_create_ex: npe

@@ -13,8 +13,21 @@ Records, as one JSON object:
     Pi* before and after, reason, min q, wall time (--quad: the plate without holes, 200 x 100 nodes of QUAD4 cells).
 Cache regime: the working sets stay in the 256 MB Infinity Cache.
 
+--neo-hookean [--quad]: the finite-strain guard (HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver, csrc/tri3_hyper_mesh.hip,
+csrc/quad4_hyper_mesh.hip) on the same meshes, at a smooth displacement field with min J about 0.5:
+  * the fused det F-safe bound launch (init + element kernel);
+  * the composition available without it -- the torch add that forms X + u on the coordinate rows, `hfem_*_step_bound` on X
+    and on X + u, and the minimum of the two (the rows of u gathered onto the coordinate rows beforehand, not timed).  It
+    bounds detJ(X) and detJ(X + u) separately, which is the weaker guarantee: det F = detJ(X + u) / detJ(X) keeps eta of its
+    value only where the reference element does not grow along the step;
+  * the deformation measure launch, without and with the per-element output;
+  * --outer N outer iterations of the finite-strain solver under a downward traction (E = 2e6, --precond for Newton):
+    per iteration the Newton solve and everything else (host clock), and the share spent outside Newton (0 skips this).
+
     python scripts/radapt_timing.py [--grid 1001x501] [--reps 200] [--out profiles/radapt/radapt_timing_T1M.json]
     python scripts/radapt_timing.py --quad [--grid 1415x708] [--out profiles/radapt/radapt_timing_quad4_T1M.json]
+    python scripts/radapt_timing.py --neo-hookean [--quad] [--outer 3] [--precond amg]
+                                    [--out profiles/radapt/hyper_radapt_timing_T1M.json | ..._Q1M.json]
 """
 import argparse
 import json
@@ -87,15 +100,107 @@ class Clock:
         return r
 
 
+def smooth_field(x):
+    """A finite-strain displacement field on [0, 2] x [0, 1] (min det F about 0.5 on these meshes)."""
+    return torch.stack([0.15 * torch.sin(2.1 * x[:, 0]) * torch.cos(1.3 * x[:, 1]),
+                        0.09 * torch.cos(1.7 * x[:, 0] + 0.3) * torch.sin(2.4 * x[:, 1])], dim=1)
+
+
+def main_neo_hookean(a, dev, nx, ny):
+    from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
+    from hidenn_fem_amd.radapt import HyperRAdaptiveSolver, Quad4HyperRAdaptiveSolver, _Mesh, _QuadMesh
+    mesher, Solver, Loss, Small = (structured_quad_mesh, Quad4HyperRAdaptiveSolver, Quad4NeoHookeanLoss2D, _QuadMesh) if a.quad \
+        else (structured_tri_mesh, HyperRAdaptiveSolver, NeoHookeanLoss2D, _Mesh)
+    coords, conn, geom, bc, mn, edges = mesher(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    torch.manual_seed(0)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(dev)
+    U = smooth_field(coords)
+    with torch.no_grad():
+        m.u_free.copy_(m.from_caller_order(U[~bc], "u").to(dev))
+    m.u_fixed = U[bc].to(dev)
+    lf = Loss(E=2e6, device=dev, dtype=F64)
+    down = lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -a.traction)], dim=1)
+    ne, nn = m.Nelems, m.Nnodes
+    rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=ne, n_nodes=nn,
+               n_x_rows=int(m.node_coords_free.shape[0]),
+               regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
+    s = Solver(m, lf, t_force=down, max_outer=a.outer, precond=a.precond)
+    mesh, small = s.mesh, Small(m)
+    j, summary = mesh.deformation()
+    rec["state"] = dict(min_J=summary[0].item(), n_inverted=int(summary[1].item()), max_J=j.max().item())
+    d = torch.randn(m.node_coords_free.shape, dtype=F64, device=dev) * 1e-3
+    alpha = torch.empty((), dtype=F64, device=dev)
+    fused_us = graphed_us(lambda: mesh.step_bound(d, 0.25, out=alpha), a.reps)
+    alg = 4 * conn.shape[1] * ne + (4 + 4 + 16 + 16 + 16) * nn
+    rec["fused_bound"] = dict(us=fused_us, launches=2, alpha=alpha.item(), algorithmic_bytes=alg, tb_per_s=alg / fused_us * 1e-6,
+                              note=f"{4 * conn.shape[1]} B/element of connectivity + per node: x_src, u_src 4 B each, x, u, d rows 16 B each")
+
+    # ---- the composition: X + u on the coordinate rows, the small-strain bound on X and on X + u
+    u_full = m.u_full.detach()
+    xf, xfix = m.node_coords_free.detach(), mesh.fixed()
+    u_on_x = u_full[m._idx_free.long()].contiguous()
+    yfix = None if xfix is None else (xfix + u_full[m._idx_fixed.long()]).contiguous()
+    y = torch.empty_like(xf)
+    a2 = torch.empty(2, dtype=F64, device=dev)
+    both = torch.empty((), dtype=F64, device=dev)
+    from hidenn_fem_amd._lib import dev_index, ptr, stream_ptr
+
+    def composed():
+        torch.add(xf, u_on_x, out=y)
+        for k, (rows, fixed) in enumerate(((xf, xfix), (y, yfix))):
+            small._call("step_bound", dev_index(dev), ptr(small.conn), small.ne, ptr(small.x_src), ptr(rows), ptr(fixed), ptr(d), 0.25,
+                        a2.data_ptr() + 8 * k, stream_ptr(dev))
+        torch.amin(a2, dim=0, out=both)
+
+    composed_us = graphed_us(composed, a.reps)
+    rec["composed_bound"] = dict(us=composed_us, launches=6, alpha=both.item(),
+                                 note="torch add + 2 x (init + element kernel) + amin; bounds detJ(X) and detJ(X + u) separately")
+    rec["fused_over_composed"] = fused_us / composed_us
+    rec["measure"] = dict(us=graphed_us(lambda: mesh.deformation(per_element=False), a.reps), launches=3)
+    rec["measure_per_element_output"] = dict(us=graphed_us(lambda: mesh.deformation(per_element=True), a.reps))
+
+    # ---- outer iterations from u = 0 under the traction: Newton vs everything else
+    if a.outer > 0:
+        with torch.no_grad():
+            m.u_free.zero_()
+        m.u_fixed = torch.zeros_like(m.u_fixed)
+        m.__dict__.pop("_ufix_cache", None)
+        solve_clock = Clock(s.solver.solve)
+        s.solver.solve = solve_clock
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = s.run()
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        rec["outer"] = dict(iterations=info.iterations, reason=info.reason, precond=a.precond, traction=a.traction,
+                            newton_iterations=info.newton_iterations, cg_iterations=info.cg_iterations, energy=info.energy,
+                            min_J=info.min_J, min_q=info.min_q, alpha=info.alpha, alpha_max=info.alpha_max, trials=info.trials,
+                            step_ratio=info.step_ratio, J_step_ratio=info.J_step_ratio, seconds_total=total,
+                            seconds_newton=solve_clock.total, seconds_other=total - solve_clock.total,
+                            share_outside_newton=(total - solve_clock.total) / total)
+    line = json.dumps(rec)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", default="")
     ap.add_argument("--quad", action="store_true", help="QUAD4 cells (default grid 1415x708: 10^6 cells)")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default="")
+    ap.add_argument("--neo-hookean", action="store_true", help="the finite-strain guard and solver (module docstring)")
+    ap.add_argument("--outer", type=int, default=3, help="--neo-hookean: outer iterations to time (0: none)")
+    ap.add_argument("--precond", default="amg", help="--neo-hookean: Newton's preconditioner")
+    ap.add_argument("--traction", type=float, default=2e4, help="--neo-hookean: the downward traction on the right edge")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     nx, ny = (int(v) for v in (a.grid or ("1415x708" if a.quad else "1001x501")).split("x"))
+    if a.neo_hookean:
+        return main_neo_hookean(a, dev, nx, ny)
     mesher, Solver, quality = (structured_quad_mesh, Quad4RAdaptiveSolver, quad4_mesh_quality) if a.quad else \
         (structured_tri_mesh, RAdaptiveSolver, mesh_quality)
     coords, conn, geom, bc, mn, edges = mesher(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)

@@ -1,0 +1,453 @@
+"""r-adaptive solve at finite strain (hidenn_fem_amd/radapt.py HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver,
+csrc/tri3_hyper_mesh.hip, csrc/quad4_hyper_mesh.hip): the det F-safe step bound and the deformation measure against the numpy
+closed forms of tests/test_hyper_radapt_host.py, the reduced coordinate gradient against a central difference with Newton
+re-solved on each side, the alternating run's contract (monotone objective, no element and no det F collapses, Newton's
+gradient at the end, untouched rows and .grad), dispatch and refusals, and example 4's --neo-hookean --r-adapt path.
+
+Meshes: those of test_gpu_radapt.py and test_gpu_radapt_quad4.py -- the jittered structured 61 x 41 mesh with the rows as
+given and tile-major, with fp32 rows, the Delaunay mesh (about 6,000 elements) and, for QUAD4 off structured numbering, the
+Delaunay mesh split into cells (valence 1..11).  The displacement is 0.6 x the finite-strain test field of
+tests/hyper_reference.py plus nodal noise of 3 % of the smallest element size, on every node (the Dirichlet rows carry it too):
+0.3 < min J < 0.9 on every mesh, asserted on the CPU reference and on the device."""
+import math
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import hyper_reference as H
+import newton_reference as N
+import quad4_hyper_reference as Q
+from test_gpu_radapt import _caller_rows, _plate as _tri_plate, _structured, _unstructured
+from test_gpu_radapt_quad4 import _plate as _quad_plate
+from test_gpu_solve_quad4 import _model as _quad_model
+from test_hyper_radapt_host import (det_f_np, hyper_step_bound_np, kind_of, quad4_corner_ratios_np,
+                                    quad4_hyper_step_bound_np)
+
+pytestmark = pytest.mark.gpu
+F64, F32 = torch.float64, torch.float32
+DEV = torch.device("cuda:0")
+
+
+def _split_model():
+    from test_gpu_quad4_shapes import _mesh
+    from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+    nc, conn, geom, bc, mn, edges = _mesh("T")[0]
+    torch.manual_seed(0)
+    return PiecewiseLinearShapeNN2D(nc, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(DEV)
+
+
+MESHES = {
+    "tri_off": lambda: _structured("off"), "tri_tile": lambda: _structured("tile"),
+    "tri_delaunay": lambda: _unstructured(n=3000), "tri_f32": lambda: _structured("auto", dtype=F32),
+    "quad_off": lambda: _quad_model(nx=61, ny=41, reorder="off"), "quad_tile": lambda: _quad_model(nx=61, ny=41, reorder="tile"),
+    "quad_f32": lambda: _quad_model(nx=61, ny=41, dtype=F32), "quad_split": _split_model,
+}
+
+
+def _is_quad(m):
+    return getattr(m, "nodes_per_element", 3) == 4
+
+
+def _field(m, scale=0.6, noise=0.03, seed=11):
+    """[Nn, 2] fp64 by node id: scale x H.field + uniform noise of +-noise x (the square root of the smallest element area)."""
+    nc = m.initial_node_coords.double().cpu()
+    P = nc.numpy()[m.connectivity.cpu().numpy()]
+    cr = lambda a, b: a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    h = math.sqrt(np.abs(cr(P[:, 1] - P[:, 0], P[:, -1] - P[:, 0])).min())
+    g = torch.Generator().manual_seed(seed)
+    return scale * H.field(nc) + noise * h * (2.0 * torch.rand(nc.shape, generator=g, dtype=F64) - 1.0)
+
+
+def _set_u(m, U):
+    """Write the rows U [Nn, 2] (by node id) into the model: the free rows into ``u_free``, the Dirichlet rows into ``u_fixed``."""
+    bc = m.dirichlet_mask.cpu()
+    with torch.no_grad():
+        m.u_free.copy_(m.from_caller_order(U[~bc].to(m.dtype), "u").to(DEV))
+    m.u_fixed = U[bc].to(device=DEV, dtype=m.dtype)
+    m.__dict__.pop("_ufix_cache", None)
+    return m
+
+
+def _u_rows(m):
+    """[Nn, 2] fp64 by node id: the displacement rows as the kernels see them (fp32 rows widened)."""
+    with torch.no_grad():
+        return m.u_full.detach().double().cpu().numpy()
+
+
+def _j_np(m, X=None):
+    conn = m.connectivity.cpu().numpy()
+    X = _caller_rows(m) if X is None else X
+    U = _u_rows(m)
+    return quad4_corner_ratios_np(X[conn], U[conn]).min(axis=1) if _is_quad(m) else det_f_np(X[conn], U[conn])
+
+
+def _deformed(which):
+    from hidenn_fem_amd.radapt import deformation_measure, quad4_deformation_measure
+    m = MESHES[which]()
+    _set_u(m, _field(m))
+    j = _j_np(m)
+    assert 0.3 < j.min() < 0.9, (which, j.min())                     # the CPU reference ...
+    conn, nc, U = m.connectivity.cpu(), torch.as_tensor(_caller_rows(m)), torch.as_tensor(_u_rows(m))
+    if _is_quad(m):
+        assert 0.3 < Q.total(nc, U, conn, *Q.lame())["min_J"] < 0.9
+    else:
+        assert abs(H.total(nc, U, conn, *H.lame(), H.tri_W())["min_J"] - j.min()) <= 1e-13
+    dm = (quad4_deformation_measure if _is_quad(m) else deformation_measure)(m)
+    assert 0.3 < dm.min_J < 0.9 and dm.n_inverted == 0, (which, dm.min_J)       # ... and the device, before use
+    return m
+
+
+def _step(m):
+    from hidenn_fem_amd import radapt
+    return radapt.quad4_hyper_max_feasible_step if _is_quad(m) else radapt.hyper_max_feasible_step
+
+
+def _ref_bound(m, d, eta):
+    conn = m.connectivity.cpu().numpy()
+    X, D, U = _caller_rows(m), _caller_rows(m, d), _u_rows(m)
+    fn = quad4_hyper_step_bound_np if _is_quad(m) else hyper_step_bound_np
+    a, ref, dfc, _, _ = fn(X[conn], U[conn], D[conn], eta)
+    return a.min(), kind_of(ref.min(), dfc.min()), X, D, U, conn
+
+
+def _landed(m, X, D, U, conn, alpha):
+    """min(min_e R_e(alpha) / R_e(0), min_e J_e(alpha) / J_e(0)); QUAD4: both per corner."""
+    Y = X + alpha * D
+    if _is_quad(m):
+        from test_radapt_quad4_host import quad4_corners_np
+        r = quad4_corners_np(Y[conn])[0] / quad4_corners_np(X[conn])[0]
+        j = quad4_corner_ratios_np(Y[conn], U[conn]) / quad4_corner_ratios_np(X[conn], U[conn])
+    else:
+        det = lambda T: (T[:, 0, 0] - T[:, 2, 0]) * (T[:, 1, 1] - T[:, 2, 1]) - (T[:, 1, 0] - T[:, 2, 0]) * (T[:, 0, 1] - T[:, 2, 1])
+        r = det(Y[conn]) / det(X[conn])
+        j = det_f_np(Y[conn], U[conn]) / det_f_np(X[conn], U[conn])
+    return min(r.min(), j.min())
+
+
+def _directions(m):
+    """Three directions of scales 0.1, 1 and 10.  The first and the last are random: on the whole mesh the reference crossing
+    of some small element usually comes first.  The middle one is the descent direction of sum_e log J_e over the free
+    coordinate rows at fixed u (J per element, QUAD4: per corner), scaled to max |d| = 1: it shrinks the deformed elements and
+    grows the reference ones, so the det F crossing comes first."""
+    g = torch.Generator().manual_seed(5)
+    conn = m.connectivity.cpu()
+    X = torch.as_tensor(_caller_rows(m)).requires_grad_(True)
+    U = torch.as_tensor(_u_rows(m))
+    cross = lambda a, b: a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+    if _is_quad(m):
+        corners = lambda T: cross(torch.roll(T, -1, dims=1) - T, torch.roll(T, 1, dims=1) - T)
+    else:
+        corners = lambda T: cross(T[:, 0] - T[:, 2], T[:, 1] - T[:, 2])
+    (gx,) = torch.autograd.grad(torch.log(corners((X + U)[conn]) / corners(X[conn])).sum(), X)
+    descent = -gx[m._idx_free.cpu().long()]
+    out = []
+    for k in range(3):
+        d = torch.randn(m.node_coords_free.shape, generator=g, dtype=F64) * 10.0 ** (k - 1)
+        out.append((descent / descent.abs().max() if k == 1 else d).to(DEV))
+    return out
+
+
+# ---------------------------------------------------------------- 1. step bound
+@pytest.mark.parametrize("which", list(MESHES))
+def test_hyper_step_bound_matches_numpy_and_lands_on_eta(which):
+    m = _deformed(which)
+    step = _step(m)
+    active = []
+    for eta in (0.25, 0.6):
+        for k, d in enumerate(_directions(m)):
+            got = step(m, d, eta=eta)
+            want, kind, X, D, U, conn = _ref_bound(m, d, eta)
+            print(f"{which} eta {eta} scale 1e{k - 1}: bound {got:.9e} numpy {want:.9e} active crossing {kind}")
+            assert math.isfinite(got) and abs(got - want) <= 1e-12 * want, (eta, k, got, want)
+            landed = _landed(m, X, D, U, conn, got)
+            assert abs(landed - eta) <= 1e-10, (eta, k, landed)
+            t = step(m, d, eta=eta, as_tensor=True)
+            assert t.is_cuda and t.dtype == F64 and t.item() == got       # the tensor form, bitwise: deterministic
+            active.append(kind)
+    # the log J descent direction stops at the det F crossing; of the random ones some stop at the reference crossing
+    # (found on the CPU: at eta = 0.25 the descent direction stops at the det F crossing on every mesh here; at eta = 0.6 some
+    # reference element gives up 40 % of its area before any det F does)
+    assert active[1] == "det_f" and "reference" in active, active
+    assert step(m, torch.zeros_like(m.node_coords_free)) == math.inf
+
+
+@pytest.mark.parametrize("which", ["tri_tile", "quad_split"])
+def test_hyper_step_bound_of_an_inverted_state_is_zero(which):
+    m = _deformed(which)
+    conn, X, U = m.connectivity.cpu().numpy(), _caller_rows(m), _u_rows(m)
+    V, _ = _invert(m, X, U, conn, 1)
+    _set_u(m, torch.as_tensor(V))
+    d = torch.randn(m.node_coords_free.shape, generator=torch.Generator().manual_seed(2), dtype=F64).to(DEV)
+    assert _step(m)(m, d) == 0.0 and _ref_bound(m, d, 0.25)[0] == 0.0
+    assert _step(m)(m, torch.zeros_like(d)) == 0.0                  # no step keeps a share of an inverted state
+
+
+@pytest.mark.parametrize("which", list(MESHES))
+def test_with_u_zero_the_bound_is_the_small_strain_bound_to_the_bit(which):
+    """BITWISE, not within 1 ulp: with u = 0 the deformed element is the reference element, det F stays 1 along any step, and
+    the det F polynomial (1 - eta) R(0) R(a) reaches 0 only where R does -- strictly after the reference crossing
+    R(a) = eta R(0).  So the minimum is the reference crossing, which both kernels compute with the same expressions."""
+    from hidenn_fem_amd import radapt
+    m = MESHES[which]()
+    _set_u(m, torch.zeros(m.Nnodes, 2, dtype=F64))
+    small = radapt.quad4_max_feasible_step if _is_quad(m) else radapt.max_feasible_step
+    g = torch.Generator().manual_seed(5)
+    for eta in (0.25, 0.6):
+        for k in range(3):
+            d = torch.randn(m.node_coords_free.shape, generator=g, dtype=F64).to(DEV) * 10.0 ** (k - 1)
+            a, b = _step(m)(m, d, eta=eta), small(m, d, eta=eta)
+            assert math.isfinite(a) and a == b, (eta, k, a, b)
+
+
+# ---------------------------------------------------------------- 2. deformation measure
+def _invert(m, X, U, conn, count):
+    """A copy of U (by node id) in which `count` more elements than before have J <= 0: free interior nodes, far apart, are
+    pushed through the line of their two neighbours in one of their elements, 15 % past it; a push is kept when it inverts
+    exactly one more element.  -> (V, nodes moved)"""
+    quad = _is_quad(m)
+    jfun = (lambda V: quad4_corner_ratios_np(X[conn], V[conn]).min(axis=1)) if quad else (lambda V: det_f_np(X[conn], V[conn]))
+    free = (~m.dirichlet_mask.cpu().numpy()) & (~m.boundary_mask.cpu().numpy())
+    V, moved = U.copy(), []
+    base = int((jfun(V) <= 0.0).sum())
+    npe = conn.shape[1]
+    for e in range(0, conn.shape[0], max(conn.shape[0] // 40, 1)):
+        n = int(conn[e, 0])
+        if not free[n] or any(np.linalg.norm(X[n] - X[o]) < 0.3 for o in moved):
+            continue
+        p, q = (X + V)[conn[e, 1]], (X + V)[conn[e, npe - 1]]
+        x = (X + V)[n]
+        foot = p + (q - p) * np.dot(x - p, q - p) / np.dot(q - p, q - p)
+        W = V.copy()
+        W[n] = V[n] + 1.15 * (foot - x)
+        if int((jfun(W) <= 0.0).sum()) == base + len(moved) + 1:
+            V, moved = W, moved + [n]
+            if len(moved) == count:
+                return V, moved
+    raise RuntimeError("no such pushes found")
+
+
+def _flipped(quad, fraction=0.4, seed=8):
+    """The jittered structured mesh with `fraction` of its elements numbered clockwise."""
+    from hidenn_fem_amd.mesh import structured_quad_mesh, structured_tri_mesh
+    from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+    if quad:
+        nc, conn, geom, bc, mn, edges = structured_quad_mesh(61, 41, jitter=0.25, seed=4, dtype=F64)
+        flip = torch.rand(conn.shape[0], generator=torch.Generator().manual_seed(seed)) < fraction
+        conn = torch.where(flip[:, None], conn[:, [0, 3, 2, 1]], conn).contiguous()
+    else:
+        nc, conn, geom, bc, mn, edges = structured_tri_mesh(61, 41, jitter=0.25, seed=3, flip_fraction=fraction, dtype=F64)
+    torch.manual_seed(0)
+    return PiecewiseLinearShapeNN2D(nc, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(DEV)
+
+
+def _check_deformation(m, tol=1e-13):
+    from hidenn_fem_amd.radapt import deformation_measure, quad4_deformation_measure
+    dm = (quad4_deformation_measure if _is_quad(m) else deformation_measure)(m)
+    want = _j_np(m)
+    got = dm.J.cpu().numpy()
+    assert got.shape == want.shape and np.abs(got - want).max() <= tol * np.abs(want).max()
+    assert dm.min_J == got.min()                                     # the device reduction is exact
+    assert dm.n_inverted == int((want <= 0.0).sum())
+    return dm, want
+
+
+@pytest.mark.parametrize("which", list(MESHES) + ["tri_flipped", "quad_flipped"])
+def test_deformation_measure_matches_numpy(which):
+    flipped = which.endswith("flipped")
+    if flipped:
+        m = _flipped(which.startswith("quad"))
+        X = _caller_rows(m)[m.connectivity.cpu().numpy()]
+        area = (X[:, 1, 0] - X[:, 0, 0]) * (X[:, -1, 1] - X[:, 0, 1]) - (X[:, 1, 1] - X[:, 0, 1]) * (X[:, -1, 0] - X[:, 0, 0])
+        assert 0.3 < (area < 0.0).mean() < 0.5                       # about 40 % clockwise
+        _set_u(m, _field(m))
+    else:
+        m = _deformed(which)
+    dm, want = _check_deformation(m)
+    assert dm.n_inverted == 0 and 0.3 < dm.min_J < 0.9               # clockwise elements too: J is a ratio of two signed areas
+    if not _is_quad(m):                                              # the loss reports the same minimum (QUAD4: over Gauss points)
+        from hidenn_fem_amd.loss import NeoHookeanLoss2D
+        lf = NeoHookeanLoss2D(device=DEV, dtype=m.dtype)
+        with torch.no_grad():
+            lf(m)
+        assert abs(lf.info[0].item() - dm.min_J) <= 1e-13 and lf.info[1].item() == 0.0
+    if flipped or which in ("tri_f32", "quad_split"):                # two inverted deformed elements
+        conn, X, U = m.connectivity.cpu().numpy(), _caller_rows(m), _u_rows(m)
+        V, moved = _invert(m, X, U, conn, 2)
+        _set_u(m, torch.as_tensor(V))
+        dm, want = _check_deformation(m)
+        assert dm.n_inverted == 2 and dm.min_J < 0.0, (dm.n_inverted, moved)
+
+
+# ---------------------------------------------------------------- 3. reduced gradient
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_central_difference_of_the_reduced_energy_matches_g_dot_d(kind):
+    """The 17 x 9 plate of the Newton tests under the default traction (E = 2e6: strains of a few per cent), Newton re-solved
+    to rtol 1e-12 on each side; the step and the tolerance of the small-strain twin."""
+    from hidenn_fem_amd import radapt
+    if kind == "tri3":
+        import test_gpu_newton as T
+        cls = radapt.HyperRAdaptiveSolver
+    else:
+        import test_gpu_quad4_newton as T
+        cls = radapt.Quad4HyperRAdaptiveSolver
+    m, t_force = T.run_model("default")
+    s = cls(m, T.make_loss(E=N.E_SOFT), t_force=t_force, newton_rtol=1e-12)
+    assert s.solver.solve().converged
+    _, _, g = s.objective_and_grad()
+    x0 = m.node_coords_free.detach().clone()
+    d = torch.randn(x0.shape, generator=torch.Generator().manual_seed(3), dtype=F64).to(DEV)
+    h = 1e-3 * min(s.mesh.step_bound(d, 0.25).item(), 1.0)
+
+    def pistar(a):
+        with torch.no_grad():
+            m.node_coords_free.copy_(x0 + a * d)
+        assert s.solver.solve().converged
+        return s.objective()
+
+    fd = (pistar(h) - pistar(-h)) / (2.0 * h)
+    gd = torch.dot(g, d.reshape(-1)).item()
+    print(f"{kind}: central difference {fd:.9e} vs g.d {gd:.9e} (h = {h:.3e})")
+    assert abs(fd - gd) <= 1e-5 * abs(gd), (fd, gd)
+
+
+# ---------------------------------------------------------------- 4. r-adaptive runs
+# The traction pulls the right edge DOWN, (0, -factor x 1e5) with 1e5 the default traction, on E = 2e6: the plate bends and
+# the elements at the foot of the clamped edge are compressed.  Factor and the start's min J (the equilibrium on the initial
+# mesh from u = 0) come from the CPU Newton reference (tests/newton_reference.py `newton` on tests/hyper_reference.py /
+# tests/quad4_hyper_reference.py, rtol 1e-8): TRI3 60 x 30 holed plate, factor 0.2: 10 Newton iterations, min J 0.672425;
+# QUAD4 41 x 21 plate, factor 0.4: 8 Newton iterations, min J 0.628680 (over the Gauss points).
+RUNS = {"tri3": (0.2, 0.6724247544718143), "quad4": (0.4, 0.6286802880835447)}
+
+
+def _down(factor):
+    return lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -factor * 1e5)], dim=1)
+
+
+def _run_setup(kind, dtype=F64, **loss_kw):
+    from hidenn_fem_amd import radapt
+    from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
+    quad = kind == "quad4"
+    m = _quad_plate(dtype) if quad else _tri_plate(dtype=dtype)
+    with torch.no_grad():
+        m.u_free.zero_()
+    lf = (Quad4NeoHookeanLoss2D if quad else NeoHookeanLoss2D)(E=N.E_SOFT, device=DEV, dtype=dtype, **loss_kw)
+    cls = radapt.Quad4HyperRAdaptiveSolver if quad else radapt.HyperRAdaptiveSolver
+    quality = radapt.quad4_mesh_quality if quad else radapt.mesh_quality
+    return m, lf, cls, quality, _down(RUNS[kind][0]), RUNS[kind][1]
+
+
+def _report(tag, info):
+    print(f"{tag}: {info.iterations} outer iterations ({info.reason}), energy {info.energy[0]:.9e} -> {info.energy[-1]:.9e}, "
+          f"min J {info.min_J[0]:.6f} -> {info.min_J[-1]:.6f}, min q {info.min_q[0]:.4f} -> {info.min_q[-1]:.4f}, "
+          f"Newton {info.newton_iterations}, CG {info.cg_iterations}, step ratios {[round(r, 4) for r in info.step_ratio[1:]]}, "
+          f"J step ratios {[round(r, 4) for r in info.J_step_ratio[1:]]}")
+
+
+@pytest.mark.parametrize("quality_weight", [0.0, 0.05])
+@pytest.mark.parametrize("precond", ["block_jacobi", "amg"])
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_hyper_r_adaptive_run_lowers_the_reduced_energy_and_keeps_det_f(kind, precond, quality_weight):
+    from hidenn_fem_amd.radapt import HyperRAdaptInfo
+    m, lf, cls, quality, t_force, start_min_j = _run_setup(kind)
+    if kind == "tri3":
+        assert 2000 <= m.Nelems <= 8000
+    xfix0, ufull_dir0 = m.node_coords_fixed.clone(), m.u_full.detach()[m.dirichlet_mask].clone()
+    assert m.node_coords_free.grad is None and m.u_free.grad is None
+    eta, rtol = 0.25, 1e-8
+    s = cls(m, lf, t_force=t_force, eta=eta, quality_weight=quality_weight, precond=precond, newton_rtol=rtol, max_outer=10)
+    info = s.run()
+    _report(f"{kind} {precond} w = {quality_weight}", info)
+    assert isinstance(info, HyperRAdaptInfo) and info.iterations >= 3, info
+    assert abs(info.min_J[0] - start_min_j) <= 1e-6 and info.min_J[0] < 0.9          # the recorded start
+    n = info.iterations + 1
+    assert all(len(v) == n for v in (info.newton_iterations, info.min_J, info.J_step_ratio, info.cg_iterations, info.energy))
+    f = info.objective
+    for a, b in zip(f, f[1:]):
+        assert b <= a + 1e-12 * abs(a), f
+    assert info.energy[-1] < info.energy[0], info.energy
+    assert all(r >= eta * (1.0 - 1e-12) for r in info.step_ratio[1:]), info.step_ratio
+    assert all(r >= eta * (1.0 - 1e-12) for r in info.J_step_ratio[1:]), info.J_step_ratio
+    assert math.isnan(info.J_step_ratio[0]) and all(j > 0.0 for j in info.min_J), info.min_J
+    assert all(0.0 < a <= 0.9 * am for a, am in zip(info.alpha[1:], info.alpha_max[1:]))
+    mq = quality(m)
+    assert mq.n_inverted == 0 and mq.min_q > 0.0
+    assert info.reason != "newton" and s.last_solve.converged, (info.reason, s.last_solve)
+    with torch.enable_grad():
+        (gu,) = torch.autograd.grad(lf(m, None, t_force), m.u_free)
+    assert gu.norm().item() <= 10.0 * rtol * s.last_solve.rhs_norm, (gu.norm().item(), s.last_solve.rhs_norm)
+    assert torch.equal(m.node_coords_fixed, xfix0) and torch.equal(m.u_full.detach()[m.dirichlet_mask], ufull_dir0)
+    assert m.node_coords_free.grad is None and m.u_free.grad is None
+
+
+def test_hyper_r_adaptive_run_on_an_fp32_model_keeps_every_element_and_det_f():
+    """fp32 rows: every rounded trial is measured against x_k with both measures, so the ratios hold for the rows as stored."""
+    m, lf, cls, quality, t_force, _ = _run_setup("tri3", dtype=F32)
+    info = cls(m, lf, t_force=t_force, max_outer=10).run()
+    _report("tri3 fp32", info)
+    assert info.iterations >= 1 and m.node_coords_free.dtype == F32 and m.u_free.dtype == F32
+    assert quality(m).n_inverted == 0 and all(j > 0.0 for j in info.min_J)
+    assert all(r >= 0.25 * (1.0 - 1e-6) for r in info.step_ratio[1:]), info.step_ratio
+    assert all(r >= 0.25 * (1.0 - 1e-6) for r in info.J_step_ratio[1:]), info.J_step_ratio
+    assert info.energy[-1] < info.energy[0]
+
+
+def test_quad4_hyper_run_off_the_default_tile_shape_and_through_r_adapt():
+    """``r_adapt_`` dispatches on the loss; the loss at ``tile_elems=300`` puts the plate's 800 cells on tiles of another shape
+    than the default plan's."""
+    from hidenn_fem_amd.radapt import HyperRAdaptInfo, r_adapt_
+    m, lf, _, quality, t_force, start_min_j = _run_setup("quad4", tile_elems=300)
+    shape = lambda p: (p.n_tiles, p.stats["max_tile_elems"])
+    assert shape(m.tile_plan(300)) != shape(m.tile_plan(0)), shape(m.tile_plan(0))
+    info = r_adapt_(m, lf, t_force=t_force, max_outer=4)
+    _report("quad4 tile_elems 300", info)
+    assert isinstance(info, HyperRAdaptInfo) and info.iterations >= 3 and abs(info.min_J[0] - start_min_j) <= 1e-6
+    assert all(b <= a + 1e-12 * abs(a) for a, b in zip(info.objective, info.objective[1:]))
+    assert all(r >= 0.25 * (1.0 - 1e-12) for r in info.step_ratio[1:] + info.J_step_ratio[1:])
+    assert quality(m).n_inverted == 0
+
+
+def test_r_adapt_dispatch_an_inverted_start_and_the_kept_refusals():
+    from hidenn_fem_amd import radapt
+    from hidenn_fem_amd.loss import EnergyLoss2D
+    from hidenn_fem_amd.post import StressRecovery
+    from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver
+    m, lf, cls, _, t_force, _ = _run_setup("tri3")
+    info = radapt.r_adapt_(m, lf, t_force=t_force, max_outer=1)
+    assert isinstance(info, radapt.HyperRAdaptInfo) and info.iterations == 1 and info.reason == "max_outer"
+    assert info.newton_iterations[0] > 0 and info.energy[1] < info.energy[0]
+    lin = radapt.r_adapt_(m, EnergyLoss2D(device=DEV, dtype=F64), max_outer=1)         # the small-strain dispatch is unchanged
+    assert type(lin) is radapt.RAdaptInfo
+    # an inverted start raises and names min_J; nothing is written
+    conn, X, U = m.connectivity.cpu().numpy(), _caller_rows(m), _u_rows(m)
+    V, _ = _invert(m, X, U, conn, 1)
+    _set_u(m, torch.as_tensor(V))
+    before = m.u_free.detach().clone(), m.node_coords_free.detach().clone()
+    with pytest.raises(RuntimeError, match=r"inverted \(min_J = -"):
+        cls(m, lf, t_force=t_force).run()
+    assert torch.equal(m.u_free.detach(), before[0]) and torch.equal(m.node_coords_free.detach(), before[1])
+    # kept refusals
+    mq, lfq, clsq, *_ = _run_setup("quad4")
+    for bad in (lambda: radapt.RAdaptiveSolver(m, lf), lambda: radapt.Quad4RAdaptiveSolver(mq, lfq),
+                lambda: FrozenMeshSolver(m, lf), lambda: Quad4FrozenMeshSolver(mq, lfq), lambda: StressRecovery(m, lf),
+                lambda: cls(mq, lfq), lambda: clsq(m, lf), lambda: cls(m, EnergyLoss2D(device=DEV, dtype=F64)),
+                lambda: radapt.RAdaptiveSolver(mq, EnergyLoss2D(device=DEV, dtype=F64)),
+                lambda: radapt.hyper_max_feasible_step(mq, torch.zeros_like(mq.node_coords_free)),
+                lambda: radapt.quad4_deformation_measure(m)):
+        with pytest.raises(NotImplementedError):
+            bad()
+
+
+# ---------------------------------------------------------------- 5. example
+@pytest.mark.parametrize("quad", [False, True], ids=["tri3", "quad4"])
+def test_example4_neo_hookean_r_adapt_ends_below_the_frozen_mesh_energy(capsys, quad):
+    import examples.example4 as e4
+    m, final = e4.run_neo_hookean(nx=40, ny=20, quad=quad, r_adapt=True, outer=5)
+    out = capsys.readouterr().out
+    assert _is_quad(m) == quad
+    frozen = float(re.search(r"frozen-mesh energy (\S+)", out).group(1))
+    adapted = float(re.search(r"r-adapted energy (\S+)", out).group(1))
+    gained = float(re.search(r"energy gained over the frozen mesh (\S+)", out).group(1))
+    assert re.search(r"inverted elements 0\b", out) and re.search(r"outer +1: energy \S+ min J \S+ min q \S+ .*Newton \d+ CG \d+", out), out
+    assert adapted < frozen and abs(adapted - final) <= 1e-9 * abs(final) and gained > 0.0, out
