@@ -1,5 +1,5 @@
-// The closed form every step bound shares: the first positive root of the quadratic a step bound solves (hfem_mesh_dev.h:
-// detJ(x + a d) = eta detJ(x); hfem_hyper_mesh_dev.h: det F(a) = eta det F(0) as well).  A plain inline function, no wave
+// The closed form every step bound shares: the first positive root of the quadratic a step bound solves (hfem_mesh_elem_dev.h:
+// detJ(x + a d) = eta detJ(x), and at finite strain det F(a) = eta det F(0) as well).  A plain inline function, no wave
 // intrinsics: a host program compiles it against tests/host/hip_stub.  Internal linkage, one instance per translation unit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -6,13 +6,13 @@ theorem gives
 ``grad Pi*(x) = dE/dx`` at ``u = u*(x)`` -- the coordinate gradient the graded energy kernel already returns.  A step on ``x``
 at fixed ``u_k`` that passes an Armijo test gives ``Pi*(x_k+1) <= E(u_k, x_k+1) < E(u_k, x_k) = Pi*(x_k)``: re-solving ``u`` (CG
 from ``u_k``, whose energy only decreases) can only lower it further, so every outer iteration lowers the reduced energy.
-What keeps each step valid is device code (``csrc/tri3_mesh.hip``): the step bound (the largest step before some element
+What keeps each step valid is device code (``csrc/mesh_guard.hip``): the step bound (the largest step before some element
 keeps less than ``eta`` of its signed area -- ``detJ(x + a d)`` is an exact quadratic in ``a``), the element measure (signed
 mean-ratio quality ``q``, the ``detJ`` ratio to the initial mesh, the inverted count) and the opt-in quality barrier
 ``Q(x) = (w / Ne) sum (1/q - 1)``: the ``mesh_quality_loss`` the reference's example 4 sketches (examples/example4.py:83-110)
 and never defines.
 
-QUAD4 models (``csrc/quad4_mesh.hip``): the same three pieces per CORNER of a bilinear cell.  With the corner cross product
+QUAD4 models (the same file): the same three pieces per CORNER of a bilinear cell.  With the corner cross product
 ``c_k = (X_k+1 - X_k) x (X_k-1 - X_k)`` (``= 4 detJ`` at corner ``k``; ``detJ`` is affine over the reference square, so its
 extremes are at the corners) a cell is valid everywhere iff all four ``s c_k > 0``, the step bound is the first step at which
 some ``c_k`` keeps only ``eta`` of its value (every Gauss-point ``detJ`` then keeps at least ``eta``), ``q = min_k q_k`` with
@@ -28,7 +28,7 @@ Finite strain (``NeoHookeanLoss2D`` / ``Quad4NeoHookeanLoss2D``): ``H
 ``Quad4HyperRAdaptiveSolver`` run the same loop with ``newton.NewtonKrylovSolver`` / ``Quad4NewtonKrylovSolver`` as the
 displacement solve.  There the quantity that must not collapse is ``det F = detJ(X + u) / detJ(X)``, and a coordinate step at
 fixed nodal ``u`` moves numerator and denominator: a trial that keeps the reference area can still drive ``det F`` to zero
-and the energy to ``+inf``.  ``csrc/tri3_hyper_mesh.hip`` / ``csrc/quad4_hyper_mesh.hip`` hold the guard: the step bound that
+and the energy to ``+inf``.  ``csrc/mesh_guard.hip`` holds the guard for both element kinds as well: the step bound that
 also stops at the first step with ``det F(a) = eta det F(0)`` (an exact quadratic as well; ``hyper_max_feasible_step``,
 ``quad4_hyper_max_feasible_step``) and the deformation measure ``J`` (``deformation_measure``,
 ``quad4_deformation_measure``).
@@ -55,7 +55,7 @@ def _check_eta(eta):
 
 class _Mesh:
     """What the mesh kernels read of a model: the int32 connectivity, the x row map, the fixed and the reference rows (all on
-    the model's device, in its coordinate dtype).  TRI3 (``csrc/tri3_mesh.hip``); ``_QuadMesh`` is the QUAD4 one."""
+    the model's device, in its coordinate dtype).  TRI3 (``csrc/mesh_guard.hip``); ``_QuadMesh`` is the QUAD4 one."""
 
     abi, npe, kind = "hfem_tri3", 3, "TRI3"                    # prefix of the three entry points, nodes per element
     other = "QUAD4 models: quad4_mesh_quality, quad4_max_feasible_step, quad4_quality_barrier, Quad4RAdaptiveSolver"
@@ -83,10 +83,18 @@ class _Mesh:
         t = self.model.node_coords_fixed.to(device=self.device, dtype=self.dtype).contiguous()
         return t if t.numel() else None
 
-    def _call(self, name, *args):
-        """Call the entry point ``name`` of this element kind (its ``_f32`` twin for fp32 rows) and check its return code."""
+    def _x_rows(self):
+        """The x row map and the tensors behind it: the model's CURRENT free rows and its fixed rows (None if there are none)."""
+        return self.x_src, self.model.node_coords_free.detach(), self.fixed()
+
+    def _call(self, name, *args, rows=None):
+        """Call the entry point ``name`` of this element kind (its ``_f32`` twin for fp32 rows) and check its return code.  Every
+        entry point starts with the device, the connectivity, the element count and the row maps with their rows -- ``rows``
+        (default ``_x_rows()``), referenced here until the call returns -- and ends with the stream; ``args`` go in between."""
+        rows = self._x_rows() if rows is None else rows
         name = f"{self.abi}_{name}"
-        check(getattr(_lib.lib(), name + "_f32" if self.f32 else name)(*args), name)
+        fn = getattr(_lib.lib(), name + "_f32" if self.f32 else name)
+        check(fn(dev_index(self.device), ptr(self.conn), self.ne, *(ptr(t) for t in rows), *args, stream_ptr(self.device)), name)
 
     def measure(self, x_ref=None, per_element=True):
         """(q [Ne] or None, ratio [Ne] or None, summary [3] fp64 device) against ``x_ref`` (default: initial coordinates)."""
@@ -95,21 +103,14 @@ class _Mesh:
         r = torch.empty(self.ne, dtype=F64, device=dev) if per_element else None
         summary = torch.empty(3, dtype=F64, device=dev)
         xr = self.x_ref if x_ref is None else x_ref.to(dtype=self.dtype).contiguous()
-        xf = self.model.node_coords_free.detach()
-        xfix = self.fixed()
-        self._call("mesh_measure", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix), ptr(xr), ptr(q),
-                   ptr(r), ptr(summary), stream_ptr(dev))
+        self._call("mesh_measure", ptr(xr), ptr(q), ptr(r), ptr(summary))
         return q, r, summary
 
     def step_bound(self, d, eta, out=None):
         """0-d fp64 device tensor: the largest step along ``d`` (fp64 [n_x, 2], storage order) that keeps every element's
         ``detJ`` at or above ``eta`` times its current value."""
-        dev = self.device
-        out = torch.empty((), dtype=F64, device=dev) if out is None else out
-        xf = self.model.node_coords_free.detach()
-        xfix = self.fixed()
-        self._call("step_bound", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix), ptr(d), float(eta),
-                   ptr(out), stream_ptr(dev))
+        out = torch.empty((), dtype=F64, device=self.device) if out is None else out
+        self._call("step_bound", ptr(d), float(eta), ptr(out))
         return out
 
     def barrier(self, weight, grad=True):
@@ -117,10 +118,7 @@ class _Mesh:
         dev = self.device
         val = torch.zeros((), dtype=F64, device=dev)
         g = torch.zeros((self.n_x, 2), dtype=F64, device=dev) if grad else None
-        xf = self.model.node_coords_free.detach()
-        xfix = self.fixed()
-        self._call("quality_barrier", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
-                   ptr(self.x_ref), float(weight), ptr(val), ptr(g), stream_ptr(dev))
+        self._call("quality_barrier", ptr(self.x_ref), float(weight), ptr(val), ptr(g))
         return val, g
 
     # ---- the public functions of an element kind
@@ -138,7 +136,7 @@ class _Mesh:
 
 
 class _QuadMesh(_Mesh):
-    """``_Mesh`` of a QUAD4 model: connectivity ``[Ne, 4]``, the corner-wise kernels of ``csrc/quad4_mesh.hip``."""
+    """``_Mesh`` of a QUAD4 model: connectivity ``[Ne, 4]``, the corner-wise kernels of ``csrc/mesh_guard.hip``."""
 
     abi, npe, kind = "hfem_quad4", 4, "QUAD4"
     other = "TRI3 models: mesh_quality, max_feasible_step, quality_barrier, RAdaptiveSolver"
@@ -146,10 +144,9 @@ class _QuadMesh(_Mesh):
 
 
 class _HyperRows:
-    """What the finite-strain mesh kernels read besides the coordinates (``csrc/tri3_hyper_mesh.hip``,
-    ``csrc/quad4_hyper_mesh.hip``): the u row map and the model's CURRENT ``u_free`` and ``u_fixed_rows()``.  Mixed into a mesh
-    class, it replaces the step bound by the det F-safe one and adds the deformation measure; fp32 trials are measured for both
-    element kinds."""
+    """What the finite-strain mesh kernels read besides the coordinates (``csrc/mesh_guard.hip``): the u row map and the
+    model's CURRENT ``u_free`` and ``u_fixed_rows()``.  Mixed into a mesh class, it replaces the step bound by the det F-safe
+    one and adds the deformation measure; fp32 trials are measured for both element kinds."""
 
     measure_f32_trials = True
 
@@ -160,33 +157,24 @@ class _HyperRows:
                                f"({self.dtype}, {self.device}), got {model.u_free.dtype}, {model.u_free.device}")
         self.u_src = torch.from_numpy(model._u_src).to(self.device)
 
-    def _u_rows(self):
+    def _xu_rows(self):
+        """``_x_rows()``, then the u row map and the tensors behind it: the model's CURRENT ``u_free`` and fixed rows."""
         uf = self.model.u_free.detach().contiguous()
         ufix = self.model.u_fixed_rows().detach().to(device=self.device, dtype=self.dtype).contiguous()
-        return (uf if uf.numel() else None), (ufix if ufix.numel() else None)
+        return self._x_rows() + (self.u_src, uf if uf.numel() else None, ufix if ufix.numel() else None)
 
     def step_bound(self, d, eta, out=None):
         """0-d fp64 device tensor: the largest step along ``d`` (fp64 [n_x, 2], storage order) at fixed ``u`` that keeps every
         element's (QUAD4: corner's) ``detJ`` and ``det F`` at or above ``eta`` times their current values."""
-        dev = self.device
-        out = torch.empty((), dtype=F64, device=dev) if out is None else out
-        xf = self.model.node_coords_free.detach()
-        xfix = self.fixed()
-        uf, ufix = self._u_rows()
-        self._call("hyper_step_bound", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
-                   ptr(self.u_src), ptr(uf), ptr(ufix), ptr(d), float(eta), ptr(out), stream_ptr(dev))
+        out = torch.empty((), dtype=F64, device=self.device) if out is None else out
+        self._call("hyper_step_bound", ptr(d), float(eta), ptr(out), rows=self._xu_rows())
         return out
 
     def deformation(self, per_element=True):
         """(J [Ne] or None, summary [2] fp64 device = {min J, number of elements with J <= 0 or NaN}) at the current rows."""
-        dev = self.device
-        j = torch.empty(self.ne, dtype=F64, device=dev) if per_element else None
-        summary = torch.empty(2, dtype=F64, device=dev)
-        xf = self.model.node_coords_free.detach()
-        xfix = self.fixed()
-        uf, ufix = self._u_rows()
-        self._call("deformation_measure", dev_index(dev), ptr(self.conn), self.ne, ptr(self.x_src), ptr(xf), ptr(xfix),
-                   ptr(self.u_src), ptr(uf), ptr(ufix), ptr(j), ptr(summary), stream_ptr(dev))
+        j = torch.empty(self.ne, dtype=F64, device=self.device) if per_element else None
+        summary = torch.empty(2, dtype=F64, device=self.device)
+        self._call("deformation_measure", ptr(j), ptr(summary), rows=self._xu_rows())
         return j, summary
 
     def deformation_measure(self):
@@ -614,7 +602,7 @@ class RAdaptiveSolver(_RAdaptBase):
 class Quad4RAdaptiveSolver(_RAdaptBase):
     """``RAdaptiveSolver`` for QUAD4 models (``QuadShapeNN2D``): the same arguments, the same ``RAdaptInfo``, the same outer
     loop, line search and stopping rules (one piece of code).  The displacement solve is ``Quad4FrozenMeshSolver``; the step
-    bound, the measure and the opt-in barrier are the corner-wise kernels of ``csrc/quad4_mesh.hip`` (module docstring): a step
+    bound, the measure and the opt-in barrier are the corner-wise kernels of ``csrc/mesh_guard.hip`` (module docstring): a step
     keeps every corner cross product, and so ``detJ`` at every Gauss point, at or above ``eta`` of its value, and
     ``step_ratio`` is the smallest corner ratio.  fp32 models: each rounded trial of the line search is measured against
     ``x_k`` and halved while it keeps less than ``eta`` (``_line_search``), so the bound holds for the rows as stored.  Refuses TRI3 models, ``EnergyLoss2D(deterministic=True)`` and the planless
@@ -742,7 +730,7 @@ class HyperRAdaptiveSolver(_HyperRAdaptBase):
 class Quad4HyperRAdaptiveSolver(_HyperRAdaptBase):
     """``HyperRAdaptiveSolver`` for QUAD4 models under a ``Quad4NeoHookeanLoss2D``: the same arguments, loop and
     ``HyperRAdaptInfo``.  The displacement solve is ``Quad4NewtonKrylovSolver``; the step bound and the deformation measure are
-    the corner-wise kernels of ``csrc/quad4_hyper_mesh.hip``: a step keeps ``eta`` of every corner cross product and of every
+    the corner-wise kernels of ``csrc/mesh_guard.hip``: a step keeps ``eta`` of every corner cross product and of every
     corner ratio ``c_k^def / c_k``, so ``det F`` at every Gauss point stays at or above ``eta`` times the cell's smallest corner
     ratio before the step; ``J_step_ratio`` is taken on the cells' smallest corner ratios.  Refuses an ``EnergyLoss2D``
     (``Quad4RAdaptiveSolver``) and TRI3 models or losses (``HyperRAdaptiveSolver``)."""

@@ -806,7 +806,7 @@ int hfem_tri3_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, c
                                   double *grad_acc, void *stream);
 
 /* ------------------------------------------------------------------ mesh validity for r-adaptivity (QUAD4)
- * The bilinear-cell twins of the TRI3 entry points above (csrc/quad4_mesh.hip; Quad4RAdaptiveSolver in
+ * The bilinear-cell twins of the TRI3 entry points above (csrc/mesh_guard.hip; Quad4RAdaptiveSolver in
  * hidenn_fem_amd/radapt.py): the same argument lists, row maps, row types and argument checks, over conn [ne][4] (local nodes
  * counter-clockwise, neighbour indices mod 4).  Corner cross product c_k = (X_k+1 - X_k) x (X_k-1 - X_k) = 4 detJ at corner k;
  * detJ is affine over the reference square, so a cell is valid everywhere iff all four s c_k > 0, s = sign of c_0 + c_2 (twice
@@ -838,7 +838,7 @@ int hfem_quad4_quality_barrier_f32(int device, const int32_t *conn, int64_t ne, 
                                    double *grad_acc, void *stream);
 
 /* ------------------------------------------------------------------ mesh validity for r-adaptivity at finite strain
- * The det F-safe step bound and the deformation measure (csrc/tri3_hyper_mesh.hip, csrc/quad4_hyper_mesh.hip;
+ * The det F-safe step bound and the deformation measure (csrc/mesh_guard.hip;
  * HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver in hidenn_fem_amd/radapt.py).  The argument lists of the step_bound entry
  * points above plus the displacement rows after the coordinate rows: u_src [nn] the u row map (>= 0: row of u_free, < 0: row
  * -1 - u_src of u_fixed, the Dirichlet rows), u_free, u_fixed in the row type of the coordinates (either may be NULL when no

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""r-adaptive solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/radapt.py, csrc/tri3_mesh.hip).
---quad: the same records for 10^6 QUAD4 cells (Quad4RAdaptiveSolver, csrc/quad4_mesh.hip).
+"""r-adaptive solve at T1M (dev tool): 10^6 TRI3, fp64, default traction (hidenn_fem_amd/radapt.py, csrc/mesh_guard.hip).
+--quad: the same records for 10^6 QUAD4 cells (Quad4RAdaptiveSolver).
 
 Records, as one JSON object:
   * the step-bound launch (init + element kernel), the measure launch (init + element kernel + finish), the barrier launch
@@ -13,8 +13,8 @@ Records, as one JSON object:
     Pi* before and after, reason, min q, wall time (--quad: the plate without holes, 200 x 100 nodes of QUAD4 cells).
 Cache regime: the working sets stay in the 256 MB Infinity Cache.
 
---neo-hookean [--quad]: the finite-strain guard (HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver, csrc/tri3_hyper_mesh.hip,
-csrc/quad4_hyper_mesh.hip) on the same meshes, at a smooth displacement field with min J about 0.5:
+--neo-hookean [--quad]: the finite-strain guard (HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver) on the same meshes, at a
+smooth displacement field with min J about 0.5:
   * the fused det F-safe bound launch (init + element kernel);
   * the composition available without it -- the torch add that forms X + u on the coordinate rows, `hfem_*_step_bound` on X
     and on X + u, and the minimum of the two (the rows of u gathered onto the coordinate rows beforehand, not timed).  It
@@ -23,6 +23,9 @@ csrc/quad4_hyper_mesh.hip) on the same meshes, at a smooth displacement field wi
   * the deformation measure launch, without and with the per-element output;
   * --outer N outer iterations of the finite-strain solver under a downward traction (E = 2e6, --precond for Newton):
     per iteration the Newton solve and everything else (host clock), and the share spent outside Newton (0 skips this).
+--lib FILE: load that build of the library instead of the tree's own (A/B of two builds with one ABI under the same driver).
+--pieces: the mesh-kernel launches only (bound, measure, barrier; --neo-hookean: fused and composed bound, deformation
+measure) on the mesh classes of radapt.py, no solver built and none of the solves.
 
     python scripts/radapt_timing.py [--grid 1001x501] [--reps 200] [--out profiles/radapt/radapt_timing_T1M.json]
     python scripts/radapt_timing.py --quad [--grid 1415x708] [--out profiles/radapt/radapt_timing_quad4_T1M.json]
@@ -106,6 +109,15 @@ def smooth_field(x):
                         0.09 * torch.cos(1.7 * x[:, 0] + 0.3) * torch.sin(2.4 * x[:, 1])], dim=1)
 
 
+def emit(rec, out):
+    line = json.dumps(rec)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main_neo_hookean(a, dev, nx, ny):
     from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.radapt import HyperRAdaptiveSolver, Quad4HyperRAdaptiveSolver, _Mesh, _QuadMesh
@@ -124,8 +136,12 @@ def main_neo_hookean(a, dev, nx, ny):
     rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=ne, n_nodes=nn,
                n_x_rows=int(m.node_coords_free.shape[0]),
                regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
-    s = Solver(m, lf, t_force=down, max_outer=a.outer, precond=a.precond)
-    mesh, small = s.mesh, Small(m)
+    if a.pieces:
+        from hidenn_fem_amd.radapt import _HyperMesh, _QuadHyperMesh
+        mesh, small = (_QuadHyperMesh if a.quad else _HyperMesh)(m), Small(m)
+    else:
+        s = Solver(m, lf, t_force=down, max_outer=a.outer, precond=a.precond)
+        mesh, small = s.mesh, Small(m)
     j, summary = mesh.deformation()
     rec["state"] = dict(min_J=summary[0].item(), n_inverted=int(summary[1].item()), max_J=j.max().item())
     d = torch.randn(m.node_coords_free.shape, dtype=F64, device=dev) * 1e-3
@@ -143,13 +159,12 @@ def main_neo_hookean(a, dev, nx, ny):
     y = torch.empty_like(xf)
     a2 = torch.empty(2, dtype=F64, device=dev)
     both = torch.empty((), dtype=F64, device=dev)
-    from hidenn_fem_amd._lib import dev_index, ptr, stream_ptr
+    from hidenn_fem_amd._lib import ptr
 
     def composed():
         torch.add(xf, u_on_x, out=y)
         for k, (rows, fixed) in enumerate(((xf, xfix), (y, yfix))):
-            small._call("step_bound", dev_index(dev), ptr(small.conn), small.ne, ptr(small.x_src), ptr(rows), ptr(fixed), ptr(d), 0.25,
-                        a2.data_ptr() + 8 * k, stream_ptr(dev))
+            small._call("step_bound", ptr(d), 0.25, a2.data_ptr() + 8 * k, rows=(small.x_src, rows, fixed))
         torch.amin(a2, dim=0, out=both)
 
     composed_us = graphed_us(composed, a.reps)
@@ -160,7 +175,7 @@ def main_neo_hookean(a, dev, nx, ny):
     rec["measure_per_element_output"] = dict(us=graphed_us(lambda: mesh.deformation(per_element=True), a.reps))
 
     # ---- outer iterations from u = 0 under the traction: Newton vs everything else
-    if a.outer > 0:
+    if a.outer > 0 and not a.pieces:
         with torch.no_grad():
             m.u_free.zero_()
         m.u_fixed = torch.zeros_like(m.u_fixed)
@@ -178,12 +193,7 @@ def main_neo_hookean(a, dev, nx, ny):
                             step_ratio=info.step_ratio, J_step_ratio=info.J_step_ratio, seconds_total=total,
                             seconds_newton=solve_clock.total, seconds_other=total - solve_clock.total,
                             share_outside_newton=(total - solve_clock.total) / total)
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(rec, a.out)
 
 
 def main():
@@ -196,7 +206,12 @@ def main():
     ap.add_argument("--outer", type=int, default=3, help="--neo-hookean: outer iterations to time (0: none)")
     ap.add_argument("--precond", default="amg", help="--neo-hookean: Newton's preconditioner")
     ap.add_argument("--traction", type=float, default=2e4, help="--neo-hookean: the downward traction on the right edge")
+    ap.add_argument("--lib", default="", help="the library file to load (default: the tree's own build)")
+    ap.add_argument("--pieces", action="store_true", help="the mesh-kernel launches only, no solver")
     a = ap.parse_args()
+    if a.lib:
+        from hidenn_fem_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     dev = torch.device("cuda:0")
     nx, ny = (int(v) for v in (a.grid or ("1415x708" if a.quad else "1001x501")).split("x"))
     if a.neo_hookean:
@@ -211,8 +226,12 @@ def main():
     rec = dict(mesh=f"{nx}x{ny} structured {'QUAD4' if a.quad else 'TRI3'}, jitter 0.2", n_elems=ne, n_nodes=nn, n_x_rows=int(m.node_coords_free.shape[0]),
                regime="cache (working set < 256 MB Infinity Cache; back-to-back launches of the same buffers)")
 
-    s = Solver(m, lf, max_outer=3)
-    mesh = s.mesh
+    if a.pieces:
+        from hidenn_fem_amd.radapt import _Mesh, _QuadMesh
+        mesh = (_QuadMesh if a.quad else _Mesh)(m)
+    else:
+        s = Solver(m, lf, max_outer=3)
+        mesh = s.mesh
     d = torch.randn(m.node_coords_free.shape, dtype=F64, device=dev) * 1e-3
     alpha = torch.empty((), dtype=F64, device=dev)
     bound_us = graphed_us(lambda: mesh.step_bound(d, 0.25, out=alpha), a.reps)
@@ -222,6 +241,8 @@ def main():
     rec["measure"] = dict(us=graphed_us(lambda: mesh.measure(per_element=False), a.reps), launches=3)
     rec["measure_per_element_outputs"] = dict(us=graphed_us(lambda: mesh.measure(per_element=True), a.reps))
     rec["barrier"] = dict(us=graphed_us(lambda: mesh.barrier(1.0), a.reps), launches="2 fills + 1")
+    if a.pieces:
+        return emit(rec, a.out)
     energy_us = graphed_us(lambda: lf.value_and_grad_(m), a.reps)
     rec["energy_value_and_grad"] = dict(us=energy_us, note="graded energy kernel + tile-energy sum launch")
     rec["step_bound_over_energy"] = bound_us / energy_us
@@ -275,12 +296,7 @@ def main():
                         energy_frozen=pi.energy[0], energy_final=pi.energy[-1], decrease=pi.energy[0] - pi.energy[-1],
                         cg_iterations=pi.cg_iterations, min_q_initial=pi.min_q[0], min_q_final=mq.min_q,
                         n_inverted=mq.n_inverted, seconds=time.perf_counter() - t0, energy=pi.energy)
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(rec, a.out)
 
 
 if __name__ == "__main__":

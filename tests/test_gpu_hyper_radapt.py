@@ -1,5 +1,5 @@
 """r-adaptive solve at finite strain (hidenn_fem_amd/radapt.py HyperRAdaptiveSolver / Quad4HyperRAdaptiveSolver,
-csrc/tri3_hyper_mesh.hip, csrc/quad4_hyper_mesh.hip): the det F-safe step bound and the deformation measure against the numpy
+csrc/mesh_guard.hip): the det F-safe step bound and the deformation measure against the numpy
 closed forms of tests/test_hyper_radapt_host.py, the reduced coordinate gradient against a central difference with Newton
 re-solved on each side, the alternating run's contract (monotone objective, no element and no det F collapses, Newton's
 gradient at the end, untouched rows and .grad), dispatch and refusals, and example 4's --neo-hookean --r-adapt path.

@@ -1,4 +1,4 @@
-"""r-adaptive TRI3 solve (hidenn_fem_amd/radapt.py, csrc/tri3_mesh.hip): the element measure and the step bound against numpy
+"""r-adaptive TRI3 solve (hidenn_fem_amd/radapt.py, csrc/mesh_guard.hip): the element measure and the step bound against numpy
 closed forms, the quality barrier against autograd of the same formula, the reduced coordinate gradient against the dense
 oracle, the P1 patch test, the alternating run's contract (monotone energy, no inversion, untouched rows and .grad), and the
 example's --r-adapt path."""
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import tri_mesh_dict
-from test_radapt_host import step_bound_np
+from test_radapt_host import _measure_np, step_bound_np
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -25,15 +25,6 @@ def _caller_rows(m, d=None):
     out = np.zeros((m.Nnodes, 2))
     out[m._idx_free.cpu().numpy()] = d.detach().double().cpu().numpy()
     return out
-
-
-def _measure_np(X, Xref, conn):
-    P, R = X[conn], Xref[conn]
-    det = lambda T: (T[:, 0, 0] - T[:, 2, 0]) * (T[:, 1, 1] - T[:, 2, 1]) - (T[:, 1, 0] - T[:, 2, 0]) * (T[:, 0, 1] - T[:, 2, 1])
-    d, dr = det(P), det(R)
-    S = sum(((P[:, (i + 1) % 3] - P[:, i]) ** 2).sum(axis=1) for i in range(3))
-    q = 2.0 * math.sqrt(3.0) * np.sign(dr) * d / S
-    return q, d / dr
 
 
 def _perturb(m, scale, seed):

@@ -1,4 +1,4 @@
-"""r-adaptive QUAD4 solve (hidenn_fem_amd/radapt.py Quad4RAdaptiveSolver, csrc/quad4_mesh.hip): the element measure and the
+"""r-adaptive QUAD4 solve (hidenn_fem_amd/radapt.py Quad4RAdaptiveSolver, csrc/mesh_guard.hip): the element measure and the
 step bound against the numpy closed forms of tests/test_radapt_quad4_host.py, the quality barrier against autograd of the same
 formula, the reduced coordinate gradient against the dense QUAD4 oracle, the bilinear patch test, the alternating run's
 contract (monotone objective, no inversion, untouched rows and .grad) and example 4's --quad path.  Tolerances are those of the
@@ -85,77 +85,6 @@ def test_measure_matches_numpy(which):
         m.node_coords_free[row] = torch.tensor(far, dtype=m.node_coords_free.dtype, device=DEV)
     mq, _ = _check_measure(m)
     assert mq.n_inverted >= 1 and mq.min_q <= 0.0
-
-
-def _strip(ne, seed):
-    """A hand-built strip of `ne` cells (nodes (i, j), i = 0..ne, j = 0, 1; id 2 i + j), jittered, every third node a fixed row,
-    the free rows stored in reverse order: (conn [ne, 4] int32, x_src [nn] int32, x_free, x_fixed, X [nn, 2] by node id)."""
-    rng = np.random.default_rng(seed)
-    nn = 2 * (ne + 1)
-    i, j = np.divmod(np.arange(nn), 2)
-    X = np.stack([i.astype(float), j.astype(float)], axis=1) + rng.uniform(-0.2, 0.2, size=(nn, 2))
-    k = np.arange(ne)
-    conn = np.stack([2 * k, 2 * k + 2, 2 * k + 3, 2 * k + 1], axis=1).astype(np.int32)       # counter-clockwise
-    fixed = np.arange(nn) % 3 == 0
-    x_src = np.empty(nn, dtype=np.int32)
-    x_src[fixed] = -1 - np.arange(int(fixed.sum()))
-    nfree = int((~fixed).sum())
-    x_src[~fixed] = nfree - 1 - np.arange(nfree)
-    x_free = np.empty((nfree, 2))
-    x_free[x_src[~fixed]] = X[~fixed]
-    return conn, x_src, x_free, X[fixed].copy(), X
-
-
-@pytest.mark.parametrize("ne", [0, 1, 257])
-def test_c_abi_on_hand_built_arrays_with_fixed_rows(ne):
-    from hidenn_fem_amd import _lib
-    from hidenn_fem_amd._lib import check, ptr, stream_ptr
-    L = _lib.lib()
-    conn, x_src, x_free, x_fixed, X = _strip(max(ne, 1), seed=ne)
-    conn = conn[:ne]
-    rng = np.random.default_rng(100 + ne)
-    Xref = X + rng.uniform(-0.05, 0.05, size=X.shape)
-    dn = rng.normal(size=x_free.shape)
-    t = lambda a, dt=F64: torch.as_tensor(a, dtype=dt).to(DEV).contiguous()
-    st = stream_ptr(DEV)
-    for suffix, dt in (("", F64), ("_f32", torch.float32)):
-        cast = lambda a: t(a, dt).double().cpu().numpy()                  # what the kernel sees of fp32 rows
-        Xk = np.empty_like(X)
-        Xk[x_src >= 0] = cast(x_free)[x_src[x_src >= 0]]
-        Xk[x_src < 0] = cast(x_fixed)[-1 - x_src[x_src < 0]]
-        Rk = cast(Xref)
-        D = np.zeros_like(X)
-        D[x_src >= 0] = dn[x_src[x_src >= 0]]
-        c32, s32, xf, xx, xr, d = t(conn, torch.int32), t(x_src, torch.int32), t(x_free, dt), t(x_fixed, dt), t(Xref, dt), t(dn)
-        q = torch.full((max(ne, 1),), -7.0, dtype=F64, device=DEV)
-        r = torch.full((max(ne, 1),), -7.0, dtype=F64, device=DEV)
-        summ = torch.full((3,), -7.0, dtype=F64, device=DEV)
-        check(getattr(L, "hfem_quad4_mesh_measure" + suffix)(0, ptr(c32), ne, ptr(s32), ptr(xf), ptr(xx), ptr(xr), ptr(q), ptr(r),
-                                                             ptr(summ), st), "measure")
-        alpha = torch.full((), -7.0, dtype=F64, device=DEV)
-        check(getattr(L, "hfem_quad4_step_bound" + suffix)(0, ptr(c32), ne, ptr(s32), ptr(xf), ptr(xx), ptr(d), 0.25, ptr(alpha),
-                                                           st), "bound")
-        val = torch.full((), 3.0, dtype=F64, device=DEV)
-        grad = torch.full((x_free.shape[0], 2), 1.0, dtype=F64, device=DEV)
-        check(getattr(L, "hfem_quad4_quality_barrier" + suffix)(0, ptr(c32), ne, ptr(s32), ptr(xf), ptr(xx), ptr(xr), 0.7,
-                                                                ptr(val), ptr(grad), st), "barrier")
-        summ = summ.tolist()
-        if ne == 0:
-            assert summ[2] == 0.0 and alpha.item() == math.inf and val.item() == 3.0 and (grad == 1.0).all()
-            assert (q == -7.0).all() and (r == -7.0).all()
-            continue
-        wq, wr, winv = quad4_measure_np(Xk[conn], Rk[conn])
-        assert np.abs(q.cpu().numpy() - wq).max() <= 1e-13 * np.abs(wq).max()
-        assert np.abs(r.cpu().numpy() - wr).max() <= 1e-13 * np.abs(wr).max()
-        assert summ[0] == q.min().item() and summ[1] == r.min().item() and summ[2] == float(winv.sum()) == 0.0
-        wa, *_ = quad4_step_bound_np(Xk[conn], D[conn], 0.25)
-        assert math.isfinite(wa.min()) and abs(alpha.item() - wa.min()) <= 1e-12 * wa.min()
-        wv, wg = _barrier_torch(torch.as_tensor(Xk), torch.as_tensor(Rk), torch.as_tensor(conn).long(),
-                                torch.as_tensor(np.nonzero(x_src >= 0)[0]), 0.7)
-        got_g = np.zeros_like(X)
-        got_g[x_src >= 0] = (grad.cpu().numpy() - 1.0)[x_src[x_src >= 0]]       # ACCUMULATED onto the ones
-        assert abs(val.item() - 3.0 - wv) <= 1e-11 * abs(wv)
-        assert np.abs(got_g[x_src >= 0] - wg.numpy()).max() <= 1e-11 * wg.abs().max().item()
 
 
 # ---------------------------------------------------------------- 2. step bound

@@ -2,7 +2,7 @@
 oracles tests/test_gpu_hyper_radapt.py checks the kernels against) agree with a brute-force scan of det F(alpha) - eta det F(0)
 and of R(alpha) - eta R(0); the QUAD4 bound guarantees what DESIGN 22 says it does; the eight entry points are exported, bound
 and prototyped; argument errors come back as negative codes with a message before any device is touched; the Python API
-refuses what it does not support and dispatches on the loss; and csrc/hfem_hyper_mesh_dev.h runs clean under the address and
+refuses what it does not support and dispatches on the loss; and csrc/hfem_mesh_elem_dev.h runs clean under the address and
 undefined-behaviour sanitizers as a stand-alone host program."""
 import ctypes as C
 import math
@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_radapt_host import step_bound_np
-from test_radapt_quad4_host import _jittered_unit_cells, quad4_corners_np
+from test_radapt_host import _measure_np, step_bound_np
+from test_radapt_quad4_host import _jittered_unit_cells, quad4_corners_np, quad4_measure_np
 
 HYPER_MESH_SYMBOLS = ["hfem_tri3_hyper_step_bound", "hfem_tri3_deformation_measure", "hfem_quad4_hyper_step_bound",
                       "hfem_quad4_deformation_measure"]
@@ -86,6 +86,38 @@ def det_f_np(X, U):
 def quad4_corner_ratios_np(X, U):
     """r [Ne, 4] = c_k^def / c_k; a cell's J is r.min(axis=1)."""
     return quad4_corners_np(X + U)[0] / quad4_corners_np(X)[0]
+
+
+def barrier_terms_torch(P, R, weight):
+    """[Ne] tensor: an element's share of Q = (w / (terms Ne)) sum (1/q - 1) (TRI3: terms = 1, q = 2 sqrt(3) s detJ / sum |e|^2;
+    QUAD4: terms = 4, the sum runs over the corners, q_k = 2 s c_k / (|e_k-1|^2 + |e_k|^2)), as hidenn_fem_amd/radapt.py states
+    it.  P, R: [Ne, 3 or 4, 2] fp64 tensors, the current and the reference corner rows; differentiable in P."""
+    cross = lambda a, b: a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+    ne, npe = P.shape[0], P.shape[1]
+    if npe == 3:
+        det = lambda T: cross(T[:, 0] - T[:, 2], T[:, 1] - T[:, 2])
+        S = sum(((P[:, (i + 1) % 3] - P[:, i]) ** 2).sum(dim=1) for i in range(3))
+        q = 2.0 * math.sqrt(3.0) * torch.sign(det(R)) * det(P) / S
+        return weight / ne * (1.0 / q - 1.0)
+
+    def corners(T):
+        a, b = torch.roll(T, -1, dims=1) - T, torch.roll(T, 1, dims=1) - T
+        return cross(a, b), (a ** 2).sum(dim=-1) + (b ** 2).sum(dim=-1)
+
+    c, S = corners(P)
+    cr, _ = corners(R)
+    q = 2.0 * torch.sign(cr[:, 0] + cr[:, 2])[:, None] * c / S
+    return weight / (4.0 * ne) * (1.0 / q - 1.0).sum(dim=1)
+
+
+def barrier_torch(X, Xr, conn, idx_free, weight):
+    """(Q, dQ/d(rows idx_free of X)) by autograd on the CPU; X, Xr [Nn, 2] fp64 tensors, conn [Ne, 3 or 4] long."""
+    xf = X[idx_free].clone().requires_grad_(True)
+    full = X.clone()
+    full[idx_free] = xf
+    Q = barrier_terms_torch(full[conn], Xr[conn], weight).sum()
+    (g,) = torch.autograd.grad(Q, xf)
+    return Q.item(), g
 
 
 def kind_of(ref, dfc):
@@ -426,10 +458,12 @@ def test_the_finite_strain_classes_run_the_small_strain_loop():
 
 # ---------------------------------------------------------------- the closed forms under the sanitizers
 def test_hyper_mesh_closed_forms_under_address_and_ub_sanitizers(tmp_path):
-    """csrc/hfem_hyper_mesh_dev.h (the text the kernels compile) as plain C++ against the stub <hip/hip_runtime.h>, built with
+    """csrc/hfem_mesh_elem_dev.h (the text the kernels compile) as plain C++ against the stub <hip/hip_runtime.h>, built with
     -fsanitize=address,undefined and run as a child process: both crossings and J of every element within 1e-12 of this
-    module's numpy values -- random valid triangles and cells, plus an inverted element and a zero direction of each kind.
-    CPU only."""
+    module's numpy values -- random valid triangles and cells, plus an inverted element and a zero direction of each kind --
+    and, at the rows X + U against the reference rows X, the measure (q, ratio within 1e-12, the inverted flag) against the
+    numpy forms and each element's barrier term and per-node gradient against CPU autograd (1e-11; the program's header has the
+    rule).  CPU only."""
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     here = os.path.dirname(os.path.abspath(__file__))
@@ -442,7 +476,7 @@ def test_hyper_mesh_closed_forms_under_address_and_ub_sanitizers(tmp_path):
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr
     rng = np.random.default_rng(7)
-    eta = 0.3
+    eta, weight = 0.3, 0.7
     X3, U3, D3 = _random_triangles(200, rng)
     X4, U4, D4 = _random_cells(200, rng)
     for X, U, D in ((X3, U3, D3), (X4, U4, D4)):
@@ -454,11 +488,25 @@ def test_hyper_mesh_closed_forms_under_address_and_ub_sanitizers(tmp_path):
     assert np.isinf(ref3[0]) and np.isinf(def3[0]) and np.isinf(ref4[0]) and np.isinf(def4[0])
     assert J3[1] < 0.0 and def3[1] == 0.0 and J4[1] < 0.0 and def4[1] == 0.0
     assert (J3[2:] > 0.0).all() and (J4[2:] > 0.0).all()
+    # the measure of the rows X + U against the rows X: each element its own three / four nodes
+    n3, n4 = X3.shape[0], X4.shape[0]
+    q3, r3 = _measure_np((X3 + U3).reshape(-1, 2), X3.reshape(-1, 2), np.arange(3 * n3).reshape(n3, 3))
+    inv3 = ~(q3 > 0.0)                                               # s detJ(X + U) <= 0: q carries that sign
+    q4, r4, inv4 = quad4_measure_np(X4 + U4, X4)
+    assert inv3[1] and inv4[1] and not inv3[2:].any() and not inv4[2:].any()
+    assert np.array_equal(inv3, J3 <= 0.0) and np.array_equal(r4, J4)
+    barrier = []
+    for X, U in ((X3, U3), (X4, U4)):
+        P = torch.as_tensor(X + U).requires_grad_(True)
+        terms = barrier_terms_torch(P, torch.as_tensor(X), weight)
+        (G,) = torch.autograd.grad(terms.sum(), P)
+        barrier.append((terms.detach().numpy(), G.numpy()))
+    assert all(np.isfinite(Q).all() and np.isfinite(G).all() and (Q[2:] > 0.0).all() for Q, G in barrier)
     path = str(tmp_path / "case.bin")
     with open(path, "wb") as f:
-        f.write(struct.pack("<2q", X3.shape[0], X4.shape[0]))
-        f.write(struct.pack("<d", eta))
-        for a in (X3, U3, D3, ref3, def3, J3, X4, U4, D4, ref4, def4, J4):
+        f.write(struct.pack("<2q", n3, n4))
+        f.write(struct.pack("<2d", eta, weight))
+        for a in (X3, U3, D3, ref3, def3, J3, q3, r3, inv3, *barrier[0], X4, U4, D4, ref4, def4, J4, q4, r4, inv4, *barrier[1]):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
     run = subprocess.run([exe, path], capture_output=True, text=True)
     print(run.stdout.strip())

@@ -91,10 +91,19 @@ def test_python_api_refuses_quad4_deterministic_losses_and_a_bad_eta():
                 fn(tri)
 
 
-# ---------------------------------------------------------------- the numpy oracle of the step bound
+# ---------------------------------------------------------------- the numpy oracles of the measure and the step bound
+def _measure_np(X, Xref, conn):
+    P, R = X[conn], Xref[conn]
+    det = lambda T: (T[:, 0, 0] - T[:, 2, 0]) * (T[:, 1, 1] - T[:, 2, 1]) - (T[:, 1, 0] - T[:, 2, 0]) * (T[:, 0, 1] - T[:, 2, 1])
+    d, dr = det(P), det(R)
+    S = sum(((P[:, (i + 1) % 3] - P[:, i]) ** 2).sum(axis=1) for i in range(3))
+    q = 2.0 * math.sqrt(3.0) * np.sign(dr) * d / S
+    return q, d / dr
+
+
 def step_bound_np(X, D, eta):
     """Per element: the smallest alpha > 0 with detJ(X + alpha D) = eta detJ(X) (inf if none; 0 if detJ(X) = 0).  X, D: [Ne, 3, 2]
-    corner rows.  The same closed form as csrc/tri3_mesh.hip, written independently over arrays."""
+    corner rows.  The same closed form as csrc/hfem_mesh_elem_dev.h, written independently over arrays."""
     a = X[:, 0] - X[:, 2]
     b = X[:, 1] - X[:, 2]
     da = D[:, 0] - D[:, 2]

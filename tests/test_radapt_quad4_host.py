@@ -153,7 +153,7 @@ def quad4_measure_np(X, Xref):
 def quad4_step_bound_np(X, D, eta):
     """Per element: the smallest alpha > 0 at which some corner has c_k(X + alpha D) = eta c_k(X) (inf if none; 0 if some
     c_k(X) = 0).  X, D: [Ne, 4, 2] corner rows.  Returns (bound [Ne], A0, A1, A2 [Ne, 4]) with c_k(alpha) = A0 + A1 alpha +
-    A2 alpha^2.  The closed form of csrc/hfem_mesh_dev.h first_crossing, written independently over arrays."""
+    A2 alpha^2.  The closed form of csrc/hfem_crossing_dev.h first_crossing, written independently over arrays."""
     a, b = np.roll(X, -1, axis=1) - X, np.roll(X, 1, axis=1) - X
     da, db = np.roll(D, -1, axis=1) - D, np.roll(D, 1, axis=1) - D
     cr = lambda p, r: p[..., 0] * r[..., 1] - p[..., 1] * r[..., 0]
