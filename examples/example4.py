@@ -131,7 +131,7 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
 
 
 def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3, newton=False,
-                    precond="block_jacobi", quad=False, r_adapt=False, outer=10):
+                    precond="block_jacobi", quad=False, r_adapt=False, outer=10, error_estimate=False):
     """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
     clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
     of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
@@ -152,7 +152,11 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     iterations of the finite-strain r-adaptive solve there (``hidenn_fem_amd.radapt.r_adapt_``: ``HyperRAdaptiveSolver`` /
     ``Quad4HyperRAdaptiveSolver`` -- Newton-Krylov with ``precond`` for ``u``, coordinate steps bounded so that neither an
     element nor its ``det F`` collapses); prints energy, min J, min q and the Newton / CG counts per outer iteration and the
-    energy gained over the frozen mesh, and returns the r-adapted energy."""
+    energy gained over the frozen mesh, and returns the r-adapted energy.
+    ``error_estimate=True`` (``--error-estimate``): after every converged load increment one line with the relative ZZ error
+    indicator eta_rel, min J and the largest nodal von Mises stress of the recovered CAUCHY stress
+    (``hidenn_fem_amd.post.HyperStressRecovery`` -- an indicator, not an estimate, away from small strain: DESIGN 24); with
+    ``r_adapt`` also on the frozen mesh and on the r-adapted one, all from one reused object."""
     newton = newton or r_adapt
     from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
@@ -201,6 +205,7 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
         ginf = float("inf") if not info.converged else info.grad_norm       # an unconverged increment is taken back
         return info.energy, info.min_J, 0 if info.converged else 1, ginf, info, s.amg if precond == "amg_tangent" else None
 
+    recovery = None
     done, inc, first = 0.0, 1.0 / load_steps, True
     energy = float("nan")
     prev, prev_load = torch.zeros_like(model.u_free), 0.0          # the accepted state before the last one (secant predictor)
@@ -239,18 +244,34 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
             gap = (model.u_free.detach() - u_lin).abs().max().item() / u_lin.abs().max().item()
             print(f"load {target:.4f}: gap to the linear frozen-mesh solution max|u - u_lin| / max|u_lin| = {gap:.3e}")
             first = False
+        if error_estimate:
+            recovery = _print_hyper_error(model, loss_fn, f"at load {target:.4f}", recovery)
     if r_adapt:
         if done < 1.0 - 1e-12:
             raise RuntimeError(f"example 4: the load ramp stopped at {done:.4f}; no r-adaptation below the full load")
-        return _r_adapt_neo_hookean(model, loss_fn, traction(1.0), outer, precond)
+        return _r_adapt_neo_hookean(model, loss_fn, traction(1.0), outer, precond, recovery)
     return model, energy
 
 
-def _r_adapt_neo_hookean(model, loss_fn, t_force, outer, precond):
+def _print_hyper_error(model, loss_fn, when, recovery=None):
+    """One line with the finite-strain ZZ indicator; returns the ``HyperStressRecovery`` (reusable: the connectivity never
+    changes, coordinates and displacements are read on every call)."""
+    from hidenn_fem_amd.post import HyperStressRecovery
+    recovery = recovery or HyperStressRecovery(model, loss_fn)
+    err = recovery.error()
+    s = err.nodal_stress
+    vm = torch.sqrt(s[:, 0] ** 2 - s[:, 0] * s[:, 1] + s[:, 1] ** 2 + 3.0 * s[:, 2] ** 2).max().item()
+    print(f"ZZ error indicator {when}: eta_rel {err.relative:.6e} min_J {err.min_J:.4f} max nodal von Mises {vm:.6e}")
+    return recovery
+
+
+def _r_adapt_neo_hookean(model, loss_fn, t_force, outer, precond, recovery=None):
     import time
     from hidenn_fem_amd.radapt import mesh_quality, quad4_mesh_quality, r_adapt_
     quality = quad4_mesh_quality if getattr(model, "nodes_per_element", 3) == 4 else mesh_quality
     model.node_coords_free.requires_grad_(True)                    # the ramp froze the mesh
+    if recovery is not None:
+        _print_hyper_error(model, loss_fn, "on the frozen mesh", recovery)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     info = r_adapt_(model, loss_fn, t_force=t_force, max_outer=outer, precond=precond)     # (Quad4)HyperRAdaptiveSolver
@@ -266,6 +287,8 @@ def _r_adapt_neo_hookean(model, loss_fn, t_force, outer, precond):
     print(f"r-adapted energy {info.energy[-1]:.9e} after {info.iterations} outer iterations ({info.reason}), "
           f"min J {info.min_J[-1]:.4f}, min q {mq.min_q:.4f}, inverted elements {mq.n_inverted}, {time.perf_counter() - t0:.3f} s")
     print(f"energy gained over the frozen mesh {gain:.6e} ({gain / abs(info.energy[0]):.3e} of |Pi*|)")
+    if recovery is not None:
+        _print_hyper_error(model, loss_fn, "on the r-adapted mesh", recovery)
     return model, info.energy[-1]
 
 
@@ -323,7 +346,8 @@ if __name__ == "__main__":
                     help="CG preconditioner of --solve-first, --r-adapt and --neo-hookean --newton (amg_tangent: the latter only)")
     ap.add_argument("--error-estimate", action="store_true",
                     help="print the relative ZZ error estimate after the solve (with --r-adapt: before and after adaptation); "
-                         "builds the loss with grad_convention='physical'")
+                         "builds the loss with grad_convention='physical'.  With --neo-hookean: the finite-strain indicator on "
+                         "the recovered Cauchy stress after every load increment (and before and after --r-adapt)")
     ap.add_argument("--neo-hookean", action="store_true",
                     help="the plate at finite strain: Neo-Hookean material, load ramped in steps, FusedLBFGS on u_free (fp64)")
     ap.add_argument("--load-steps", type=int, default=8, help="load increments of --neo-hookean")
@@ -335,7 +359,7 @@ if __name__ == "__main__":
         ap.error("--precond amg_tangent needs --neo-hookean with --newton or --r-adapt (with or without --quad)")
     if a.neo_hookean:
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad,
-                        r_adapt=a.r_adapt, outer=a.outer or 10)
+                        r_adapt=a.r_adapt, outer=a.outer or 10, error_estimate=a.error_estimate)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,

@@ -276,7 +276,8 @@ class NeoHookeanLoss2D(EnergyLoss2D):
     the last launch wrote, ``{min J, number of elements with J <= 0}``: the same tensor on every call, no host sync.
 
     fp32 models: float rows widened on load, fp64 arithmetic, one rounding on store.  Not available: ``deterministic=True``,
-    ``arithmetic="fp32"``, QUAD4 models (they take ``Quad4NeoHookeanLoss2D``), ``FrozenMeshSolver`` / ``StressRecovery`` (they are linear)."""
+    ``arithmetic="fp32"``, QUAD4 models (they take ``Quad4NeoHookeanLoss2D``), ``FrozenMeshSolver`` / ``StressRecovery`` (they are linear;
+    the stress of this material: ``hidenn_fem_amd.post.HyperStressRecovery``)."""
 
     def __init__(self, E: float = 10e9, nu: float = 0.3, length: float = 1.0, height: float = 1.0,
                  gauss_order: int = 4, gauss_order_1d: int = 2, device: Optional[torch.device] = None,
@@ -450,7 +451,8 @@ def require_linear(loss_fn, who: str):
         raise NotImplementedError(f"{who}: small-strain linear elasticity only; a NeoHookeanLoss2D would be linearised "
                                   "silently -- its equilibrium is hidenn_fem_amd.newton.NewtonKrylovSolver / newton_solve_ "
                                   "(Newton-Krylov on the tangent; QUAD4 models: Quad4NewtonKrylovSolver / quad4_newton_solve_); "
-                                  "or pass an EnergyLoss2D")
+                                  "its stress is hidenn_fem_amd.post.HyperStressRecovery / recover_cauchy_stress / "
+                                  "hyper_zz_error; or pass an EnergyLoss2D")
 
 
 # ---------------------------------------------------------------- inline losses of examples 1-3

@@ -8,7 +8,9 @@
 
 No reference counterpart: ``StressRecovery`` / ``recover_stress`` / ``zz_error`` -- the nodal (smoothed) stress
 by lumped L2 projection and the Zienkiewicz-Zhu energy-norm error estimate built on it, TRI3 and QUAD4 models
-(csrc/recover.hip); ``von_mises`` of a QUAD4 model is taken at the cell centre.
+(csrc/recover.hip); ``von_mises`` of a QUAD4 model is taken at the cell centre.  Their finite-strain twins:
+``HyperStressRecovery`` / ``recover_cauchy_stress`` / ``hyper_zz_error`` -- the recovered Cauchy stress of a Neo-Hookean
+model and a ZZ indicator on it, the same kernels with another stress law.
 """
 from __future__ import annotations
 
@@ -197,3 +199,124 @@ def recover_stress(model, loss_fn) -> torch.Tensor:
 def zz_error(model, loss_fn) -> ZZError:
     """One-shot ``StressRecovery(model, loss_fn).error()``."""
     return StressRecovery(model, loss_fn).error()
+
+
+# ---------------------------------------------------------------- Cauchy stress recovery, ZZ indicator at finite strain (DESIGN 24)
+@dataclass
+class HyperZZError(ZZError):
+    """Result of ``HyperStressRecovery.error()``: ``ZZError``'s fields (``nodal_stress`` is the recovered CAUCHY stress) plus
+    ``min_J`` = min det F over all points and ``inverted`` = the number of inverted elements.  With ``inverted > 0`` those
+    elements' ``eta2`` is ``+inf``, ``eta`` is ``inf`` and ``relative`` is 1.0.  The four scalars come from one device read."""
+    min_J: float = float("nan")
+    inverted: int = 0
+
+
+class HyperStressRecovery:
+    """Recovered nodal Cauchy stress and a ZZ error indicator of a finite-strain model: a ``NeoHookeanLoss2D`` on a TRI3 model
+    or a ``Quad4NeoHookeanLoss2D`` on a QUAD4 model (the same kernels as ``StressRecovery`` with another stress law,
+    csrc/recover.hip).
+
+    ``(lambda, mu) = loss_fn.lame``; per point ``H = G J^-1`` (always the physical gradient), ``F = I + H``,
+    ``j = tr H + det H = det F - 1`` and ``sigma_h = (mu (H + H^T + H H^T) + lambda log1p(j) I) / (1 + j)`` -- the Cauchy stress
+    ``P F^T / det F`` of the energy the model was solved with, in a cancellation-free form.  Points and weights are
+    ``StressRecovery``'s, taken on the reference configuration, and so is the lumped L2 projection; ``return_J`` gives the
+    same projection of ``det F``.  ``error()``: ``eta_e^2 = int_e (sigma* - sigma_h).S.(sigma* - sigma_h) dX`` and
+    ``||sigma_h||^2 = int sigma_h.S.sigma_h dX`` with ``S = C0^-1``, ``C0`` the linearisation of the material at ``F = I``
+    (``c11 = c22 = lambda + 2 mu, c12 = lambda, c33 = mu``; ``plane="stress"``: ``EnergyLoss2D.C`` entry for entry).
+
+    * IT IS AN INDICATOR, NOT AN ESTIMATE, AWAY FROM SMALL STRAIN: ``S`` is the compliance at the undeformed state, so ``eta`` is
+      no bound of an error in an energy norm of the deformed body; it says where the stress jumps between elements.
+    * It reduces to the linear ZZ estimate of ``EnergyLoss2D(grad_convention="physical")`` as ``u -> 0``.
+    * It is exactly zero for a homogeneous deformation, and unchanged by a superposed rigid rotation because ``S`` is isotropic
+      (the recovered stress turns with the body: ``sigma* -> Q sigma* Q^T``).
+
+    Inverted elements (``det F <= 0`` or NaN at a point; a QUAD4 cell when any of its four points is): weight 0 in the
+    projection, ``eta_e^2 = +inf``, nothing added to ``||sigma_h||^2``; a node all of whose elements are inverted gets zeros and
+    lumped area 0; ``relative`` is 1.0.  No NaN arises from finite inputs.
+
+    The adjacency is built and uploaded once; ``model.coords`` / ``model.u_full`` are read on every call, so one object stays
+    valid across r-adaptive steps and load increments.  fp32 models are widened on the way in and get fp32 results back."""
+
+    def __init__(self, model, loss_fn):
+        from .loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
+        npe = getattr(model, "nodes_per_element", 3)
+        if not isinstance(loss_fn, NeoHookeanLoss2D):
+            raise NotImplementedError("HyperStressRecovery: a NeoHookeanLoss2D (TRI3) or Quad4NeoHookeanLoss2D (QUAD4); the "
+                                      "small-strain stress of an EnergyLoss2D is hidenn_fem_amd.post.StressRecovery")
+        if npe not in (3, 4) or not hasattr(model, "_conn32"):
+            raise NotImplementedError("HyperStressRecovery: TRI3 and QUAD4 mesh models")
+        if isinstance(loss_fn, Quad4NeoHookeanLoss2D) != (npe == 4):
+            raise NotImplementedError("HyperStressRecovery: NeoHookeanLoss2D goes with a TRI3 model, Quad4NeoHookeanLoss2D with "
+                                      f"a QUAD4 model (got {type(loss_fn).__name__} and {npe} nodes per element)")
+        self.model, self.loss_fn, self.npe = model, loss_fn, npe
+        dev = model.node_coords_free.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"hidenn_fem_amd: model is on {dev}; the recovery kernels need a ROCm device. "
+                               "There is no CPU fallback -- call model.to('cuda').")
+        self.device = dev
+        adj_ptr, adj = node_adjacency(model._conn32, model.Nnodes)
+        self._adj_ptr, self._adj = adj_ptr.to(dev), adj.to(dev)
+        self._partials = torch.empty(4 * max((model.Nelems + 255) // 256, 1), dtype=F64, device=dev)
+        self._lame = (C.c_double * 2)(*loss_fn.lame)
+        L = _lib.lib()
+        self._recover = L.hfem_quad4_hyper_stress_recover if npe == 4 else L.hfem_tri3_hyper_stress_recover
+        self._zz = L.hfem_quad4_hyper_zz_error if npe == 4 else L.hfem_tri3_hyper_zz_error
+        self._name = "quad4" if npe == 4 else "tri3"
+
+    def _inputs(self):
+        m = self.model
+        X, U = m.coords.detach(), m.u_full.detach()
+        require_gpu_tensor(X.contiguous(), "model.coords", dtype=None)
+        return X.dtype, X.to(F64).contiguous(), U.to(F64).contiguous()
+
+    def _nodal(self, X64, U64, J, area):
+        m = self.model
+        sig = torch.empty(m.Nnodes, 3, dtype=F64, device=self.device)
+        check(self._recover(_lib.dev_index(self.device), ptr(X64), ptr(U64), ptr(m._conn32), m.Nelems, m.Nnodes,
+                            ptr(self._adj_ptr), ptr(self._adj), self._lame, ptr(sig), ptr(J), ptr(area),
+                            stream_ptr(self.device)), f"hfem_{self._name}_hyper_stress_recover")
+        return sig
+
+    def nodal_stress(self, return_area: bool = False, return_J: bool = False):
+        """Recovered Cauchy stress ``[Nnodes, 3]`` = (sxx, syy, sxy) by node id; then, as asked, the lumped nodal areas
+        ``[Nnodes]`` (reference configuration) and the recovered ``det F`` ``[Nnodes]``, in that order."""
+        with torch.no_grad():
+            dt, X64, U64 = self._inputs()
+            nn = self.model.Nnodes
+            area = torch.empty(nn, dtype=F64, device=self.device) if return_area else None
+            J = torch.empty(nn, dtype=F64, device=self.device) if return_J else None
+            out = (self._nodal(X64, U64, J, area).to(dt),)
+            out += (area.to(dt),) if return_area else ()
+            out += (J.to(dt),) if return_J else ()
+            return out if len(out) > 1 else out[0]
+
+    def nodal_von_mises(self):
+        """Plane-stress von Mises of the recovered Cauchy stress, ``[Nnodes]``."""
+        s = self.nodal_stress()
+        return torch.sqrt(s[:, 0] ** 2 - s[:, 0] * s[:, 1] + s[:, 1] ** 2 + 3.0 * s[:, 2] ** 2)
+
+    def error(self) -> HyperZZError:
+        with torch.no_grad():
+            m = self.model
+            dt, X64, U64 = self._inputs()
+            sig = self._nodal(X64, U64, None, None)
+            eta2 = torch.empty(m.Nelems, dtype=F64, device=self.device)
+            totals = torch.zeros(4, dtype=F64, device=self.device)
+            check(self._zz(_lib.dev_index(self.device), ptr(X64), ptr(U64), ptr(m._conn32), m.Nelems, ptr(sig), self._lame,
+                           ptr(eta2), None, ptr(self._partials), ptr(totals), stream_ptr(self.device)),
+                  f"hfem_{self._name}_hyper_zz_error")
+            e2, n2, min_j, count = totals.tolist()
+            count = int(count)
+            rel = 1.0 if count > 0 else ((e2 / (n2 + e2)) ** 0.5 if n2 + e2 > 0.0 else 0.0)
+            return HyperZZError(eta2=eta2.to(dt), energy_norm2=n2, eta=e2 ** 0.5, relative=rel, nodal_stress=sig.to(dt),
+                                min_J=min_j, inverted=count)
+
+
+def recover_cauchy_stress(model, loss_fn) -> torch.Tensor:
+    """One-shot ``HyperStressRecovery(model, loss_fn).nodal_stress()``."""
+    return HyperStressRecovery(model, loss_fn).nodal_stress()
+
+
+def hyper_zz_error(model, loss_fn) -> HyperZZError:
+    """One-shot ``HyperStressRecovery(model, loss_fn).error()``."""
+    return HyperStressRecovery(model, loss_fn).error()

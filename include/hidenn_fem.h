@@ -941,6 +941,31 @@ int hfem_cg_start_amg(hfem_cg *cg, hfem_amg *amg, const double *g0, const double
                       int64_t max_iter, void *stream);
 int hfem_cg_iterate_amg(hfem_cg *cg, hfem_amg *amg, double *u_free, int32_t n_iter, void *stream);
 
+/* ------------------------------------------------------------------ Cauchy stress recovery and a ZZ indicator at finite strain
+ * No reference counterpart.  The arrays, the points, the weights (on the REFERENCE configuration), the adjacency and the
+ * lumped projection of hfem_*_stress_recover / hfem_*_zz_error, with the stress of the Neo-Hookean material of
+ * hfem_*_hyper_energy_plan: lame[2] = (lambda, mu) (HOST pointer, mu > 0 and lambda + mu > 0), per point H = G J^-1 (always the
+ * physical gradient), j = tr H + det H (= det F - 1), L = log1p(j) and the Cauchy stress
+ *   sigma_h = (mu (H + H^T + H H^T) + lambda L I) / (1 + j)  ->  (sxx, syy, sxy).
+ * S = C0^-1 with C0 the linearisation at F = I (c11 = c22 = lambda + 2 mu, c12 = lambda, c33 = mu): an INDICATOR, not an
+ * estimate, away from small strain.  nodal_J[Nn] (optional, NULL) = the same projection of 1 + j.
+ * An element is inverted when j <= -1 or j is NaN at any of its points: it is evaluated at j = 0, has weight 0 in the projection
+ * (a node with no other element gets zeros and area 0), eta2 = +inf and norm2 = 0.
+ * totals[4] = {sum eta2, sum norm2, min over all points of 1 + j, number of inverted elements}; partials: caller-owned workspace of
+ * 4 * ceil(Ne / 256) doubles.  Launch-only (capturable).  Ne == 0 (or Nn == 0) returns 0 without touching a device. */
+int hfem_tri3_hyper_stress_recover(int device, const double *X, const double *U, const int32_t *conn, int64_t ne, int64_t nn,
+                                   const int32_t *adj_ptr, const int32_t *adj, const double lame[2], double *nodal_stress,
+                                   double *nodal_J, double *nodal_area, void *stream);
+int hfem_quad4_hyper_stress_recover(int device, const double *X, const double *U, const int32_t *conn, int64_t ne, int64_t nn,
+                                    const int32_t *adj_ptr, const int32_t *adj, const double lame[2], double *nodal_stress,
+                                    double *nodal_J, double *nodal_area, void *stream);
+int hfem_tri3_hyper_zz_error(int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
+                             const double *nodal_stress, const double lame[2], double *eta2, double *norm2, double *partials,
+                             double *totals, void *stream);
+int hfem_quad4_hyper_zz_error(int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
+                              const double *nodal_stress, const double lame[2], double *eta2, double *norm2, double *partials,
+                              double *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
