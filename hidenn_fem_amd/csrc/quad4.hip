@@ -674,11 +674,11 @@ using namespace hfem;
 extern "C" int hfem_quad4_energy_atomic(int device, const double *X, const double *U, const int32_t *conn,
                                         int64_t e_begin, int64_t e_end, int64_t nn, const double mat[4],
                                         double *loss_acc, double *gX, double *gU, void *stream) {
-    HFEM_ARG_CHECK(X && U && conn && mat && loss_acc, "null pointer");
     HFEM_ARG_CHECK(e_begin >= 0 && e_end >= e_begin && nn >= 0, "bad element range");
     HFEM_ARG_CHECK((gX == nullptr) == (gU == nullptr), "gX and gU must both be given or both NULL");
+    if (e_end == e_begin) return 0;   // an empty range reads nothing: every pointer may be NULL, as for the per-point entries
+    HFEM_ARG_CHECK(X && U && conn && mat && loss_acc, "null pointer");
     if (int rc = use_device(device)) return rc;
-    if (e_end == e_begin) return 0;
     Tri3Consts k;
     k.c11 = mat[0]; k.c12 = mat[1]; k.c22 = mat[2]; k.c33 = mat[3];
     k.W = 1.0;

@@ -701,11 +701,11 @@ extern "C" int hfem_tri3_energy_atomic(int device, const double *X, const double
                                        int64_t e_begin, int64_t e_end, int64_t nn, const double mat[4],
                                        double W, const double Bk[6], double *loss_acc, double *gX,
                                        double *gU, void *stream) {
-    HFEM_ARG_CHECK(X && U && conn && mat && loss_acc, "null pointer");
     HFEM_ARG_CHECK(e_begin >= 0 && e_end >= e_begin && nn >= 0, "bad element range");
     HFEM_ARG_CHECK((gX == nullptr) == (gU == nullptr), "gX and gU must both be given or both NULL");
+    if (e_end == e_begin) return 0;   // an empty range reads nothing: every pointer may be NULL, as for the per-point entries
+    HFEM_ARG_CHECK(X && U && conn && mat && loss_acc, "null pointer");
     if (int rc = use_device(device)) return rc;
-    if (e_end == e_begin) return 0;
     hipLaunchKernelGGL(tri3_energy_atomic_kernel, dim3(grid_for(e_end - e_begin)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const double2 *)X, (const double2 *)U, conn, e_begin, e_end,
                        make_consts(mat, W, Bk), loss_acc, gX, gU);
@@ -715,12 +715,12 @@ extern "C" int hfem_tri3_energy_atomic(int device, const double *X, const double
 extern "C" int hfem_edge2_energy_atomic(int device, const double *X, const double *U, const int32_t *edges,
                                         int64_t ned, const double *T, const double Tconst[4],
                                         double *loss_acc, double *gX, double *gU, void *stream) {
-    HFEM_ARG_CHECK(X && U && loss_acc && (edges || ned == 0), "null pointer");
-    HFEM_ARG_CHECK(T || Tconst, "need a per-edge traction table or a constant one");
     HFEM_ARG_CHECK(ned >= 0, "negative edge count");
     HFEM_ARG_CHECK((gX == nullptr) == (gU == nullptr), "gX and gU must both be given or both NULL");
+    if (ned == 0) return 0;           // no edge reads nothing: every pointer may be NULL
+    HFEM_ARG_CHECK(X && U && edges && loss_acc, "null pointer");
+    HFEM_ARG_CHECK(T || Tconst, "need a per-edge traction table or a constant one");
     if (int rc = use_device(device)) return rc;
-    if (ned == 0) return 0;
     const double4 tc = Tconst ? make_double4(Tconst[0], Tconst[1], Tconst[2], Tconst[3]) : make_double4(0, 0, 0, 0);
     hipLaunchKernelGGL(edge2_energy_atomic_kernel, dim3(grid_for(ned)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const double2 *)X, (const double2 *)U, edges, ned, (const double4 *)T, tc, loss_acc,

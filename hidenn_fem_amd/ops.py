@@ -294,8 +294,11 @@ class Edge2EvalFn(torch.autograd.Function):
         Xd, Ud, edges32, xd, eid = ctx.saved_tensors
         dev = Xd.device
         gX, gU = torch.zeros_like(Xd), torch.zeros_like(Ud)
+        # named, so that a widened / materialised copy (fp32 model, expanded cotangent of a .sum()) lives until the launch:
+        # as a temporary it is freed once its pointer is taken, and the next copy may be given the same block
+        cu, cds = _f64(cu, "cu"), _f64(cds, "cds")
         check(_lib.lib().hfem_edge2_eval_bwd(dev_index(dev), ptr(Xd), ptr(Ud), ptr(edges32), ptr(xd), ptr(eid),
-                                             eid.shape[0], ptr(_f64(cu, "cu")), ptr(_f64(cds, "cds")), ptr(gX),
+                                             eid.shape[0], ptr(cu), ptr(cds), ptr(gX),
                                              ptr(gU), stream_ptr(dev)), "hfem_edge2_eval_bwd")
         return gX.to(ctx.dt), gU.to(ctx.dt), None, None, None
 
@@ -474,8 +477,9 @@ class RectQ4EvalFn(torch.autograd.Function):
         ggy = torch.zeros_like(gyd) if ctx.needs_input_grad[1] else None
         gu = torch.zeros_like(ud) if ctx.needs_input_grad[2] else None
         gxe = torch.empty_like(xd) if ctx.needs_input_grad[3] else None
+        g = _as(g, "grad", ud.dtype)                                          # named: alive until the launch (see Edge2EvalFn)
         check(getattr(_lib.lib(), "hfem_rectq4_eval_bwd" + ctx.suf)(dev_index(dev), ptr(gxd), gxd.shape[0], ptr(gyd), gyd.shape[0],
-                                                                    ptr(ud), ptr(xd), xd.shape[0], ptr(_as(g, "grad", ud.dtype)),
+                                                                    ptr(ud), ptr(xd), xd.shape[0], ptr(g),
                                                                     ptr(ggx), ptr(ggy), ptr(gu), ptr(gxe), stream_ptr(dev)),
               "hfem_rectq4_eval_bwd")
         d = ctx.dts
@@ -564,8 +568,9 @@ class Quad4EvalFn(torch.autograd.Function):
         Xd, Ud, conn32, xe, eid = ctx.saved_tensors
         dev = Xd.device
         gX, gU = torch.zeros_like(Xd), torch.zeros_like(Ud)
+        cu, cd, cg = _f64(cu, "cu"), _f64(cd, "cd"), _f64(cg, "cg")      # named: alive until the launch (see Edge2EvalFn)
         check(_lib.lib().hfem_quad4_eval_bwd(dev_index(dev), ptr(Xd), ptr(Ud), ptr(conn32), ptr(xe), ptr(eid),
-                                             eid.shape[0], ptr(_f64(cu, "cu")), ptr(_f64(cd, "cd")), ptr(_f64(cg, "cg")),
+                                             eid.shape[0], ptr(cu), ptr(cd), ptr(cg),
                                              ptr(gX), ptr(gU), stream_ptr(dev)), "hfem_quad4_eval_bwd")
         return gX.to(ctx.dt), gU.to(ctx.dt), None, None, None
 

@@ -49,7 +49,9 @@ int hfem_device_count(void);
  * EnergyLoss2D.domain_energy + its autograd backward (src/loss.py:55-88,
  * src/models.py:316-357) on ASSEMBLED arrays X,U [Nn][2].
  * ACCUMULATES: loss_acc[0] += E_domain, gX += dE/dX, gU += dE/dU (caller zeroes).
- * gX/gU may be NULL (forward only).  Elements [e_begin, e_end).               */
+ * gX/gU may be NULL (forward only).  Elements [e_begin, e_end); an empty range
+ * (here, ned == 0 below, and for hfem_quad4_energy_atomic) returns 0 and reads
+ * no pointer.                                                                 */
 int hfem_tri3_energy_atomic(int device, const double *X, const double *U,
                             const int32_t *conn, int64_t e_begin, int64_t e_end, int64_t nn,
                             const double mat[4], double W, const double Bk[6],
