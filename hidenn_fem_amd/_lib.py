@@ -41,6 +41,9 @@ class AdamTensor(C.Structure):
                 ("beta2", _f64), ("eps", _f64), ("dtype", _i32), ("block_begin", _i32)]
 
 
+ADAM_TICKET_INTS = 1056     # HFEM_ADAM_TICKET_INTS (include/hidenn_fem.h): int32 of hfem_adam_multi_dev's ticket buffer
+
+
 # name -> (restype, argtypes); must list every symbol include/hidenn_fem.h declares
 PROTOTYPES = {
     "hfem_version": (C.c_int, []),

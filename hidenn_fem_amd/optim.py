@@ -2,8 +2,10 @@
 
 ``FusedAdam`` is a drop-in for ``torch.optim.Adam(params, lr=...)`` as the reference's examples use it
 (``/root/reference/examples/example1.py:31``, ``example2.py:37``, ``example3.py:89``: default betas and
-eps, no weight decay, no amsgrad): one HIP launch per parameter tensor instead of torch's chain of
-element-wise kernels, same arithmetic operation for operation.  ROCm tensors only (no CPU fallback).
+eps, no weight decay, no amsgrad): ONE HIP launch for all parameter tensors of a step (``hfem_adam_multi_dev``) when they
+sit on one device and share a step count -- always so with ``capturable=True`` -- and one launch per tensor otherwise (a
+single tensor, diverging host step counts, several devices), instead of torch's chain of element-wise kernels; same
+arithmetic operation for operation.  ROCm tensors only (no CPU fallback).
 """
 from __future__ import annotations
 
@@ -180,7 +182,7 @@ class FusedAdam(torch.optim.Optimizer):
         import ctypes as C
         nbytes = max(1, n_params) * C.sizeof(_lib.AdamTensor)
         self._tabs = dict(n=n_params, dev=dev, nbytes=nbytes, next=0, slots=[self._new_slot(dev, nbytes) for _ in range(self._TAB_SLOTS)])
-        self._ticket = torch.zeros(1056, dtype=torch.int32, device=dev)      # HFEM_ADAM_TICKET_INTS
+        self._ticket = torch.zeros(_lib.ADAM_TICKET_INTS, dtype=torch.int32, device=dev)
 
     def _table(self, todo):
         """Device table of this step's tensors.  A slot (pinned host buffer + device buffer) is reused only when nothing can
