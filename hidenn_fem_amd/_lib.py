@@ -191,6 +191,11 @@ PROTOTYPES = {
     "hfem_quad4_hyper_stress_recover": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_tri3_hyper_zz_error": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hfem_quad4_hyper_zz_error": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hfem_mass_apply": (C.c_int, [C.c_int, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _i32, _vp, _i32, _vp, _vp]),
+    "hfem_block_gram": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "hfem_block_combine": (C.c_int, [C.c_int, _vp, _i32, _vp, _i32, _i64, _vp, _vp]),
+    "hfem_block_residual": (C.c_int, [C.c_int, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "hfem_block_jacobi_apply": (C.c_int, [C.c_int, _vp, _vp, _i32, _i64, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

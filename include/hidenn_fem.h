@@ -968,6 +968,38 @@ int hfem_quad4_hyper_zz_error(int device, const double *X, const double *U, cons
                               const double *nodal_stress, const double lame[2], double *eta2, double *norm2, double *partials,
                               double *totals, void *stream);
 
+/* ------------------------------------------------------------------ free-vibration modes: mass operator and block-vector kernels
+ * (csrc/modal.hip; hidenn_fem_amd/modal.py).  K_ff phi = lambda M_ff phi by block LOBPCG; K_ff is what hfem_cg_apply
+ * applies.  fp64; a block vector is [m][n_u][2]: every vector contiguous in the storage order of u_free, so a slice is what
+ * hfem_cg_apply / hfem_amg_vcycle take.  `len` = 2 n_u doubles of one vector (even).  Every entry point is bitwise reproducible
+ * (fixed-order sums, no floating-point atomics), checks its arguments before it touches a device (negative codes, message through
+ * hfem_last_error) and only enqueues launches on `stream`.
+ *   mass_apply   MV[k] = M_ff V[k], k < m <= 8, matrix-free: one thread per free u row walks the row's node fan (adj_ptr / adj:
+ *                the node -> (element, corner) CSR of the stress recovery, entries e << 2 | c, ascending e) and forms each
+ *                element's mass row from X [nn][2] (coordinates by node id).  npe 3: rho |det J| / 24 (1 + delta_ab); npe 4:
+ *                rho sum_q N_a N_b |det J_q| over the 2x2 Gauss points; lumped != 0: the row sum on the diagonal.  M x I_2, unit
+ *                thickness, always |det J|.  row_node [n_u]: node id of every row; node_row [nn]: row of every node, -1 for a
+ *                Dirichlet node (contributes 0).  MV must not alias V.
+ *   block_gram   G [ma][mb] = A B^T, A [ma][len], B [mb][len], ma, mb <= 24; one pass with per-workgroup partials (at least
+ *                HFEM_BLOCK_GRAM_PARTIALS doubles) and a fixed-order finish into the device matrix G.
+ *   block_combine  Out[j] = sum_i C[i][j] S[i]: S [ms][len], C [ms][mo] row-major on the device, Out [mo][len], ms, mo <= 24;
+ *                Out must not overlap S.
+ *   block_residual  R[k] = KX[k] - lambda[k] MX[k], k < m <= 8 (lambda on the device); norms[2k] = |R_k|_2, norms[2k + 1] =
+ *                |MX_k|_2 on the device; partials: at least HFEM_BLOCK_RESIDUAL_PARTIALS doubles.
+ *   block_jacobi_apply  W[k] = D^-1 R[k], D the 2x2 blocks {K_xx, K_xy, K_yy} of hfem_cg_setup's diag_out [n_u][3]; W may be R.
+ */
+#define HFEM_BLOCK_GRAM_PARTIALS 73728
+#define HFEM_BLOCK_RESIDUAL_PARTIALS 16384
+int hfem_mass_apply(int device, int32_t npe, const double *X, const int32_t *conn, int64_t ne, int64_t nn, const int32_t *adj_ptr,
+                    const int32_t *adj, const int32_t *row_node, const int32_t *node_row, int64_t n_u, double rho, int32_t lumped,
+                    const double *V, int32_t m, double *MV, void *stream);
+int hfem_block_gram(int device, const double *A, int32_t ma, const double *B, int32_t mb, int64_t len, double *partials, double *G,
+                    void *stream);
+int hfem_block_combine(int device, const double *S, int32_t ms, const double *C, int32_t mo, int64_t len, double *Out, void *stream);
+int hfem_block_residual(int device, const double *KX, const double *MX, const double *lambda, int32_t m, int64_t len, double *R,
+                        double *partials, double *norms, void *stream);
+int hfem_block_jacobi_apply(int device, const double *diag, const double *R, int32_t m, int64_t len, double *W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
