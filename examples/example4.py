@@ -12,7 +12,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
-        r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0):
+        r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0, dynamics=0, dt=None):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -38,12 +38,19 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     ``modes=N`` (``--modes N``, N <= 8): after the mesh is built, prints the N lowest free-vibration frequencies of the plate
     (``hidenn_fem_amd.modal.vibration_modes``: block LOBPCG on ``K phi = lambda M phi`` with the consistent mass, unit density,
     preconditioner ``precond``) and returns ``(model, ModalInfo)``; nothing else runs.  The loss is built with
-    ``grad_convention="physical"``, where the frequencies are those of the elastic plate; ``quad=True`` gives the QUAD4 plate."""
+    ``grad_convention="physical"``, where the frequencies are those of the elastic plate; ``quad=True`` gives the QUAD4 plate.
+    ``dynamics=N`` (``--dynamics N``): a step load on the plate at rest -- the default traction switched on at t = 0 -- followed
+    for N Newmark steps (``hidenn_fem_amd.dynamics.NewmarkSolver``: average acceleration, consistent mass, unit density,
+    preconditioner ``precond``), printing t, the tip displacement, the CG iterations and the total energy of every step;
+    ``dt`` (``--dt``) defaults to 1/20 of the lowest mode's period (one ``vibration_modes`` solve).  Physical convention;
+    returns ``(model, [StepInfo])``; nothing else runs."""
     import os
     import torch.distributed as dist
     if modes and sharded:
         raise NotImplementedError("example 4: modes=N / --modes N runs on one GPU (the modal solver is not sharded); drop "
                                   "sharded=True / --sharded")
+    if dynamics and (sharded or modes):
+        raise NotImplementedError("example 4: dynamics=N / --dynamics N runs on one GPU and on its own; drop --sharded / --modes")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dev = torch.device("cuda", local % max(torch.cuda.device_count(), 1)) if sharded else torch.device("cuda")
     if sharded and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1 and not dist.is_initialized():
@@ -54,9 +61,9 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
     if quad:
-        if not r_adapt and not modes:
-            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve or the modes only (pass r_adapt=True / "
-                                      "--r-adapt, or modes=N / --modes N)")
+        if not r_adapt and not modes and not dynamics:
+            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes or the dynamics only (pass "
+                                      "r_adapt=True / --r-adapt, modes=N / --modes N or dynamics=N / --dynamics N)")
         from hidenn_fem_amd.mesh import structured_quad_mesh
         nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
     else:
@@ -69,9 +76,11 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype,
-                           grad_convention="physical" if (error_estimate or modes) else None)
+                           grad_convention="physical" if (error_estimate or modes or dynamics) else None)
     if modes:
         return _modes(model, loss_fn, modes, precond, rank0)
+    if dynamics:
+        return _dynamics(model, loss_fn, dynamics, dt, precond)
     if error_estimate and rank0:
         print('error estimate: the loss uses grad_convention="physical" (eta estimates the discretisation error only there)')
     if r_adapt:
@@ -318,6 +327,36 @@ def _modes(model, loss_fn, n_modes, precond, rank0=True):
     return model, info
 
 
+def _dynamics(model, loss_fn, n_steps, dt, precond):
+    import time
+    from hidenn_fem_amd.dynamics import NewmarkSolver
+    from hidenn_fem_amd.modal import vibration_modes
+    if dt is None:
+        lam = vibration_modes(model, loss_fn, n_modes=1, precond=precond, max_iter=200 if precond == "amg" else 5000).eigenvalues[0].item()
+        dt = 2.0 * 3.141592653589793 / lam ** 0.5 / 20.0
+        print(f"lowest mode: period {20.0 * dt:.6e}; dt = period / 20 = {dt:.6e}")
+    with torch.no_grad():
+        model.u_free.zero_()
+    solver = NewmarkSolver(model, loss_fn, dt, precond=precond)
+    solver.set_state()
+    x = model.coords.detach()[model._idx_ufree.to(model.coords.device)]                 # node of every free u row (storage order)
+    tip = int(torch.argmax(x[:, 0] - 1e-3 * (x[:, 1] - 0.5 * x[:, 1].max()).abs()))     # right edge, nearest mid-height
+    print(f"step load from rest (consistent mass, density 1, beta 1/4, gamma 1/2, {precond}); tip = free row {tip} at "
+          f"({x[tip, 0].item():.3f}, {x[tip, 1].item():.3f})")
+    infos = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n_steps):
+        info = solver.step(1)[0]
+        u = solver.u[tip]
+        print(f"t {info.t:.6e}: tip u ({u[0].item():+.6e}, {u[1].item():+.6e}) CG {info.iterations:4d} ({info.reason}) "
+              f"energy {solver.energy()['total']:+.9e}")
+        infos.append(info)
+    torch.cuda.synchronize()
+    print(f"{n_steps} steps, {sum(i.iterations for i in infos)} CG iterations, {time.perf_counter() - t0:.3f} s")
+    return model, infos
+
+
 def _print_error(model, loss_fn, when, recovery=None):
     """One line with the relative ZZ error estimate; returns the ``StressRecovery`` (reusable: the connectivity never changes)."""
     from hidenn_fem_amd.post import StressRecovery
@@ -380,6 +419,10 @@ if __name__ == "__main__":
     ap.add_argument("--modes", type=int, default=0, metavar="N",
                     help="print the N lowest free-vibration frequencies of the plate (block LOBPCG, N <= 8; with --quad and "
                          "--precond block_jacobi|amg) and stop")
+    ap.add_argument("--dynamics", type=int, default=0, metavar="N",
+                    help="a step load on the plate at rest, N Newmark steps (t, tip displacement, CG iterations and total "
+                         "energy per step; with --dt, --quad and --precond block_jacobi|amg) and stop")
+    ap.add_argument("--dt", type=float, default=None, help="time step of --dynamics (default: 1/20 of the lowest mode's period)")
     ap.add_argument("--newton", action="store_true",
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
@@ -392,4 +435,4 @@ if __name__ == "__main__":
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,
-        precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes)
+        precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes, dynamics=a.dynamics, dt=a.dt)

@@ -2,8 +2,9 @@
 // level -- the vector kernels, the status record, the halt logic and the hfem_cg_* entry points.  Nothing here knows the
 // element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
 // (the model's own QUAD4 plan), tri3_hyper_cg.hip or quad4_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point,
-// on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
-// cg_apply and cg_diag; the residual r = -dE/du comes from the graded energy kernel, called by the host once per solve.
+// on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py),
+// tri3_dyn_cg.hip or quad4_dyn_cg.hip (the shifted operator c_K K + c_M M of a Newmark step after hfem_cg_setup_shifted, on the
+// plans of the plain kernels: hidenn_fem_amd/dynamics.py), chosen in cg_apply and cg_diag; the residual r = -dE/du comes from the graded energy kernel, called by the host once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
 //                   order, forms beta, and applies the stopping test (START: r = -g0, z = D^-1 r, |f|).
 //   cg_rz_kernel    rho = r^T z in block order, then beta (precond = AMG only).
@@ -177,6 +178,9 @@ struct hfem_cg {
     // bound by hfem_cg_setup
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     hfem::Tri3Consts k{};
+    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; kernels of tri3_dyn_cg.hip / quad4_dyn_cg.hip)
+    bool shifted = false;
+    hfem::DynMass dm{};
     // bound by hfem_cg_setup_hyper
     const double2 *u_lin = nullptr, *u_fixed = nullptr;
     hfem::HyperConsts hk{};
@@ -188,7 +192,7 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     hfem::CgElemArgs A;
     A.plan = c->plan; A.n_tiles = c->n_tiles; A.block = c->block; A.phys = c->phys; A.x_free = c->x_free; A.x_fixed = c->x_fixed;
     A.k = c->k; A.lds = lds; A.s = s;
-    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq;
+    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq; A.dm = c->dm;
     return A;
 }
 
@@ -198,6 +202,8 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
     const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->shifted && c->quad) hfem::launch_quad4_dyn_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->shifted) hfem::launch_tri3_dyn_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
@@ -206,6 +212,8 @@ void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStrea
     const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    else if (c->shifted && c->quad) hfem::launch_quad4_dyn_cg_diag(A, diag, c->dinv, precond);
+    else if (c->shifted) hfem::launch_tri3_dyn_cg_diag(A, diag, c->dinv, precond);
     else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }
@@ -381,8 +389,32 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
     hipStream_t s = (hipStream_t)stream;
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);   // QUAD4: the 2x2 rule's weights are 1 (hfem_quad4_energy_plan_ex)
+    c->shifted = false; c->dm = hfem::DynMass{};
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup")) return rc;
+    c->ready = true;
+    return 0;
+}
+
+// hfem_cg_setup for A = c_K K + c_M M: the same bindings, the material constants scaled by c_K and the mass coefficients
+extern "C" int hfem_cg_setup_shifted(hfem_cg *c, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                     double c_k, double c_m, int32_t lumped, int32_t precond, double *diag_out, void *stream) {
+    HFEM_ARG_CHECK(std::isfinite(c_k) && std::isfinite(c_m) && c_k >= 0.0 && c_m >= 0.0 && (c_k > 0.0 || c_m > 0.0),
+                   "c_k and c_m must be finite, >= 0 and not both zero");
+    HFEM_ARG_CHECK(c && x_free && mat, "null pointer");
+    HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+    HFEM_ARG_CHECK(!c->hyper, "this solver was created by hfem_cg_create_hyper: the shifted operator exists for hfem_cg_create");
+    bool fixed_rows = false;
+    const hfem::HostPlan &h = c->plan->host;
+    for (size_t i = 0; i < h.node_src.size(); i += 2) fixed_rows = fixed_rows || h.node_src[i] < 0;
+    HFEM_ARG_CHECK(x_fixed || !fixed_rows, "the plan reads fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
+    c->k = hfem::scaled_consts(hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr), c_k);
+    c->shifted = true; c->dm = hfem::dyn_mass(c->quad, c_m, lumped != 0);
+    cg_diag(c, diag_out, precond, nullptr, s);
+    if (int rc = hfem::launch_status("hfem_cg_setup_shifted")) return rc;
     c->ready = true;
     return 0;
 }

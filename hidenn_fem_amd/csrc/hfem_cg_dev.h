@@ -3,7 +3,8 @@
 // For the element kernels (apply and block diagonal of tri3_cg.hip, quad4_cg.hip, tri3_hyper_cg.hip and quad4_hyper_cg.hip) the phases that do not depend on
 // the element: the iteration state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
 // block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
-// element, 3 or 4 corners, and the x row code.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
+// element, 3 or 4 corners, and the x row code.  For the shifted operator of implicit dynamics (tri3_dyn_cg.hip,
+// quad4_dyn_cg.hip, the shifted assembly of tri3_amg.hip): the mass coefficients and one element's mass row.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
 // calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the index loads, the
 // staging of coordinates and p, and the slot loop.
 #pragma once
@@ -180,6 +181,73 @@ __device__ __forceinline__ double2 x_row(const double2 *x_free, const double2 *x
     return code >= 0 ? x_free[code] : x_fixed[-1 - code];
 }
 
+// ---------------------------------------------------------------- the shifted operator A = c_K K + c_M M
+// The mass part of tri3_dyn_cg.hip, quad4_dyn_cg.hip and amg_assemble_shifted_kernel as two run-time coefficients (c_M includes
+// the density), so consistent and lumped mass are one instance.  K's part is scaled on the host: the material constants times c_K.
+//   TRI3   M_e[a][b] = |det J| (m_off + m_dd delta_ab):  consistent m_off = m_dd = c_M / 24;  lumped m_off = 0, m_dd = c_M / 6
+//   QUAD4  M_e[a][b] = sum_q |det J_q| N_a(q) (m_off N_b(q) + m_dd delta_ab):  consistent m_off = c_M, m_dd = 0;  lumped the reverse
+struct DynMass {
+    double m_off = 0.0, m_dd = 0.0;
+};
+inline DynMass dyn_mass(bool quad, double c_m, bool lumped) {
+    DynMass m;
+    if (quad) { m.m_off = lumped ? 0.0 : c_m; m.m_dd = lumped ? c_m : 0.0; }
+    else { m.m_off = lumped ? 0.0 : c_m / 24.0; m.m_dd = lumped ? c_m / 6.0 : c_m / 24.0; }
+    return m;
+}
+inline Tri3Consts scaled_consts(Tri3Consts k, double c_k) {
+    k.c11 *= c_k; k.c12 *= c_k; k.c22 *= c_k; k.c33 *= c_k;
+    return k;
+}
+
+// |det J_q| at the four 2x2 Gauss points, in quad4_element_u's order (-,-) (+,-) (-,+) (+,+) and from its bilinear
+// coefficients (the unscaled ones carry 16 |det|).
+__device__ __forceinline__ void quad4_abs_dets(const double2 (&Xn)[4], double (&ad)[4]) {
+    const double gp = 0.57735026918962576451;   // 1/sqrt(3)
+    double a1[2], a2[2], a3[2];
+    {
+        const double v[2][4] = {{Xn[0].x, Xn[1].x, Xn[2].x, Xn[3].x}, {Xn[0].y, Xn[1].y, Xn[2].y, Xn[3].y}};
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const double s = v[i][1] - v[i][0], t = v[i][2] - v[i][3];
+            a1[i] = s + t;
+            a3[i] = t - s;
+            a2[i] = (v[i][3] - v[i][0]) + (v[i][2] - v[i][1]);
+        }
+    }
+    const double am = a1[0] - gp * a3[0], ap = a1[0] + gp * a3[0], cm = a1[1] - gp * a3[1], cp = a1[1] + gp * a3[1];
+    const double bm = a2[0] - gp * a3[0], bp = a2[0] + gp * a3[0], dm = a2[1] - gp * a3[1], dp = a2[1] + gp * a3[1];
+    ad[0] = 0.0625 * fabs(am * dm - bm * cm); ad[1] = 0.0625 * fabs(am * dp - bp * cm);
+    ad[2] = 0.0625 * fabs(ap * dm - bm * cp); ad[3] = 0.0625 * fabs(ap * dp - bp * cp);
+}
+
+// N_a(q) of the 2x2 rule: one of three values by how many of the two reference coordinates of corner a and point q agree
+__device__ __forceinline__ constexpr double quad4_n(int a, int q) {
+    const double gp = 0.57735026918962576451;
+    const double xi = (q & 1) ? gp : -gp, eta = (q & 2) ? gp : -gp;
+    return 0.25 * (1.0 + corner_xi(a) * xi) * (1.0 + corner_eta(a) * eta);
+}
+
+// Row a of one element's mass in the two coefficients, a a run-time corner (selects and signs, never an index of a local
+// array): mrow[b] = M_e[a][b].  For the diag kernels' M_e[a][a] and the AMG fine level of A (tri3_amg.hip).
+__device__ __forceinline__ void dyn_mass_row(const double2 (&X)[3], int a, const DynMass &m, double (&mrow)[3]) {
+    const double A = fabs((X[0].x - X[2].x) * (X[1].y - X[2].y) - (X[1].x - X[2].x) * (X[0].y - X[2].y));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) mrow[b] = A * (m.m_off + (b == a ? m.m_dd : 0.0));
+}
+__device__ __forceinline__ void dyn_mass_row(const double2 (&X)[4], int a, const DynMass &m, double (&mrow)[4]) {
+    double ad[4];
+    quad4_abs_dets(X, ad);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) mrow[b] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const double wa = ad[q] * quad4_n(a, q);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) mrow[b] += wa * (m.m_off * quad4_n(b, q) + (b == a ? m.m_dd : 0.0));
+    }
+}
+
 // ---------------------------------------------------------------- element launchers (tri3_cg.hip, quad4_cg.hip)
 // What the driver binds of a solve, by value.  block: threads per tile of a paired TRI3 plan (QUAD4 tiles are 256).
 struct CgElemArgs {
@@ -196,6 +264,8 @@ struct CgElemArgs {
     // quad4_hyper_cg.hip: c = mu - lambda L per slot and Gauss point, [n_tiles][4][elem_stride]; the diag launch of a
     // linearisation writes it, its apply launches read it instead of calling log1p
     double *cq = nullptr;
+    // the shifted operator (tri3_dyn_cg.hip, quad4_dyn_cg.hip): k carries c_K, dm the mass coefficients
+    DynMass dm{};
 };
 // q = K p (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
@@ -218,5 +288,14 @@ constexpr int kQuad4HyperCgBlock = 256;
 void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
                                  double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
+
+// The shifted operator A = c_K K + c_M M (tri3_dyn_cg.hip on the paired TRI3 plan, quad4_dyn_cg.hip on the QUAD4 plan; A.k is
+// scaled by c_K, A.dm carries c_M): q = A p and the 2x2 diagonal blocks of A, the instance matrix of the plain launchers.
+void launch_tri3_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                              double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_quad4_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                               double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_tri3_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
+void launch_quad4_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 
 }  // namespace hfem

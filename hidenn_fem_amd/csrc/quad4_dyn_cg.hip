@@ -1,0 +1,224 @@
+// Implicit transient dynamics on QUAD4, gfx950 (MI355X): the element kernels of the shifted operator A = c_K K + c_M M of a
+// Newmark step (hidenn_fem_amd/dynamics.py) on the model's own QUAD4 tile plan.  The PCG driver (cg.hip) launches
+// them through launch_quad4_dyn_cg_apply / launch_quad4_dyn_cg_diag once hfem_cg_setup_shifted has bound the solver.
+//
+// They mirror quad4_cg_apply_kernel / quad4_cg_diag_kernel (quad4_cg.hip): the same clamped index loads, gather, ping-pong p,
+// slot loop, LDS accumulation, store_q_p and apply_finish (hfem_cg_dev.h).  The stiffness part is quad4_element_u on material
+// constants the host scaled by c_K; the mass part is formed in the slot loop from the corner rows the element already holds:
+//   (M_e p)_a = sum_q |det J_q| N_a(q) (m_off p_h(q) + m_dd p_a),  p_h(q) = sum_b N_b(q) p_b,  2x2 Gauss points
+// consistent: m_off = c_M, m_dd = 0; lumped (the row sum on the diagonal): m_off = 0, m_dd = c_M (DynMass, hfem_cg_dev.h; c_M
+// includes the density; run-time coefficients, not instances).  Always |det J_q|: no gradient convention enters the mass.
+// The tile energy is c_K e + 1/2 c_M p^T M_e p, so apply_finish's p^T q = 2 x sum stays right.
+#include <hip/hip_runtime.h>
+
+#include "hfem_cg_dev.h"
+
+namespace hfem {
+namespace {
+
+// One element's mass part: adds (M_e p)_a to the four rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double quad4_mass_rows(const double2 (&Xn)[4], const double2 (&Pn)[4], const DynMass &m,
+                                                  double2 (&gu)[4]) {
+    double ad[4];
+    quad4_abs_dets(Xn, ad);
+    double2 r[4];
+    double nl[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { r[a] = make_double2(0.0, 0.0); nl[a] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double hx = 0.0, hy = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { hx += quad4_n(b, q) * Pn[b].x; hy += quad4_n(b, q) * Pn[b].y; }
+        const double w = ad[q] * m.m_off;
+        hx *= w; hy *= w;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            r[a].x += quad4_n(a, q) * hx; r[a].y += quad4_n(a, q) * hy;
+            nl[a] += quad4_n(a, q) * ad[q];
+        }
+    }
+    double e = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double wl = nl[a] * m.m_dd;
+        r[a].x = __builtin_fma(wl, Pn[a].x, r[a].x); r[a].y = __builtin_fma(wl, Pn[a].y, r[a].y);
+        gu[a].x += r[a].x; gu[a].y += r[a].y;
+        e += Pn[a].x * r[a].x + Pn[a].y * r[a].y;
+    }
+    return 0.5 * e;
+}
+
+// ---------------------------------------------------------------- q = A p
+// st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
+// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  k: the material constants times c_K.
+// LDS: xy[cap_nodes] double2 | p[cap_nodes] double2 | acc[2][cap_owned] | red[BLOCK / 64 + 2]
+template <int BLOCK, int NPT, int EPT, bool PHYS>
+__global__ __launch_bounds__(BLOCK) void quad4_dyn_cg_apply_kernel(
+    PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
+    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k, DynMass dm,
+    double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out, int cap_nodes, int cap_owned) {
+    if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
+    extern __shared__ double2 lds[];
+    double2 *nd_xy = lds, *nd_p = lds + cap_nodes;
+    double *acc0 = reinterpret_cast<double *>(lds + 2 * cap_nodes), *acc1 = acc0 + cap_owned;
+    double *red = acc1 + cap_owned;                         // BLOCK / 64 doubles + one flag word
+    const int tid = threadIdx.x;
+    const CgIter it = cg_iter(st, pbuf0, pbuf1);
+    const int slot = xcd_tile((int)blockIdx.x, (int)gridDim.x);
+    mem_phase_begin();                                      // prologue at raised wave priority (hfem_plan_dev.h)
+    int2 s[NPT];
+    uint32_t pk[EPT], pk3[EPT];
+    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
+    const size_t rec0 = (size_t)slot * pd.elem_stride;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const size_t i = rec0 + min(tid + j * BLOCK, pd.elem_stride - 1);
+        pk[j] = pd.elem_pack[i];
+        pk3[j] = pd.elem_pack_hi[i];
+    }
+    const TileDesc d = pd.tiles[slot];
+    const int n_owned = d.n_owned;
+    // gather: coordinates through the x row map, p through the u row map (fixed u rows are 0)
+    double vxx[NPT], vxy[NPT], vpx[NPT], vpy[NPT];          // plain doubles (double2 arrays end up in scratch)
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const double2 tx = *(s[j].x >= 0 ? x_free + s[j].x : x_fixed + ~s[j].x);
+        vxx[j] = tx.x; vxy[j] = tx.y;
+        const double2 tp = gather_p(it, z, s[j].y);
+        vpx[j] = tp.x; vpy[j] = tp.y;
+    }
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (tid + j * BLOCK >= d.n_elem) { pk[j] = kSkipBit; pk3[j] = 0u; }
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < d.n_node) { nd_xy[l] = make_double2(vxx[j], vxy[j]); nd_p[l] = make_double2(vpx[j], vpy[j]); }
+        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; }
+    }
+    __syncthreads();
+    mem_phase_end();
+    double e_loc = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < EPT; ++jj) {
+        const uint32_t p = pk[jj];
+        if (!(p & kSkipBit)) {
+            const int l[4] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask),
+                              (int)((p >> (2 * kLocalBits)) & kLocalMask), (int)(pk3[jj] & kLocalMask)};
+            double2 Xn[4], Pn[4], gu[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                Xn[j] = nd_xy[l[j]];
+                Pn[j] = nd_p[l[j]];
+            }
+            double e = quad4_element_u<PHYS>(Xn, Pn, k, gu);
+            e += quad4_mass_rows(Xn, Pn, dm, gu);
+            if (p & kHomeBit) e_loc += e;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (l[j] < n_owned) {
+                    unsafeAtomicAdd(&acc0[l[j]], gu[j].x);
+                    unsafeAtomicAdd(&acc1[l[j]], gu[j].y);
+                }
+        }
+    }
+    wave_energy(e_loc, red);
+    __syncthreads();
+    store_q_p<BLOCK>(s, n_owned, acc0, acc1, nd_p, q, it.p_new);
+    apply_finish<BLOCK>(red, partials, slot, ticket, n_tiles, st, host, pq_out);
+}
+
+// ---------------------------------------------------------------- 2x2 diagonal blocks of A
+// quad4_cg_diag_kernel with the mass on xx and yy: M_e[a][a] = sum_q |det J_q| N_a(q) (m_off N_a(q) + m_dd).
+// LDS: xy[cap_nodes] double2 | acc[3][cap_owned]
+template <int BLOCK, int NPT, int EPT, bool PHYS>
+__global__ __launch_bounds__(BLOCK) void quad4_dyn_cg_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
+                                                                  const double2 *__restrict__ x_fixed, Tri3Consts k, DynMass dm,
+                                                                  double *__restrict__ diag, double *__restrict__ dinv,
+                                                                  int precond, int cap_nodes, int cap_owned) {
+    extern __shared__ double2 lds[];
+    double2 *nd_xy = lds;
+    double *acc0 = reinterpret_cast<double *>(lds + cap_nodes), *acc1 = acc0 + cap_owned, *acc2 = acc1 + cap_owned;
+    const int tid = threadIdx.x;
+    const int slot = (int)blockIdx.x;
+    int2 s[NPT];
+    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
+    const TileDesc d = pd.tiles[slot];
+    const int n_owned = d.n_owned;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < d.n_node) nd_xy[l] = *(s[j].x >= 0 ? x_free + s[j].x : x_fixed + ~s[j].x);
+        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; }
+    }
+    __syncthreads();
+    for (int j = 0; j < EPT; ++j) {
+        if (tid + j * BLOCK >= d.n_elem) continue;
+        const size_t i = (size_t)slot * pd.elem_stride + tid + j * BLOCK;
+        const uint32_t p = pd.elem_pack[i];
+        if (p & kSkipBit) continue;
+        const int l[4] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask),
+                          (int)((p >> (2 * kLocalBits)) & kLocalMask), (int)(pd.elem_pack_hi[i] & kLocalMask)};
+        const double2 Xn[4] = {nd_xy[l[0]], nd_xy[l[1]], nd_xy[l[2]], nd_xy[l[3]]};
+        double ad[4];
+        quad4_abs_dets(Xn, ad);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            if (l[a] >= n_owned) continue;
+            double mm = 0.0;                                   // M_e[a][a]
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mm += ad[q] * quad4_n(a, q) * (dm.m_off * quad4_n(a, q) + dm.m_dd);
+            double2 gu[4], hu[4];
+            unit_columns<PHYS>(Xn, a, k, gu, hu);
+            unsafeAtomicAdd(&acc0[l[a]], gu[a].x + mm);
+            unsafeAtomicAdd(&acc1[l[a]], 0.5 * (gu[a].y + hu[a].x));
+            unsafeAtomicAdd(&acc2[l[a]], hu[a].y + mm);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < n_owned && s[j].y >= 0) store_jacobi_block(diag, dinv, s[j].y, precond, acc0[l], acc1[l], acc2[l]);
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- launchers
+// The instance matrix and the dispatch of launch_quad4_cg_apply / launch_quad4_cg_diag.
+void launch_quad4_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                               double *partials, unsigned *ticket, double *st, double *host, double *pq_out) {
+    const HostPlan &h = A.plan->host;
+    const PlanDev pd = plan_dev(A.plan);
+#define HFEM_Q4DYN_APPLY(NPT, EPT, PH)                                                                                       \
+    hipLaunchKernelGGL((quad4_dyn_cg_apply_kernel<256, NPT, EPT, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.n_tiles, \
+                       A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, A.dm, partials, ticket, st, host, pq_out, h.max_nodes,  \
+                       h.max_owned)
+    if (h.max_nodes <= 3 * 256 && h.max_elems <= 3 * 256) {
+        if (A.phys) HFEM_Q4DYN_APPLY(3, 3, true);
+        else HFEM_Q4DYN_APPLY(3, 3, false);
+    } else {
+        if (A.phys) HFEM_Q4DYN_APPLY(4, 4, true);
+        else HFEM_Q4DYN_APPLY(4, 4, false);
+    }
+#undef HFEM_Q4DYN_APPLY
+}
+
+void launch_quad4_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
+    const HostPlan &h = A.plan->host;
+    const PlanDev pd = plan_dev(A.plan);
+#define HFEM_Q4DYN_DIAG(PH)                                                                                                  \
+    hipLaunchKernelGGL((quad4_dyn_cg_diag_kernel<256, 4, 4, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.x_free,      \
+                       A.x_fixed, A.k, A.dm, diag, dinv, precond, h.max_nodes, h.max_owned)
+    if (A.phys) HFEM_Q4DYN_DIAG(true);
+    else HFEM_Q4DYN_DIAG(false);
+#undef HFEM_Q4DYN_DIAG
+}
+
+}  // namespace hfem

@@ -93,6 +93,43 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
     }
 }
 
+// A_ff = c_K K_ff + c_M M_ff (implicit dynamics): amg_assemble_kernel's walk, k scaled by c_K on the host, plus the
+// corner's mass row (dyn_mass_row, hfem_cg_dev.h) on xx and yy of every block.  No atomics: bit-deterministic.
+template <int NPE, bool PHYS>
+__global__ __launch_bounds__(kBlock) void amg_assemble_shifted_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
+                                                                      const int32_t *__restrict__ fan_elem,
+                                                                      const int32_t *__restrict__ fan_corner,
+                                                                      const int32_t *__restrict__ fan_slot,
+                                                                      const int32_t *__restrict__ conn_x,
+                                                                      const double2 *__restrict__ x_free,
+                                                                      const double2 *__restrict__ x_fixed,
+                                                                      const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
+                                                                      Tri3Consts k, DynMass dm) {
+    const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (r >= n) return;
+    for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
+        *reinterpret_cast<double4 *>(a_val + 4 * (size_t)s) = make_double4(0.0, 0.0, 0.0, 0.0);
+    for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
+        const int32_t e = fan_elem[f], a = fan_corner[f];
+        const int32_t *cx = conn_x + NPE * (size_t)e;
+        double2 X[NPE], gu[NPE], hu[NPE];
+        double mrow[NPE];
+#pragma unroll
+        for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
+        unit_columns<PHYS>(X, a, k, gu, hu);
+        dyn_mass_row(X, a, dm, mrow);
+#pragma unroll
+        for (int b = 0; b < NPE; ++b) {
+            const int32_t s = fan_slot[NPE * (size_t)f + b];
+            if (s < 0) continue;
+            double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
+            double4 v = *p;
+            v.x += gu[b].x + mrow[b]; v.y += gu[b].y; v.z += hu[b].x; v.w += hu[b].y + mrow[b];
+            *p = v;
+        }
+    }
+}
+
 // K_T,ff of the Neo-Hookean energy at (x, u): one thread per free row runs amg_hyper_row (hfem_amg_hyper_dev.h)
 template <int NPE>
 __global__ __launch_bounds__(kBlock) void amg_assemble_hyper_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
@@ -709,6 +746,26 @@ void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const do
 #undef HFEM_AMG_ASM
 }
 
+void assemble_shifted(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, double c_k,
+                      double c_m, bool lumped, hipStream_t s) {
+    const DevLevel &L = a->lv[0];
+    const bool quad = a->npe == 4;
+    const hfem::Tri3Consts k = hfem::scaled_consts(consts(mat, quad ? 1.0 : W), c_k);
+    const hfem::DynMass dm = hfem::dyn_mass(quad, c_m, lumped);
+#define HFEM_AMG_ASM_SHIFTED(NPE, PH)                                                                                         \
+    hipLaunchKernelGGL((hfem::amg_assemble_shifted_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,       \
+                       a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed,  \
+                       L.a_ptr, L.a_val, k, dm)
+    if (quad) {
+        if (a->phys) HFEM_AMG_ASM_SHIFTED(4, true);
+        else HFEM_AMG_ASM_SHIFTED(4, false);
+    } else {
+        if (a->phys) HFEM_AMG_ASM_SHIFTED(3, true);
+        else HFEM_AMG_ASM_SHIFTED(3, false);
+    }
+#undef HFEM_AMG_ASM_SHIFTED
+}
+
 void assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
                     const double lame[2], double W, hipStream_t s) {
     const DevLevel &L = a->lv[0];
@@ -825,6 +882,37 @@ extern "C" int hfem_amg_setup(hfem_amg *a, const double *x_free, const double *x
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup");
+}
+
+static int check_shift(const char *who, double c_k, double c_m) {
+    if (!(std::isfinite(c_k) && std::isfinite(c_m) && c_k >= 0.0 && c_m >= 0.0 && (c_k > 0.0 || c_m > 0.0))) {
+        hfem::set_error(std::string(who) + ": c_k and c_m must be finite, >= 0 and not both zero");
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int hfem_amg_assemble_shifted(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                         double c_k, double c_m, int32_t lumped, void *stream) {
+    if (int rc = check_shift(__func__, c_k, c_m)) return rc;
+    HFEM_ARG_CHECK(a && x_free && mat, "null pointer");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    assemble_shifted(a, x_free, x_fixed, mat, W, c_k, c_m, lumped != 0, (hipStream_t)stream);
+    return hfem::launch_status("hfem_amg_assemble_shifted");
+}
+
+extern "C" int hfem_amg_setup_shifted(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                      double c_k, double c_m, int32_t lumped, double *coarse_out, void *stream) {
+    if (int rc = check_shift(__func__, c_k, c_m)) return rc;
+    HFEM_ARG_CHECK(a && x_free && mat && coarse_out, "null pointer");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    assemble_shifted(a, x_free, x_fixed, mat, W, c_k, c_m, lumped != 0, s);
+    hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
+                       (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
+    return setup_levels(a, coarse_out, s, "hfem_amg_setup_shifted");
 }
 
 extern "C" int hfem_amg_assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free,

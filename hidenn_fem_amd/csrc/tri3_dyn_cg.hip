@@ -1,0 +1,229 @@
+// Implicit transient dynamics on TRI3, gfx950 (MI355X): the element kernels of the shifted operator A = c_K K + c_M M of a
+// Newmark step (hidenn_fem_amd/dynamics.py) over the paired owner-computes tile plan.  The PCG driver (cg.hip)
+// launches them through launch_tri3_dyn_cg_apply / launch_tri3_dyn_cg_diag once hfem_cg_setup_shifted has bound the solver.
+//
+// They mirror tri3_cg_apply_kernel / tri3_cg_diag_kernel (tri3_cg.hip): the same gather, ping-pong p, LDS accumulation,
+// store_q_p and apply_finish (hfem_cg_dev.h).  The stiffness part is tri3_element on material constants the host scaled by c_K
+// (K is linear in them, so gu and e arrive scaled); the mass part is formed in the slot loop from what the element already
+// holds -- the corner coordinates and the corner values of p -- with no extra memory traffic:
+//   M_e[a][b] = |det J| (m_off + m_dd delta_ab),  consistent: m_off = m_dd = c_M / 24,  lumped: m_off = 0, m_dd = c_M / 6
+// (c_M includes the density; run-time coefficients, not instances).  Always |det J|: no gradient convention enters the mass.
+//   (M_e p)_a = |det J| (m_off (p_0 + p_1 + p_2) + m_dd p_a),   1/2 p^T M_e p = 1/2 |det J| (m_off |sum p|^2 + m_dd sum |p_a|^2)
+// The tile energy is c_K e + 1/2 c_M p^T M_e p, so apply_finish's p^T q = 2 x sum stays right.
+#include <hip/hip_runtime.h>
+
+#include "hfem_cg_dev.h"
+
+namespace hfem {
+namespace {
+
+// One element's mass part: adds (M_e p)_a to the three rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double tri3_mass_rows(const double2 X0, const double2 X1, const double2 X2, const double2 P0,
+                                                 const double2 P1, const double2 P2, const DynMass &m, double2 (&gu)[3]) {
+    const double det = (X0.x - X2.x) * (X1.y - X2.y) - (X1.x - X2.x) * (X0.y - X2.y);
+    const double A = fabs(det);
+    const double wo = A * m.m_off, wd = A * m.m_dd;
+    const double sx = wo * (P0.x + P1.x + P2.x), sy = wo * (P0.y + P1.y + P2.y);
+    const double2 r0 = make_double2(__builtin_fma(wd, P0.x, sx), __builtin_fma(wd, P0.y, sy));
+    const double2 r1 = make_double2(__builtin_fma(wd, P1.x, sx), __builtin_fma(wd, P1.y, sy));
+    const double2 r2 = make_double2(__builtin_fma(wd, P2.x, sx), __builtin_fma(wd, P2.y, sy));
+    gu[0].x += r0.x; gu[0].y += r0.y; gu[1].x += r1.x; gu[1].y += r1.y; gu[2].x += r2.x; gu[2].y += r2.y;
+    return 0.5 * (P0.x * r0.x + P0.y * r0.y + P1.x * r1.x + P1.y * r1.y + P2.x * r2.x + P2.y * r2.y);
+}
+
+// ---------------------------------------------------------------- q = A p
+// st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
+// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  k: the material constants times c_K.
+template <int BLOCK, int NPT, int EPT, bool PHYS>
+__global__ __launch_bounds__(BLOCK) void tri3_dyn_cg_apply_kernel(
+    PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
+    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k, DynMass dm,
+    double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out, int cap_nodes, int cap_owned,
+    int col_stride) {
+    if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
+    extern __shared__ double2 lds[];
+    double2 *nd_xy = lds, *nd_p = lds + cap_nodes;
+    double *acc0 = reinterpret_cast<double *>(lds + 2 * cap_nodes), *acc1 = acc0 + cap_owned;
+    double *red = acc1 + cap_owned;                         // BLOCK / 64 doubles + one flag word
+    const int tid = threadIdx.x;
+    const CgIter it = cg_iter(st, pbuf0, pbuf1);
+    const int slot = xcd_tile((int)blockIdx.x, (int)gridDim.x);
+    int2 s[NPT];
+    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
+    const TileDesc d = pd.tiles[slot];
+    uint32_t w0[EPT], w1[EPT];
+    const size_t rec0 = (size_t)slot * pd.elem_stride;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const size_t i = rec0 + min(tid + j * col_stride, pd.elem_stride - 1);
+        w0[j] = pd.elem_pack[i];
+        w1[j] = pd.elem_pack_hi[i];
+    }
+    // gather: coordinates through the x row map, p through the u row map (fixed u rows are 0)
+    double2 vx[NPT], vp[NPT];
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        vx[j] = s[j].x >= 0 ? x_free[s[j].x] : x_fixed[~s[j].x];
+        vp[j] = gather_p(it, z, s[j].y);
+    }
+    const int n_owned = d.n_owned;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (!(tid < col_stride && tid + j * col_stride < d.n_elem)) { w0[j] = kSkipBit; w1[j] = 0u; }
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < d.n_node) { nd_xy[l] = vx[j]; nd_p[l] = vp[j]; }
+        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; }
+    }
+    __syncthreads();
+    auto add_row = [&](int l, const double2 g) {
+        unsafeAtomicAdd(&acc0[l], g.x);
+        unsafeAtomicAdd(&acc1[l], g.y);
+    };
+    double e_loc = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const uint32_t a = w0[j], b = w1[j];
+        if (!(a & kSkipBit)) {
+            const int ln = (int)(a & kLocalMask), lb = (int)((a >> kLocalBits) & kLocalMask),
+                      lc = (int)((a >> (2 * kLocalBits)) & kLocalMask);
+            const double2 Xn = nd_xy[ln], Pn = nd_p[ln], Xc = nd_xy[lc], Pc = nd_p[lc];
+            double2 sn, sc;
+            {
+                const double2 Xb = nd_xy[lb], Pb = nd_p[lb];
+                double2 gx[3], gu[3];
+                double e = tri3_element<true, false, PHYS>(Xn, Xb, Xc, Pn, Pb, Pc, k, gx, gu);
+                e += tri3_mass_rows(Xn, Xb, Xc, Pn, Pb, Pc, dm, gu);
+                if (a & kHomeBit) e_loc += e;
+                if (lb < n_owned) add_row(lb, gu[1]);
+                sn = gu[0]; sc = gu[2];
+            }
+            if (b & kHasBBit) {                             // B = (n, c, d)
+                const int ld = (int)(b & kLocalMask);
+                const double2 Xd = nd_xy[ld], Pd = nd_p[ld];
+                double2 gx[3], gu[3];
+                double e = tri3_element<true, false, PHYS>(Xn, Xc, Xd, Pn, Pc, Pd, k, gx, gu);
+                e += tri3_mass_rows(Xn, Xc, Xd, Pn, Pc, Pd, dm, gu);
+                if (b & kHomeBBit) e_loc += e;
+                if (ld < n_owned) add_row(ld, gu[2]);
+                sn.x += gu[0].x; sn.y += gu[0].y; sc.x += gu[1].x; sc.y += gu[1].y;
+            }
+            if (ln < n_owned) add_row(ln, sn);
+            if (lc < n_owned) add_row(lc, sc);
+        }
+    }
+    wave_energy(e_loc, red);
+    __syncthreads();
+    store_q_p<BLOCK>(s, n_owned, acc0, acc1, nd_p, q, it.p_new);
+    apply_finish<BLOCK>(red, partials, slot, ticket, n_tiles, st, host, pq_out);
+}
+
+// ---------------------------------------------------------------- 2x2 diagonal blocks of A
+// tri3_cg_diag_kernel with the mass on xx and yy: M_e[a][a] = |det J| (m_off + m_dd).
+template <int BLOCK, int NPT, int EPT, bool PHYS>
+__global__ __launch_bounds__(BLOCK) void tri3_dyn_cg_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
+                                                                 const double2 *__restrict__ x_fixed, Tri3Consts k, DynMass dm,
+                                                                 double *__restrict__ diag, double *__restrict__ dinv,
+                                                                 int precond, int cap_nodes, int cap_owned, int col_stride) {
+    extern __shared__ double2 lds[];
+    double2 *nd_xy = lds;
+    double *acc0 = reinterpret_cast<double *>(lds + cap_nodes), *acc1 = acc0 + cap_owned, *acc2 = acc1 + cap_owned;
+    const int tid = threadIdx.x;
+    const int slot = (int)blockIdx.x;
+    int2 s[NPT];
+    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
+    const TileDesc d = pd.tiles[slot];
+    const int n_owned = d.n_owned;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < d.n_node) nd_xy[l] = s[j].x >= 0 ? x_free[s[j].x] : x_fixed[~s[j].x];
+        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; }
+    }
+    __syncthreads();
+    const double m_aa = dm.m_off + dm.m_dd;
+    auto element = [&](int l0, int l1, int l2) {
+        const int ls[3] = {l0, l1, l2};
+        const double2 X[3] = {nd_xy[l0], nd_xy[l1], nd_xy[l2]};
+        const double mm = fabs((X[0].x - X[2].x) * (X[1].y - X[2].y) - (X[1].x - X[2].x) * (X[0].y - X[2].y)) * m_aa;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (ls[a] >= n_owned) continue;
+            double2 gu[3], hu[3];
+            unit_columns<PHYS>(X, a, k, gu, hu);
+            unsafeAtomicAdd(&acc0[ls[a]], gu[a].x + mm);
+            unsafeAtomicAdd(&acc1[ls[a]], 0.5 * (gu[a].y + hu[a].x));
+            unsafeAtomicAdd(&acc2[ls[a]], hu[a].y + mm);
+        }
+    };
+    for (int j = 0; j < EPT; ++j) {
+        if (!(tid < col_stride && tid + j * col_stride < d.n_elem)) continue;
+        const size_t i = (size_t)slot * pd.elem_stride + tid + j * col_stride;
+        const uint32_t a = pd.elem_pack[i], b = pd.elem_pack_hi[i];
+        if (a & kSkipBit) continue;
+        const int ln = (int)(a & kLocalMask), lb = (int)((a >> kLocalBits) & kLocalMask),
+                  lc = (int)((a >> (2 * kLocalBits)) & kLocalMask);
+        element(ln, lb, lc);
+        if (b & kHasBBit) element(ln, lc, (int)(b & kLocalMask));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int l = tid + j * BLOCK;
+        if (l < n_owned && s[j].y >= 0) store_jacobi_block(diag, dinv, s[j].y, precond, acc0[l], acc1[l], acc2[l]);
+    }
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- launchers
+// The instance matrix and the dispatch of launch_tri3_cg_apply / launch_tri3_cg_diag.
+void launch_tri3_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
+                              double *partials, unsigned *ticket, double *st, double *host, double *pq_out) {
+    const HostPlan &h = A.plan->host;
+    const PlanDev pd = plan_dev(A.plan);
+#define HFEM_DYN_APPLY(BLOCK, NPT, EPT, PH)                                                                                   \
+    hipLaunchKernelGGL((tri3_dyn_cg_apply_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd,         \
+                       A.n_tiles, A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, A.dm, partials, ticket, st, host, pq_out,     \
+                       h.max_nodes, h.max_owned, h.col_stride)
+#define HFEM_DYN_A(BLOCK, NPT, EPT)                                                                                           \
+    do {                                                                                                                      \
+        if (A.phys) HFEM_DYN_APPLY(BLOCK, NPT, EPT, true);                                                                    \
+        else HFEM_DYN_APPLY(BLOCK, NPT, EPT, false);                                                                          \
+    } while (0)
+    if (A.block == 512) HFEM_DYN_A(512, 2, 2);
+    else if (h.max_nodes <= 3 * 256) {
+        if (h.max_rows <= 3) HFEM_DYN_A(256, 3, 3);
+        else if (h.max_rows == 4) HFEM_DYN_A(256, 3, 4);
+        else HFEM_DYN_A(256, 3, 6);
+    } else {
+        if (h.max_rows <= 3) HFEM_DYN_A(256, 4, 3);
+        else if (h.max_rows == 4) HFEM_DYN_A(256, 4, 4);
+        else HFEM_DYN_A(256, 4, 6);
+    }
+#undef HFEM_DYN_A
+#undef HFEM_DYN_APPLY
+}
+
+void launch_tri3_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
+    const HostPlan &h = A.plan->host;
+    const PlanDev pd = plan_dev(A.plan);
+#define HFEM_DYN_DIAG(BLOCK, NPT, EPT, PH)                                                                                    \
+    hipLaunchKernelGGL((tri3_dyn_cg_diag_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd, A.x_free, \
+                       A.x_fixed, A.k, A.dm, diag, dinv, precond, h.max_nodes, h.max_owned, h.col_stride)
+    if (A.block == 512) {
+        if (A.phys) HFEM_DYN_DIAG(512, 2, 2, true);
+        else HFEM_DYN_DIAG(512, 2, 2, false);
+    } else {
+        if (A.phys) HFEM_DYN_DIAG(256, 4, 6, true);
+        else HFEM_DYN_DIAG(256, 4, 6, false);
+    }
+#undef HFEM_DYN_DIAG
+}
+
+}  // namespace hfem

@@ -386,6 +386,27 @@ class _AmgDevice:
         self.seconds = time.perf_counter() - t0
         self.setups += 1
 
+    def assemble_shifted(self, xf, xfix, mat, W, c_k, c_m, lumped):
+        """Level-0 A values = c_k K_ff + c_m M_ff (implicit dynamics; ``c_m`` includes the density)."""
+        check(_lib.lib().hfem_amg_assemble_shifted(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W, float(c_k),
+                                                   float(c_m), 1 if lumped else 0, stream_ptr(self.device)),
+              "hfem_amg_assemble_shifted")
+
+    def setup_shifted(self, xf, xfix, mat, W, c_k, c_m, lumped):
+        """``setup`` on the assembled shifted operator ``c_k K_ff + c_m M_ff`` (SPD: the coarse inverse as in ``setup``)."""
+        import time
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        check(_lib.lib().hfem_amg_setup_shifted(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W, float(c_k),
+                                                float(c_m), 1 if lumped else 0, ptr(self.coarse), stream_ptr(self.device)),
+              "hfem_amg_setup_shifted")
+        inv = torch.linalg.inv(self.coarse)
+        self.coarse_inv.copy_(0.5 * (inv + inv.T))
+        check(_lib.lib().hfem_amg_set_coarse(self._h, ptr(self.coarse_inv)), "hfem_amg_set_coarse")
+        torch.cuda.synchronize(self.device)
+        self.seconds = time.perf_counter() - t0
+        self.setups += 1
+
     def assemble_hyper(self, xf, xfix, u, ufix, lame, W):
         """Level-0 A values = the Neo-Hookean tangent K_T,ff at the coordinates and the displacement rows."""
         check(_lib.lib().hfem_amg_assemble_hyper(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, ptr(u),

@@ -1000,6 +1000,38 @@ int hfem_block_residual(int device, const double *KX, const double *MX, const do
                         double *partials, double *norms, void *stream);
 int hfem_block_jacobi_apply(int device, const double *diag, const double *R, int32_t m, int64_t len, double *W, void *stream);
 
+/* ------------------------------------------------------------------ implicit transient dynamics: Newmark on A = c_M M + c_K K
+ * (csrc/tri3_dyn_cg.hip, csrc/quad4_dyn_cg.hip, csrc/dynamics.hip; hidenn_fem_amd/dynamics.py).  No reference
+ * counterpart.  M u'' + C u' + K u = load(t) b0 over the free u rows, C = alpha_R M + beta_R K, Newmark (beta, gamma) in the
+ * a-form: per step one solve A a+ = load b0 - K w - alpha_R M v~ with A = c_M M + c_K K, c_M = 1 + gamma dt alpha_R,
+ * c_K = beta dt^2 + gamma dt beta_R.  K is hfem_cg_apply's operator, M hfem_mass_apply's (always |det J|).
+ *   cg_setup_shifted   hfem_cg_setup for the shifted element kind of the PCG driver: binds the coordinate rows and the material
+ *                as hfem_cg_setup does, and c_k >= 0, c_m >= 0 (c_m INCLUDES the density; both finite, not both zero), lumped != 0:
+ *                the row-sum mass.  diag_out [n_u][3] (may be NULL): the 2x2 diagonal blocks of A (the mass on xx and yy).  After
+ *                it hfem_cg_start / iterate / status / apply / start_amg / iterate_amg work on A; a later hfem_cg_setup returns
+ *                the solver to plain K.  The mass term is formed in the slot loop of the apply from the corner rows the element
+ *                already holds.  A solver of hfem_cg_create_hyper is refused.
+ *   amg_assemble_shifted / amg_setup_shifted   hfem_amg_assemble / hfem_amg_setup with the fine level A_ff = c_k K_ff + c_m M_ff
+ *                (one thread per row, no atomics: bit-deterministic); near-null space and coarse inverse as hfem_amg_setup.
+ *   newmark_predict  u_pred = u + dt v + dt^2 (1/2 - beta) a, v_pred = v + dt (1 - gamma) a, w = u_pred + beta_r v_pred.
+ *   newmark_rhs      rhs = load b0 - kw - alpha_r mv (mv may be NULL: no such term); g_zero = rhs, g0 = aa - rhs with aa = A a of
+ *                the warm start a: the two vectors hfem_cg_start takes.
+ *   newmark_correct  u = u_pred + beta dt^2 a, v = v_pred + gamma dt a (u may be u_pred, v may be v_pred).
+ * The three vector entry points work on fp64 rows, len = 2 n_u doubles (even), are elementwise (one or two FMAs per entry:
+ * bitwise reproducible), launch-only (capturable) and check their arguments before they touch a device. */
+int hfem_cg_setup_shifted(hfem_cg *cg, const double *x_free, const double *x_fixed, const double mat[4], double W, double c_k,
+                          double c_m, int32_t lumped, int32_t precond, double *diag_out, void *stream);
+int hfem_amg_assemble_shifted(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                              double c_k, double c_m, int32_t lumped, void *stream);
+int hfem_amg_setup_shifted(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W, double c_k,
+                           double c_m, int32_t lumped, double *coarse_out, void *stream);
+int hfem_newmark_predict(int device, const double *u, const double *v, const double *a, int64_t len, double dt, double beta,
+                         double gamma, double beta_r, double *u_pred, double *v_pred, double *w, void *stream);
+int hfem_newmark_rhs(int device, const double *b0, const double *kw, const double *mv, const double *aa, int64_t len, double load,
+                     double alpha_r, double *g0, double *g_zero, void *stream);
+int hfem_newmark_correct(int device, const double *u_pred, const double *v_pred, const double *a, int64_t len, double dt,
+                         double beta, double gamma, double *u, double *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

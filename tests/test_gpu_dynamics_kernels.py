@@ -1,0 +1,325 @@
+"""The kernels of implicit dynamics one by one: the shifted apply and its p^T A p, the 2x2 diagonal blocks and the
+assembled A of ``c_K K + c_M M`` against the reference matrix -- K from ``assemble_stiffness``, M element by element from
+tests/modal_reference.py with rho = 2, as tests/test_gpu_modal.py::dense_pencil, both held SPARSE (scipy CSR, the same entries:
+the larger shapes have 10^4 dofs) -- on shapes that reach every instance of the plain launchers' dispatch (restated here and
+asserted: all seven TRI3 instances, both QUAD4 ones); the three vector kernels against their formulas in ``longdouble``; the
+V-cycle of the hierarchy built on A.
+
+Tolerances: apply, blocks and assembled A 1e-12 x max; ``p^T A p`` 1e-12 |p^T A p| (both as tests/test_gpu_solve.py holds the
+K apply and its ``p^T K p``); vector kernels 4 ulp of the largest term per entry (each output is one or two FMAs); V-cycle
+symmetric to 1e-10 |r| |V(s)| and positive."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import scipy.linalg
+import torch
+
+import modal_reference as MR
+
+pytestmark = pytest.mark.gpu
+F64 = torch.float64
+RHO = 2.0
+COEFFS = [(1.0, 0.0), (0.0, 1.0), (0.3, 1.7)]
+CONVS = ["reference", "physical"]
+# id -> (mesh: "s" structured split | "z" zigzag split (few fan-adjacent partners: many one-element slots, so many slot rows at
+# few local nodes), nx, ny, tile_elems, plan_pair_block, the tri3_cg_apply instance the dispatch must pick).  a, b, c, d: the
+# cases of tests/test_gpu_pair_ends.py; together the shapes reach all seven instances of the TRI3 dispatch.
+TRI3_SHAPES = {
+    "a": ("s", 6, 5, 0, None, "<256,3,3>"),            # one tile
+    "b": ("s", 41, 21, 48, None, "<256,3,3>"),         # tiles of < 64 owned nodes, halo rows, 34 tiles
+    "c": ("s", 101, 51, 0, None, "<256,3,3>"),         # the default policy
+    "d": ("s", 101, 51, 0, 512, "<512,2,2>"),          # the 512-thread pair block
+    "n4": ("s", 101, 51, 1400, None, "<256,4,4>"),     # more than 768 local nodes, four slot rows
+    "n43": ("s", 101, 51, 1200, None, "<256,4,3>"),    # more than 768 local nodes, three slot rows
+    "z34": ("z", 101, 51, 900, None, "<256,3,4>"),     # four slot rows at <= 768 local nodes
+    "z36": ("z", 101, 51, 1900, None, "<256,3,6>"),    # five slot rows at <= 768 local nodes
+    "z46": ("z", 101, 51, 1400, None, "<256,4,6>"),    # five slot rows at more than 768 local nodes
+}
+QUAD4_SHAPES = {"S600": ("S", 600, "<3,3>"), "S800": ("S", 800, "<4,4>"), "T0": ("T:mixed", 0, "<3,3>")}
+
+
+def _dev():
+    assert torch.cuda.is_available(), "gpu tests need a ROCm device"
+    return torch.device("cuda:0")
+
+
+def tri3_cg_apply_branch(stats):
+    """Which instance launch_tri3_cg_apply / launch_tri3_dyn_cg_apply pick."""
+    if stats["threads_per_tile"] == 512:
+        return "<512,2,2>"
+    npt = 3 if stats["max_tile_nodes"] <= 3 * 256 else 4
+    rows = stats["slot_rows"]
+    return f"<256,{npt},{3 if rows <= 3 else 4 if rows == 4 else 6}>"
+
+
+def _tri3_model(shape, conv):
+    from hidenn_fem_amd import _lib
+    from hidenn_fem_amd.loss import EnergyLoss2D
+    from hidenn_fem_amd.mesh import generate_mesh, structured_tri_mesh
+    from hidenn_fem_amd.models import PiecewiseLinearShapeNN2D
+    from hidenn_fem_amd.plan import model_plan
+    mesh, nx, ny, te, pair_block, want = TRI3_SHAPES[shape]
+    if mesh == "s":
+        coords, conn, geom, bc, _, edges = structured_tri_mesh(nx, ny, length=2.0, height=1.0, jitter=0.2, seed=0, dtype=F64)
+    else:
+        coords, conn, geom, bc, _, edges = generate_mesh(2.0, 1.0, [], {"up": 0, "down": 0, "right": 2, "left": 1}, nx, ny)
+        coords = coords.to(F64)
+    torch.manual_seed(0)
+    m = PiecewiseLinearShapeNN2D(coords, conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0, neumann_edges=edges).to(_dev())
+    lf = EnergyLoss2D(device=_dev(), dtype=F64, tile_elems=te, grad_convention=conv)
+    L = _lib.lib()
+    prev = L.hfem_get_option(b"plan_pair_block")
+    try:
+        if pair_block is not None:
+            _lib.check(L.hfem_set_option(b"plan_pair_block", pair_block))
+        plan = model_plan(m, te, paired=True)                # cached by the model: the solver reuses it
+    finally:
+        L.hfem_set_option(b"plan_pair_block", prev)
+    assert plan.stats["paired"] and tri3_cg_apply_branch(plan.stats) == want, plan.stats
+    if shape == "a":
+        assert plan.stats["n_tiles"] == 1
+    if shape == "b":
+        assert plan.stats["max_tile_owned"] < 64 and plan.stats["n_tiles"] == 34
+    if shape == "n4":
+        assert plan.stats["max_tile_nodes"] > 768
+    return m, lf, plan
+
+
+def _quad4_model(shape, conv):
+    import test_gpu_quad4_shapes as QS
+    name, te, want = QUAD4_SHAPES[shape]
+    m = QS._new_model(name, _dev(), conv=conv)
+    lf = QS._lf(tile_elems=te)
+    plan = m.tile_plan(te)
+    assert QS.quad4_cg_apply_branch(plan.stats) == want, plan.stats
+    return m, lf, plan
+
+
+def _scipy(bsr):
+    """A torch BSR tensor as a scipy CSR matrix (the same entries: nothing is summed or dropped)."""
+    import scipy.sparse as sp
+    a = sp.bsr_matrix((bsr.values().cpu().numpy(), bsr.col_indices().cpu().numpy(), bsr.crow_indices().cpu().numpy()),
+                      shape=tuple(bsr.shape))
+    return a.tocsr()
+
+
+def _mass(m, lumped):
+    """tests/modal_reference.py's mass over the free u rows (M x I_2, rows interleaved), element by element as MR.mass and
+    MR.free_rows build it, held sparse: the larger shapes here have 10^4 dofs."""
+    import scipy.sparse as sp
+    X, conn = m.coords.detach().double().cpu().numpy(), m.connectivity.cpu().numpy().astype(np.int64)
+    row_node = m._idx_ufree.cpu().numpy().astype(np.int64)
+    nn, npe = X.shape[0], conn.shape[1]
+    elem = MR.tri3_element if npe == 3 else MR.quad4_element
+    me = np.stack([elem(X[nd], RHO) for nd in conn])
+    i, j = np.repeat(conn, npe, axis=1).reshape(-1), np.tile(conn, (1, npe)).reshape(-1)
+    Mn = sp.coo_matrix((me.reshape(-1), (i, j)), shape=(nn, nn)).tocsr()
+    if lumped:
+        Mn = sp.diags(np.asarray(Mn.sum(axis=1)).reshape(-1)).tocsr()
+    return sp.kron(Mn[row_node][:, row_node], sp.identity(2)).tocsr()
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, shape, conv):
+    """(model, loss, the solver's plan, K, {lumped: M}) of one shape and convention, K and M as scipy CSR over the free u rows
+    in storage order: built once, never modified."""
+    from hidenn_fem_amd.solve import assemble_stiffness
+    m, lf, plan = _tri3_model(shape, conv) if kind == "tri3" else _quad4_model(shape, conv)
+    K = _scipy(assemble_stiffness(m, lf))
+    return m, lf, plan, (0.5 * (K + K.T)).tocsr(), {lumped: _mass(m, lumped) for lumped in (False, True)}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_cases():
+    """The cached models own library handles: let them go with the module, not at interpreter shutdown."""
+    yield
+    _case.cache_clear()
+
+
+def _solver(m, lf, mass, **kw):
+    from hidenn_fem_amd.dynamics import NewmarkSolver
+    kw.setdefault("precond", "block_jacobi")
+    return NewmarkSolver(m, lf, kw.pop("dt", 1e-3), density=RHO, mass=mass, **kw)
+
+
+ALL_SHAPES = [("tri3", s) for s in TRI3_SHAPES] + [("quad4", s) for s in QUAD4_SHAPES]
+
+
+@pytest.mark.parametrize("conv", CONVS)
+@pytest.mark.parametrize("mass", ["consistent", "lumped"])
+@pytest.mark.parametrize("kind,shape", ALL_SHAPES, ids=[f"{k}-{s}" for k, s in ALL_SHAPES])
+def test_shifted_apply_blocks_and_assembly_against_the_dense_operator(kind, shape, mass, conv):
+    m, lf, plan, K, Ms = _case(kind, shape, conv)
+    M = Ms[mass == "lumped"]
+    s = _solver(m, lf, mass)
+    assert s.solver.plan is plan                             # the branch asserted on `plan` is the one that runs
+    n = s.n_u
+    p = torch.randn(n, 2, dtype=F64, generator=torch.Generator().manual_seed(5)).to(_dev())
+    pn = p.cpu().numpy().reshape(-1)
+    for c_k, c_m in COEFFS:
+        A = (c_k * K + c_m * M).tocsr()
+        want = A @ pn
+        q, pq = s.operator_apply(p, coefficients=(c_k, c_m))
+        scale = np.abs(want).max()
+        err = np.abs(q.cpu().numpy().reshape(-1) - want).max() / scale
+        err_pq = abs(pq.item() - pn @ want) / abs(pn @ want)  # tests/test_gpu_solve.py holds p^T K p to 1e-12 |p^T K p|
+        blocks = s.operator_blocks(coefficients=(c_k, c_m)).cpu().numpy()
+        d0, up, lo = A.diagonal(0), A.diagonal(1), A.diagonal(-1)
+        wb = np.stack([d0[0::2], 0.5 * (up[0::2] + lo[0::2]), d0[1::2]], axis=1)
+        err_b = np.abs(blocks - wb).max() / np.abs(wb).max()
+        Ad = s.assemble_operator(coefficients=(c_k, c_m))
+        Ad2 = s.assemble_operator(coefficients=(c_k, c_m))
+        err_a = abs(_scipy(Ad) - A).max() / abs(A).max()
+        print(f"{kind} {shape} {mass} {conv} ({c_k}, {c_m}): apply {err:.2e} p^T A p {err_pq:.2e} blocks {err_b:.2e} "
+              f"assembled {err_a:.2e}")
+        assert err <= 1e-12
+        assert err_pq <= 1e-12
+        assert err_b <= 1e-12
+        assert err_a <= 1e-12
+        assert torch.equal(Ad.values(), Ad2.values())        # one thread per row, no atomics: bit-identical
+        if (c_k, c_m) == (1.0, 0.0):                         # plain K: the frozen-mesh solver's own apply
+            qk, pqk = s.solver.apply(p)
+            assert (q - qk).abs().max().item() <= 1e-12 * qk.abs().max().item()
+            assert abs(pq.item() - pqk.item()) <= 1e-12 * abs(pqk.item())
+    # the step's own coefficients are bound again
+    q, _ = s.operator_apply(p)
+    want = (s.c_k * K + s.c_m * M) @ pn
+    assert np.abs(q.cpu().numpy().reshape(-1) - want).max() <= 1e-12 * np.abs(want).max()
+
+
+@pytest.mark.parametrize("kind,shape", [("tri3", "b"), ("quad4", "S600")])
+def test_a_later_plain_setup_returns_the_solver_to_k_and_a_hyper_solver_is_refused(kind, shape):
+    from hidenn_fem_amd import _lib
+    from hidenn_fem_amd.plan import model_plan
+    m, lf, plan, K, Ms = _case(kind, shape, "physical")
+    s = _solver(m, lf, "consistent")
+    p = torch.randn(s.n_u, 2, dtype=F64, generator=torch.Generator().manual_seed(9)).to(_dev())
+    pn = p.cpu().numpy().reshape(-1)
+    q, _ = s.operator_apply(p)                                # binds by the state key, then applies A
+    A = s.c_k * K + s.c_m * Ms[False]
+    assert np.abs(q.cpu().numpy().reshape(-1) - A @ pn).max() <= 1e-12 * np.abs(A @ pn).max()
+    lib, st = _lib.lib(), _lib.stream_ptr(_dev())
+    mat, W = s._mat()
+    xf, xfix = s.solver._xf, s.solver._xfix
+    xfix_p = xfix.data_ptr() if xfix.numel() else None
+    _lib.check(lib.hfem_cg_setup(s._h, xf.data_ptr(), xfix_p, mat, W, 1, s.diag.data_ptr(), st), "hfem_cg_setup")
+    q = torch.empty_like(p)
+    pq = torch.empty((), dtype=F64, device=_dev())
+    _lib.check(lib.hfem_cg_apply(s._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), st), "hfem_cg_apply")
+    want = K @ pn
+    assert np.abs(q.cpu().numpy().reshape(-1) - want).max() <= 1e-12 * np.abs(want).max()
+    d0 = K.diagonal(0)
+    assert np.abs(s.diag.cpu().numpy()[:, 0] - d0[0::2]).max() <= 1e-12 * np.abs(d0).max()
+    # a solver of hfem_cg_create_hyper is refused, with a message, and stays what it was
+    hp = model_plan(m, lf.tile_elems, paired=False) if kind == "tri3" else plan
+    h = C.c_void_p()
+    _lib.check(lib.hfem_cg_create_hyper(hp.handle, s.n_u, C.byref(h)), "hfem_cg_create_hyper")
+    try:
+        rc = lib.hfem_cg_setup_shifted(h, xf.data_ptr(), xfix_p, mat, W, 1.0, 1.0, 0, 1, None, st)
+        assert rc < 0 and b"hfem_cg_create_hyper" in lib.hfem_last_error()
+    finally:
+        lib.hfem_cg_destroy(h)
+
+
+# ---------------------------------------------------------------- vector kernels
+LENGTHS = [1, 63, 64, 65, 256 * 1024 + 1]                    # one row; wave edges; past the grid cap
+
+
+def _ulp_tol(*terms):
+    return 4.0 * np.spacing(np.max(np.abs(np.stack([np.asarray(t, dtype=np.float64) for t in terms])), axis=0))
+
+
+@pytest.mark.parametrize("n", LENGTHS)
+def test_vector_kernels_against_the_formulas(n):
+    from hidenn_fem_amd import _lib
+    lib, dev = _lib.lib(), _dev()
+    rng = np.random.default_rng(n)
+    dt, beta, gamma, beta_r, alpha_r, load = 0.37, 0.3, 0.6, 0.013, 0.21, -1.7
+    host = {k: rng.standard_normal((n, 2)) * 10.0 ** rng.integers(-3, 4) for k in ("u", "v", "a", "b0", "kw", "mv", "aa", "a1")}
+    d = {k: torch.from_numpy(x).to(dev) for k, x in host.items()}
+    ld = {k: x.astype(np.longdouble) for k, x in host.items()}
+    L = np.longdouble
+    ptr = lambda t: None if t is None else t.data_ptr()
+    new = lambda: torch.full((n, 2), float("nan"), dtype=F64, device=dev)
+
+    def predict():
+        ut, vt, w = new(), new(), new()
+        _lib.check(lib.hfem_newmark_predict(0, ptr(d["u"]), ptr(d["v"]), ptr(d["a"]), 2 * n, dt, beta, gamma, beta_r, ptr(ut),
+                                            ptr(vt), ptr(w), None), "predict")
+        return ut, vt, w
+
+    ut, vt, w = predict()
+    c_ua, c_va = L(dt) * L(dt) * (L(0.5) - L(beta)), L(dt) * (L(1.0) - L(gamma))
+    ut_ref = ld["u"] + L(dt) * ld["v"] + c_ua * ld["a"]
+    vt_ref = ld["v"] + c_va * ld["a"]
+    w_ref = ut_ref + L(beta_r) * vt_ref
+    t_u = (host["u"], dt * host["v"], float(c_ua) * host["a"])
+    t_v = (host["v"], float(c_va) * host["a"])
+    for got, ref, terms, what in ((ut, ut_ref, t_u, "u~"), (vt, vt_ref, t_v, "v~"),
+                                  (w, w_ref, t_u + tuple(beta_r * t for t in t_v), "w")):
+        err = np.abs(got.cpu().numpy() - ref.astype(np.float64))
+        assert (err <= _ulp_tol(*terms)).all(), (what, n, err.max())
+    again = predict()
+    assert all(torch.equal(x, y) for x, y in zip((ut, vt, w), again))
+
+    def rhs(mv, alpha):
+        g0, gz = new(), new()
+        _lib.check(lib.hfem_newmark_rhs(0, ptr(d["b0"]), ptr(d["kw"]), ptr(mv), ptr(d["aa"]), 2 * n, load, alpha, ptr(g0),
+                                        ptr(gz), None), "rhs")
+        return g0, gz
+
+    g0, gz = rhs(d["mv"], alpha_r)
+    r_ref = L(load) * ld["b0"] - ld["kw"] - L(alpha_r) * ld["mv"]
+    t_r = (load * host["b0"], host["kw"], alpha_r * host["mv"])
+    assert (np.abs(gz.cpu().numpy() - r_ref.astype(np.float64)) <= _ulp_tol(*t_r)).all()
+    assert (np.abs(g0.cpu().numpy() - (ld["aa"] - r_ref).astype(np.float64)) <= _ulp_tol(host["aa"], *t_r)).all()
+    assert all(torch.equal(x, y) for x, y in zip((g0, gz), rhs(d["mv"], alpha_r)))
+    a0, b0 = rhs(None, alpha_r)                               # M v~ = NULL is alpha_R = 0
+    a1, b1 = rhs(d["mv"], 0.0)
+    assert torch.equal(a0, a1) and torch.equal(b0, b1)
+    r0 = L(load) * ld["b0"] - ld["kw"]
+    assert (np.abs(b0.cpu().numpy() - r0.astype(np.float64)) <= _ulp_tol(*t_r[:2])).all()
+
+    def correct(in_place):
+        uo, vo = (ut.clone(), vt.clone()) if in_place else (new(), new())
+        src = (uo, vo) if in_place else (ut, vt)
+        _lib.check(lib.hfem_newmark_correct(0, ptr(src[0]), ptr(src[1]), ptr(d["a1"]), 2 * n, dt, beta, gamma, ptr(uo), ptr(vo),
+                                            None), "correct")
+        return uo, vo
+
+    u1, v1 = correct(False)
+    utl, vtl = ut.cpu().numpy().astype(np.longdouble), vt.cpu().numpy().astype(np.longdouble)
+    c_u, c_v = L(beta) * L(dt) * L(dt), L(gamma) * L(dt)
+    assert (np.abs(u1.cpu().numpy() - (utl + c_u * ld["a1"]).astype(np.float64))
+            <= _ulp_tol(ut.cpu().numpy(), float(c_u) * host["a1"])).all()
+    assert (np.abs(v1.cpu().numpy() - (vtl + c_v * ld["a1"]).astype(np.float64))
+            <= _ulp_tol(vt.cpu().numpy(), float(c_v) * host["a1"])).all()
+    u2, v2 = correct(True)
+    assert torch.equal(u1, u2) and torch.equal(v1, v2)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- the V-cycle of the hierarchy on A
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_shifted_vcycle_is_symmetric_and_positive(kind):
+    import test_gpu_modal as TM
+    m, lf = TM.make_model(kind), TM.make_loss("physical")
+    K, M = TM.dense_pencil(m, lf)
+    w = scipy.linalg.eigh(K, M, eigvals_only=True, subset_by_index=[0, 0])
+    dt = 2.0 * np.pi / np.sqrt(w[0]) / 20.0
+    s = _solver(m, lf, "consistent", dt=dt, precond="amg")
+    g = torch.Generator().manual_seed(7)
+    R = [torch.randn(s.n_u, 2, dtype=F64, generator=g).to(_dev()) for _ in range(8)]
+    Z = [s.precondition(r) for r in R]
+    for k, (r, z) in enumerate(zip(R, Z)):
+        assert (r * z).sum().item() > 0.0, k
+    worst = 0.0
+    for k in range(0, 8, 2):
+        r, t, zr, zt = R[k], R[k + 1], Z[k], Z[k + 1]
+        asym = abs((r * zt).sum().item() - (t * zr).sum().item())
+        bound = 1e-10 * r.norm().item() * zt.norm().item()
+        worst = max(worst, asym / bound)
+        assert asym <= bound, (k, asym, bound)
+    print(f"{kind}: V-cycle on A at dt = T1/20, worst asymmetry / bound {worst:.2e}")
