@@ -199,16 +199,21 @@ def apply_update_exact(x, d, t):
     return type(x)(v) if isinstance(x, np.floating) else v
 
 
-# ---------------------------------------------------------------- the test problem of tests/test_gpu_lbfgs_lengths.py
+# ---------------------------------------------------------------- the test problems of tests/test_gpu_lbfgs_lengths.py / _histories.py
 class ChainProblem:
     """f(x) = 1/2 sum a_i x_i^2 + 1/2 c sum (x_{i+1} - x_i)^2 - b.x with a ~ U(0.5, 2.5), c = 0.5, b ~ N(0, 1), x0 ~ N(0, 1):
     convex, every L-BFGS pair is accepted, |g0|_1 >> 1 so the first step takes the 1 / |g|_1 branch.  Loss and gradient in
-    float64 on the host, then cast to the vectors' type."""
+    float64 on the host, then cast to the vectors' type.
 
-    def __init__(self, n, seed=20240611):
+    ``stiff=True``: the same chain with a ~ 10 ** U(0, 5) (the same draws of the generator: b and x0 do not change).  The
+    default converges before 20 pairs are kept (the g.d stop fires at iteration 17 of a free run); with a condition number of
+    1e5 L-BFGS keeps accepting pairs for hundreds of iterations, so a history of 257 fills and the ring turns
+    (tests/test_lbfgs_reference_host.py asserts that for every case of ``HISTORY_UNSHARDED`` / ``HISTORY_SHARDED``)."""
+
+    def __init__(self, n, seed=20240611, stiff=False):
         rng = np.random.default_rng(seed)
         self.n, self.c = int(n), 0.5
-        self.a = rng.uniform(0.5, 2.5, n)
+        self.a = 10.0 ** rng.uniform(0.0, 5.0, n) if stiff else rng.uniform(0.5, 2.5, n)
         self.b = rng.standard_normal(n)
         self.x0 = rng.standard_normal(n)
 
@@ -221,3 +226,49 @@ class ChainProblem:
         g[1:] += self.c * dx
         loss = 0.5 * _dot(self.a * x64, x64) + 0.5 * self.c * _dot(dx, dx) - _dot(self.b, x64)
         return float(x.dtype.type(loss)), g.astype(x.dtype)
+
+
+# ---------------------------------------------------------------- the cases of tests/test_gpu_lbfgs_histories.py
+STIFF_SEED = 1
+_TWO_TURNS = (65, 100, 129)          # 2 (history + 1) + 3 iterations: head passes through every slot with a full ring
+
+
+def stiff_chain(n):
+    return ChainProblem(n, seed=STIFF_SEED, stiff=True)
+
+
+# (n, T, history, applied iterations)
+HISTORY_UNSHARDED = [(1031, T, h, 2 * (h + 1) + 3 if h in _TWO_TURNS else h + 3)
+                     for h in (64, 65, 100, 128, 129, 256, 257) for T in (np.float64, np.float32)]
+# (local lengths, T, history, iterations): world 1, and two handles in one process
+HISTORY_SHARDED = ([((1030,), T, h, h + 3) for h in (100, 257) for T in (np.float64, np.float32)]
+                   + [((686, 344), T, 129, 132) for T in (np.float64, np.float32)])
+# FusedLBFGS through its Python driver: one step of max_iter iterations, two parameter tensors
+HISTORY_FUSED = dict(n=1031, first_segment=37, history=100, max_iter=106)
+
+
+# ---------------------------------------------------------------- the recursion in coefficient space
+def coefficient_direction(S, Y, g):
+    """The direction from inner products alone, in float64 -- the FORM csrc/lbfgs.hip evaluates, restated from its header
+    comment (not from its kernels): with B = [S | Y | g] and the Gram matrix G = B^T B,
+      al_i = ro_i (-s_i.g - sum_{j newer} al_j s_i.y_j),                       newest to oldest
+      be_i = ro_i (H (-y_i.g - sum_j al_j y_i.y_j) + sum_{j older} c_j s_j.y_i),  c_i = al_i - be_i,  oldest to newest
+      d = B r with r = (c, -H al, -H),  g.d = r . (B^T g),  ro_i = 1 / s_i.y_i,  H = s_m.y_m / y_m.y_m of the newest pair.
+    S, Y: the kept pairs, oldest first.  Returns (d in float64, g.d, H)."""
+    m = len(S)
+    g64 = g.astype(np.float64)
+    if m == 0:
+        return -g64, -float(g64 @ g64), 1.0
+    B = np.stack([np.asarray(v, dtype=np.float64) for v in list(S) + list(Y)] + [g64])
+    G = B @ B.T
+    SY, YY, Sg, Yg = G[:m, m:2 * m], G[m:2 * m, m:2 * m], G[:m, 2 * m], G[m:2 * m, 2 * m]
+    ro = 1.0 / np.diag(SY)
+    H = SY[m - 1, m - 1] / YY[m - 1, m - 1]
+    al, c = np.zeros(m), np.zeros(m)
+    for i in range(m - 1, -1, -1):
+        al[i] = ro[i] * (-Sg[i] - al[i + 1:] @ SY[i, i + 1:])
+    for i in range(m):
+        be = ro[i] * (H * (-Yg[i] - al @ YY[i]) + c[:i] @ SY[:i, i])
+        c[i] = al[i] - be
+    r = np.concatenate([c, -H * al, [-H]])
+    return r @ B, float(r @ G[:, 2 * m]), float(H)

@@ -47,9 +47,11 @@ def _run(opt_cls, params, f, n_steps, **kw):
 @pytest.mark.gpu
 @pytest.mark.parametrize("history", [100, 5, 64, 65, 128, 129, 300])
 def test_fused_lbfgs_matches_torch_on_a_quadratic(history):
-    """history 5 makes the ring wrap many times; two parameter tensors exercise the segment offsets.  The other sizes sit on the
-    recursion kernels' boundaries (csrc/lbfgs.hip): 64 / 65 = one / two rows per lane of the one-wavefront form, 128 = its
-    largest history (129 KB of LDS for S^T Y), 129 = the 256-thread form, 300 = the reduction form."""
+    """history 5 makes the ring wrap many times; two parameter tensors exercise the segment offsets.  The other sizes SELECT each
+    recursion kernel (csrc/lbfgs.hip): 64 / 65 = one / two rows per lane of the one-wavefront form, 128 = its largest history
+    (129 KB of LDS for S^T Y), 129 = the 256-thread form, 300 = the reduction form -- but this n = 87 quadratic converges at
+    n_iter 29 with 27 live pairs, so every one of them runs far below the range in which it differs from its neighbour.  The
+    kernels with their history full: tests/test_gpu_lbfgs_histories.py."""
     from hidenn_fem_amd.optim import FusedLBFGS
     d = torch.device("cuda:0")
     params, f = _quadratic(d, F64)

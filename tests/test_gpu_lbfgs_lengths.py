@@ -267,14 +267,11 @@ def _assert_applied(where, x_old, d, t, x_new):
 
 
 # ---------------------------------------------------------------------------------------------------------------- unsharded
-@pytest.mark.gpu
-@pytest.mark.parametrize("case", LENGTHS, ids=_id)
-def test_lbfgs_iterations_at_a_length(case):
-    n, T, history, forms = case
-    _assert_forms(n, T, forms)
+def _unsharded_run(name, n, T, history, prob, iters):
+    """The schedule of the module docstring with ``iters`` applied iterations on ``prob`` (tests/test_gpu_lbfgs_histories.py
+    runs it too, on a problem that fills large histories)."""
     R.assert_longdouble_is_wider()
-    w = _Worst(_id(case), T)
-    prob = R.ChainProblem(n)
+    w = _Worst(name, T)
     r64, rld = R.LbfgsReference(history, np.float64), R.LbfgsReference(history, np.longdouble)
     H = _Handle(n, history, T)
     try:
@@ -286,7 +283,6 @@ def test_lbfgs_iterations_at_a_length(case):
             return np.concatenate([p.cpu().numpy() for p in params])
 
         d_prev = t_prev = x_old = gtd_scale = None
-        iters = history + 3
         for k in range(iters + 3):
             # k < iters: check, direction, apply.  k = iters: no apply.  k = iters + 1: the same gradient again (rejected pair).
             # k = iters + 2: the same gradient, tolerance_change = 1e30 (the g.d stop), apply, one more check
@@ -306,6 +302,9 @@ def test_lbfgs_iterations_at_a_length(case):
                 assert int(st[R.ST_FLAGS]) == 0, (where, st)           # the problem fires no break test
             else:
                 assert int(st[R.ST_FLAGS]) == R.F_LOSS                 # the same evaluation twice: no loss change, nothing else
+                if k == iters + 2:                                     # the rejected pair left count and H_diag alone, bit for bit
+                    assert (st[R.ST_COUNT], st[R.ST_HDIAG]) == kept, (where, st, kept)
+                kept = (st[R.ST_COUNT], st[R.ST_HDIAG])
             d_dev = H.direction(1e30 if k == iters + 2 else TOL_CHANGE)
             o64, old = (r.direction(g, d_prev, t_prev, 1e30 if k == iters + 2 else None) for r in (r64, rld))
             assert o64["accepted"] is old["accepted"] is (None if k == 0 else k <= iters), (where, o64["accepted"])
@@ -322,21 +321,31 @@ def test_lbfgs_iterations_at_a_length(case):
         rec64, recld = (r.check(g, loss, d_prev, st[R.ST_T]) for r in (r64, rld))
         _assert_exact_slots("after the stop", st, rec64, recld)
         assert int(st[R.ST_FLAGS]) == R.F_GTD | R.F_LOSS
-        assert (st[R.ST_COUNT], st[R.ST_NITER]) == (history, iters + 3)
+        assert (st[R.ST_COUNT], st[R.ST_NITER]) == (history, iters + 3) and (st[R.ST_COUNT], st[R.ST_HDIAG]) == kept
         _hold_scalars(w, "after the stop", st, r64, rld, gtd_scale)
         w.report()
+        return w
     finally:
         H.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", LENGTHS, ids=_id)
+def test_lbfgs_iterations_at_a_length(case):
+    n, T, history, forms = case
+    _assert_forms(n, T, forms)
+    _unsharded_run(_id(case), n, T, history, R.ChainProblem(n), history + 3)
+
+
 # ---------------------------------------------------------------------------------------------------------------- sharded
-def _sharded_run(name, lengths, T, history=5):
+def _sharded_run(name, lengths, T, history=5, prob=None, iters=None):
     """``len(lengths)`` handles in one process, nothing exchanged: their payloads concatenated in rank order go to every finish.
-    The reference works on the whole vector [handle 0 | handle 1]."""
+    The reference works on the whole vector [handle 0 | handle 1].  ``prob``: the ChainProblem of the summed length; ``iters``:
+    history + 3 unless given."""
     R.assert_longdouble_is_wider()
     world, n = len(lengths), sum(lengths)
     w = _Worst(name, T)
-    prob = R.ChainProblem(n)
+    prob = R.ChainProblem(n) if prob is None else prob
     r64, rld = R.LbfgsReference(history, np.float64), R.LbfgsReference(history, np.longdouble)
     cuts = np.cumsum([0] + list(lengths))
     shards = []
@@ -361,7 +370,7 @@ def _sharded_run(name, lengths, T, history=5):
 
         assert np.array_equal(read_x(), x)
         d_prev = t_prev = None
-        iters = history + 3
+        iters = history + 3 if iters is None else iters
         skip_at = 3                                                   # before this iteration: one finish with want_direction = 0
         for k in range(iters + 1):
             where = f"k={k}"
@@ -400,6 +409,7 @@ def _sharded_run(name, lengths, T, history=5):
                 _assert_applied(where, x_old, d_prev, t_prev, x)
         assert (st[R.ST_COUNT], st[R.ST_NITER]) == (history, iters + 1)
         w.report()
+        return w
     finally:
         for s in shards:
             s.close()

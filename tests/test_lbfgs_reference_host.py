@@ -2,7 +2,9 @@
 the CPU -- losses, parameters, n_iter and the number of pairs kept, to the tolerances tests/test_gpu_lbfgs.py holds
 FusedLBFGS to against torch --, it states the rejected-pair rule and the g.d stop, and three mutations of it (``>=`` in the
 acceptance rule, the newest pair left out of the first loop, H_diag not refreshed) each break the comparison with torch, so
-the comparison is able to see them."""
+the comparison is able to see them.  Full histories (last section): the stiff chain fills every history
+tests/test_gpu_lbfgs_histories.py runs, the reference follows torch iteration by iteration at 100 and 257 full pairs, and the
+coefficient-space form the kernels evaluate fits half of that file's tolerance when stated in plain float64."""
 import numpy as np
 import pytest
 import torch
@@ -231,3 +233,140 @@ def test_mutation_breaks_the_torch_comparison(case, mutant):
     _compare(R.LbfgsReference, fun, x0, 3, n_steps)                               # the comparison itself holds ...
     with pytest.raises(AssertionError):                                           # ... and sees the mutation
         _compare(mutant, fun, x0, 3, n_steps)
+
+
+# ------------------------------------------------------------------------------------------------ full histories (stiff chain)
+def _history_cases():
+    """Every (n, T, history, iterations) tests/test_gpu_lbfgs_histories.py runs (the same lists: the two cannot drift)."""
+    f = R.HISTORY_FUSED
+    cases = list(R.HISTORY_UNSHARDED) + [(sum(lengths), T, h, it) for lengths, T, h, it in R.HISTORY_SHARDED]
+    return cases + [(f["n"], np.float64, f["history"], f["max_iter"])]
+
+
+def _case_id(case):
+    n, T, history, iters = case
+    return f"n{n}-{T.__name__}-h{history}-it{iters}"
+
+
+@pytest.mark.parametrize("n", sorted({c[0] for c in _history_cases()}))
+def test_stiff_chain_gradient_is_the_derivative_of_its_loss(n):
+    prob = R.stiff_chain(n)
+    assert prob.a.min() >= 1.0 and prob.a.max() > 5e4 and np.array_equal(prob.b, R.ChainProblem(n, seed=R.STIFF_SEED).b)
+    x = prob.x0.copy()
+    _, g = prob.loss_and_grad(x)
+    v = np.random.default_rng(1).standard_normal(n)
+    h = 1e-6
+    fd = (prob.loss_and_grad(x + h * v)[0] - prob.loss_and_grad(x - h * v)[0]) / (2 * h)       # exact for a quadratic, but for rounding
+    assert abs(fd - g @ v) <= 1e-6 * abs(g @ v)
+
+
+@pytest.mark.parametrize("case", _history_cases(), ids=_case_id)
+def test_stiff_chain_fills_the_history_the_gpu_test_needs(case):
+    """Free float64 run on the stiff chain: every pair is accepted, no break flag fires, g.d stays below -1e-3 (far from
+    -tolerance_change), the history is full from iteration ``history`` on, the first step takes the 1 / |g|_1 branch."""
+    n, T, history, iters = case
+    assert iters >= history + 3
+    prob = R.stiff_chain(n)
+    ref, x = R.LbfgsReference(history), prob.x0.astype(T)
+    for k in range(iters):
+        loss, g = prob.loss_and_grad(x)
+        assert g.dtype == T and float(T(loss)) == loss
+        out = ref.iterate(g, loss)
+        assert out["status"][R.ST_FLAGS] == 0 and not out["stop_gtd"], (k, out["status"])
+        assert out["gtd"] < -1e-3, (k, out["gtd"])
+        assert out["accepted"] is (None if k == 0 else True), k
+        assert out["count"] == min(k, history), (k, out["count"])
+        assert (out["t"] < 1e-3) if k == 0 else (out["t"] == 1.0)
+        x = R.apply_update(x, out["d"], out["t"])
+    assert ref.count == history and ref.n_iter == iters
+
+
+def _pin_against_torch_per_iteration(ref_cls, history, iters, n=1031):
+    """``torch.optim.LBFGS(max_iter=1)`` one ``step`` at a time (its state persists: the same recursion as one long step, the
+    direction and the step readable after every iteration).  Free trajectories of torch and the reference drift apart by
+    rounding amplified over hundreds of iterations (1e-3 of max|x| after 260 on this problem), so the float64 and the
+    longdouble reference are FED torch's d and t -- their history then has torch's bits -- and torch's d, scaled by the summed
+    magnitudes of its terms, must be within ``R.allowed`` of the gap between the two; accepted flags and pair counts equal."""
+    R.assert_longdouble_is_wider()
+    prob = R.stiff_chain(n)
+    p = torch.nn.Parameter(torch.from_numpy(prob.x0.copy()))
+    opt = torch.optim.LBFGS([p], max_iter=1, history_size=history)
+    seen = {}
+
+    def closure():
+        seen["loss"], seen["g"] = prob.loss_and_grad(p.detach().numpy().copy())
+        p.grad = torch.from_numpy(seen["g"].copy())
+        return torch.tensor(seen["loss"], dtype=torch.float64)
+
+    r64, rld = ref_cls(history, np.float64), ref_cls(history, np.longdouble)
+    d_prev = t_prev = None
+    worst = [0.0, 0.0]
+    for k in range(iters):
+        opt.step(closure)
+        st = opt.state[p]
+        d_torch, t_torch = st["d"].numpy().copy(), float(st["t"])
+        assert st["n_iter"] == k + 1
+        o64, old = (r.iterate(seen["g"], seen["loss"], d_prev, t_prev) for r in (r64, rld))
+        assert o64["accepted"] is old["accepted"] is (None if k == 0 else True), k
+        assert o64["count"] == old["count"] == len(st.get("old_dirs") or []) == min(k, history), k
+        t_ld = float(old["t"])                                                    # (1 / |g|_1 at k = 0: the sum's rounding; then lr)
+        assert abs(t_torch - t_ld) <= R.allowed(abs(float(o64["t"]) - t_ld) / t_ld) * t_ld and (k == 0 or t_torch == 1.0), k
+        scale = np.maximum(r64.term_magnitudes(seen["g"]), np.finfo(np.float64).tiny)
+        gap = float((np.abs(r64.r.astype(np.longdouble) - rld.r) / scale).max())
+        err = float((np.abs(d_torch.astype(np.longdouble) - rld.r) / scale).max())
+        worst = [max(worst[0], err), max(worst[1], gap)]
+        assert err <= R.allowed(gap), (k, err, gap, R.allowed(gap))
+        d_prev, t_prev = d_torch, t_torch
+    assert r64.count == history and len(opt.state[p]["old_dirs"]) == history
+    print(f"LBFGS-TORCH-PIN h{history}: torch {worst[0]:.2e} reference {worst[1]:.2e}")
+
+
+@pytest.mark.parametrize("history", [100, 257])
+def test_reference_follows_torch_iteration_by_iteration_at_a_full_history(history):
+    _pin_against_torch_per_iteration(R.LbfgsReference, history, history + 3)
+
+
+@pytest.mark.parametrize("mutant", [_NewestPairLeftOut, _StaleH])
+def test_mutation_breaks_the_per_iteration_torch_pin(mutant):
+    """(``_AcceptEqual`` cannot show here: no y.s of this problem is exactly 1e-10; the scripted case above holds it.)"""
+    with pytest.raises(AssertionError):
+        _pin_against_torch_per_iteration(mutant, 100, 103)
+
+
+COEFFICIENT_CASES = [(1031, np.float64, 65), (1031, np.float64, 128), (1031, np.float64, 257), (1031, np.float32, 100),
+                     (1031, np.float32, 129), (1031, np.float32, 257), (4096, np.float32, 128)]
+
+
+@pytest.mark.parametrize("case", COEFFICIENT_CASES, ids=lambda c: f"n{c[0]}-{c[1].__name__}-h{c[2]}")
+def test_coefficient_space_form_fits_half_the_tolerance(case):
+    """The kernels run the recursion on Gram entries, not on vectors.  A plain float64 numpy statement of THAT form
+    (``R.coefficient_direction``), on the history the float64 reference accumulates in a free run on the stiff chain, stays
+    within 0.5 x ``R.allowed`` of the longdouble vector-space run, d and g.d, every 7th iteration and the last four: the form
+    itself does not use up the tolerance tests/test_gpu_lbfgs_histories.py keeps (MARGIN = 32), so a kernel that exceeds it
+    is wrong.  Worst share of ``allowed`` per case is printed."""
+    n, T, history = case
+    R.assert_longdouble_is_wider()
+    prob = R.stiff_chain(n)
+    r64, rld = R.LbfgsReference(history, np.float64), R.LbfgsReference(history, np.longdouble)
+    x, iters = prob.x0.astype(T), history + 3
+    d_prev = t_prev = None
+    share = {"d": 0.0, "gtd": 0.0}
+    for k in range(iters):
+        loss, g = prob.loss_and_grad(x)
+        o64 = r64.iterate(g, loss)
+        old = rld.iterate(g, loss, d_prev, t_prev)                                 # the float64 run's history, longdouble arithmetic
+        assert o64["accepted"] is old["accepted"] and o64["count"] == old["count"] == min(k, history)
+        if k % 7 == 0 or k >= iters - 4:
+            d, gtd, H = R.coefficient_direction(r64.S, r64.Y, g)
+            scale = np.maximum(r64.term_magnitudes(g), np.finfo(np.float64).tiny)
+            gtd_scale = float((np.abs(g.astype(np.float64)) * scale).sum())
+            ld = np.longdouble
+            for what, got, a, b, sc in (("d", d, r64.r, rld.r, scale), ("gtd", gtd, r64.gtd, rld.gtd, gtd_scale)):
+                gap = float((np.abs(np.asarray(a, dtype=ld) - b) / sc).max())
+                err = float((np.abs(np.asarray(got, dtype=ld) - b) / sc).max())
+                share[what] = max(share[what], err / R.allowed(gap))
+                assert err <= 0.5 * R.allowed(gap), (k, what, err, gap)
+            assert abs(H - float(rld.H_diag)) <= 0.5 * R.allowed(abs(float(r64.H_diag) - float(rld.H_diag)) / float(rld.H_diag)) * float(rld.H_diag)
+        d_prev, t_prev = o64["d"], o64["t"]
+        x = R.apply_update(x, o64["d"], o64["t"])
+    print(f"LBFGS-COEFFICIENT n{n} {T.__name__} h{history}: share of allowed  d {share['d']:.2f}  g.d {share['gtd']:.2f}")
