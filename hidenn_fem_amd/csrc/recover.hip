@@ -246,8 +246,8 @@ template <int NPE>
 static int hyper_stress_recover(const char *who, int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
                                 int64_t nn, const int32_t *adj_ptr, const int32_t *adj, const double *lame,
                                 double *nodal_stress, double *nodal_J, double *nodal_area, void *stream) {
-    if (ne == 0 || nn == 0) return 0;
     if (ne < 0 || nn < 0) { set_error(std::string(who) + ": negative count"); return -1; }
+    if (ne == 0 || nn == 0) return 0;
     if (!(X && U && conn && adj_ptr && adj && lame && nodal_stress)) { set_error(std::string(who) + ": null pointer"); return -1; }
     if (ne >= ((int64_t)1 << 29) || nn > INT32_MAX - kRecBlock) {
         set_error(std::string(who) + ": fewer than 2^29 elements (adjacency entries are e << 2 | c) and int32 node ids");
@@ -264,8 +264,8 @@ template <int NPE>
 static int hyper_zz_error(const char *who, int device, const double *X, const double *U, const int32_t *conn, int64_t ne,
                           const double *nodal_stress, const double *lame, double *eta2, double *norm2, double *partials,
                           double *totals, void *stream) {
-    if (ne == 0) return 0;
     if (ne < 0) { set_error(std::string(who) + ": negative element count"); return -1; }
+    if (ne == 0) return 0;
     if (!(X && U && conn && nodal_stress && lame && eta2 && partials && totals)) { set_error(std::string(who) + ": null pointer"); return -1; }
     if (ne >= ((int64_t)1 << 29)) { set_error(std::string(who) + ": fewer than 2^29 elements"); return -1; }
     CauchyLaw law;
