@@ -2,9 +2,11 @@
 // level -- the vector kernels, the status record, the halt logic and the hfem_cg_* entry points.  Nothing here knows the
 // element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
 // (the model's own QUAD4 plan), tri3_hyper_cg.hip or quad4_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point,
-// on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py),
-// tri3_dyn_cg.hip or quad4_dyn_cg.hip (the shifted operator c_K K + c_M M of a Newmark step after hfem_cg_setup_shifted, on the
-// plans of the plain kernels: hidenn_fem_amd/dynamics.py), chosen in cg_apply and cg_diag; the residual r = -dE/du comes from the graded energy kernel, called by the host once per solve.
+// on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
+// cg_apply and cg_diag.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
+// hidenn_fem_amd/dynamics.py) is no element kind of its own: it is the MASS instance of the kernels of tri3_cg.hip and
+// quad4_cg.hip, picked by their launchers.  The residual r = -dE/du comes from the graded energy kernel, called by the host
+// once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
 //                   order, forms beta, and applies the stopping test (START: r = -g0, z = D^-1 r, |f|).
 //   cg_rz_kernel    rho = r^T z in block order, then beta (precond = AMG only).
@@ -178,7 +180,7 @@ struct hfem_cg {
     // bound by hfem_cg_setup
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     hfem::Tri3Consts k{};
-    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; kernels of tri3_dyn_cg.hip / quad4_dyn_cg.hip)
+    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; the MASS instances of tri3_cg.hip / quad4_cg.hip)
     bool shifted = false;
     hfem::DynMass dm{};
     // bound by hfem_cg_setup_hyper
@@ -192,7 +194,8 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     hfem::CgElemArgs A;
     A.plan = c->plan; A.n_tiles = c->n_tiles; A.block = c->block; A.phys = c->phys; A.x_free = c->x_free; A.x_fixed = c->x_fixed;
     A.k = c->k; A.lds = lds; A.s = s;
-    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq; A.dm = c->dm;
+    A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq;
+    A.shifted = c->shifted; A.dm = c->dm;
     return A;
 }
 
@@ -202,8 +205,6 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
     const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
-    else if (c->shifted && c->quad) hfem::launch_quad4_dyn_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
-    else if (c->shifted) hfem::launch_tri3_dyn_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
@@ -212,8 +213,6 @@ void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStrea
     const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
-    else if (c->shifted && c->quad) hfem::launch_quad4_dyn_cg_diag(A, diag, c->dinv, precond);
-    else if (c->shifted) hfem::launch_tri3_dyn_cg_diag(A, diag, c->dinv, precond);
     else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }

@@ -1,6 +1,6 @@
 // Implicit transient dynamics, gfx950 (MI355X): the vector kernels of a Newmark step in the a-form (hidenn_fem_amd/dynamics.py,
 // DESIGN 26).  The linear solve of a step is the PCG driver's (cg.hip) on the shifted operator A = c_M M + c_K K
-// (tri3_dyn_cg.hip, quad4_dyn_cg.hip); what is left of a step is three elementwise passes over fp64 rows [n][2] in the storage
+// (the MASS instances of tri3_cg.hip, quad4_cg.hip); what is left of a step is three elementwise passes over fp64 rows [n][2] in the storage
 // order of u_free:
 //   newmark_predict_kernel   u~ = u + dt v + dt^2 (1/2 - beta) a,   v~ = v + dt (1 - gamma) a,   w = u~ + beta_R v~
 //   newmark_rhs_kernel       rhs = load b0 - K w - alpha_R M v~;   g_zero = rhs,   g0 = A a - rhs  (what hfem_cg_start takes:

@@ -3,10 +3,11 @@
 // For the element kernels (apply and block diagonal of tri3_cg.hip, quad4_cg.hip, tri3_hyper_cg.hip and quad4_hyper_cg.hip) the phases that do not depend on
 // the element: the iteration state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
 // block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
-// element, 3 or 4 corners, and the x row code.  For the shifted operator of implicit dynamics (tri3_dyn_cg.hip,
-// quad4_dyn_cg.hip, the shifted assembly of tri3_amg.hip): the mass coefficients and one element's mass row.  Last, the launchers of the element kernels, which the PCG driver (cg.hip)
-// calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the index loads, the
-// staging of coordinates and p, and the slot loop.
+// element, 3 or 4 corners, and the x row code.  For the shifted operator of implicit dynamics (the MASS instances of the
+// kernels of tri3_cg.hip and quad4_cg.hip and of amg_assemble_kernel, tri3_amg.hip): the mass coefficients, the QUAD4 Gauss
+// point determinants and shape values, and one element's mass row.  Last, the launchers of the element kernels, which the PCG
+// driver (cg.hip) calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the
+// index loads, the staging of coordinates and p, the slot loop, and the mass part of the slot loop.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -182,8 +183,9 @@ __device__ __forceinline__ double2 x_row(const double2 *x_free, const double2 *x
 }
 
 // ---------------------------------------------------------------- the shifted operator A = c_K K + c_M M
-// The mass part of tri3_dyn_cg.hip, quad4_dyn_cg.hip and amg_assemble_shifted_kernel as two run-time coefficients (c_M includes
-// the density), so consistent and lumped mass are one instance.  K's part is scaled on the host: the material constants times c_K.
+// The mass part of the MASS instances (tri3_cg.hip, quad4_cg.hip, amg_assemble_kernel) as two run-time coefficients (c_M
+// includes the density), so consistent and lumped mass are one instance.  K's part is scaled on the host: the material
+// constants times c_K.  Every instance takes a DynMass by value; MASS = false does not read it.
 //   TRI3   M_e[a][b] = |det J| (m_off + m_dd delta_ab):  consistent m_off = m_dd = c_M / 24;  lumped m_off = 0, m_dd = c_M / 6
 //   QUAD4  M_e[a][b] = sum_q |det J_q| N_a(q) (m_off N_b(q) + m_dd delta_ab):  consistent m_off = c_M, m_dd = 0;  lumped the reverse
 struct DynMass {
@@ -194,6 +196,13 @@ inline DynMass dyn_mass(bool quad, double c_m, bool lumped) {
     if (quad) { m.m_off = lumped ? 0.0 : c_m; m.m_dd = lumped ? c_m : 0.0; }
     else { m.m_off = lumped ? 0.0 : c_m / 24.0; m.m_dd = lumped ? c_m / 6.0 : c_m / 24.0; }
     return m;
+}
+// A stiffness entry plus its mass entry in the MASS instance, the stiffness entry itself otherwise: never "+ 0.0" in a plain
+// instance (without fast-math that is a real add, and it changes a -0.0).
+template <bool MASS>
+__device__ __forceinline__ double with_mass(double v, double m) {
+    if constexpr (MASS) return v + m;
+    else return v;
 }
 inline Tri3Consts scaled_consts(Tri3Consts k, double c_k) {
     k.c11 *= c_k; k.c12 *= c_k; k.c22 *= c_k; k.c33 *= c_k;
@@ -229,7 +238,7 @@ __device__ __forceinline__ constexpr double quad4_n(int a, int q) {
 }
 
 // Row a of one element's mass in the two coefficients, a a run-time corner (selects and signs, never an index of a local
-// array): mrow[b] = M_e[a][b].  For the diag kernels' M_e[a][a] and the AMG fine level of A (tri3_amg.hip).
+// array): mrow[b] = M_e[a][b].  For the AMG fine level of A (tri3_amg.hip); the diag kernels form their M_e[a][a] inline.
 __device__ __forceinline__ void dyn_mass_row(const double2 (&X)[3], int a, const DynMass &m, double (&mrow)[3]) {
     const double A = fabs((X[0].x - X[2].x) * (X[1].y - X[2].y) - (X[1].x - X[2].x) * (X[0].y - X[2].y));
 #pragma unroll
@@ -264,15 +273,17 @@ struct CgElemArgs {
     // quad4_hyper_cg.hip: c = mu - lambda L per slot and Gauss point, [n_tiles][4][elem_stride]; the diag launch of a
     // linearisation writes it, its apply launches read it instead of calling log1p
     double *cq = nullptr;
-    // the shifted operator (tri3_dyn_cg.hip, quad4_dyn_cg.hip): k carries c_K, dm the mass coefficients
+    // shifted: the operator A = c_K K + c_M M (the MASS instances of tri3_cg.hip, quad4_cg.hip): k carries c_K, dm the mass
+    // coefficients
+    bool shifted = false;
     DynMass dm{};
 };
-// q = K p (st != NULL an iteration, st == NULL the standalone apply)
+// q = K p, or q = A p where A.shifted (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                           unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                            unsigned *ticket, double *st, double *host, double *pq_out);
-// 2x2 diagonal blocks of K and their inverses (store_jacobi_block)
+// 2x2 diagonal blocks of K (of A where A.shifted) and their inverses (store_jacobi_block)
 void launch_tri3_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 // The Neo-Hookean tangent at A.u_lin_free (tri3_hyper_cg.hip, one-element-per-slot TRI3 plan): q = K_T p, and the blocks with
@@ -288,14 +299,5 @@ constexpr int kQuad4HyperCgBlock = 256;
 void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
                                  double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
-
-// The shifted operator A = c_K K + c_M M (tri3_dyn_cg.hip on the paired TRI3 plan, quad4_dyn_cg.hip on the QUAD4 plan; A.k is
-// scaled by c_K, A.dm carries c_M): q = A p and the 2x2 diagonal blocks of A, the instance matrix of the plain launchers.
-void launch_tri3_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
-                              double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
-void launch_quad4_dyn_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
-                               double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
-void launch_tri3_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
-void launch_quad4_dyn_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 
 }  // namespace hfem

@@ -13,6 +13,17 @@
 //   quad4_cg_diag_kernel    2x2 diagonal blocks of K (block Jacobi), once per refresh: per owned corner a of every element the
 //                           block d2E/du_a^2 = the element's u-gradient at u_a = e_x / e_y, accumulated into the owner node.
 // The 2x2 rule's weights are 1, so the triangle weight sum W of the shared entry points is not read here.
+//
+// MASS = true is the shifted operator A = c_K K + c_M M of a Newmark step (hidenn_fem_amd/dynamics.py), which the
+// launchers pick once hfem_cg_setup_shifted has bound the solver: the same kernels with the mass code compiled in.  The
+// stiffness part is quad4_element_u on material constants the host scaled by c_K; the mass part is formed in the slot loop
+// from the corner rows the element already holds:
+//   M_e[a][b] = sum_q |det J_q| N_a(q) (m_off N_b(q) + m_dd delta_ab),  2x2 Gauss points
+//   (M_e p)_a = sum_q |det J_q| N_a(q) (m_off p_h(q) + m_dd p_a),  p_h(q) = sum_b N_b(q) p_b
+// consistent: m_off = c_M, m_dd = 0; lumped (the row sum on the diagonal): m_off = 0, m_dd = c_M (DynMass, hfem_cg_dev.h; c_M
+// includes the density; run-time coefficients, not instances).  Always |det J_q|: no gradient convention enters the mass.
+// The tile energy is c_K e + 1/2 c_M p^T M_e p, so apply_finish's p^T q = 2 x sum stays right.  The diag kernel adds
+// M_e[a][a] to xx and yy of every block.  MASS = false takes the DynMass argument and does not read it.
 #include <hip/hip_runtime.h>
 
 #include "hfem_cg_dev.h"
@@ -20,14 +31,47 @@
 namespace hfem {
 namespace {
 
-// ---------------------------------------------------------------- q = K p
+// One element's mass part: adds (M_e p)_a to the four rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double quad4_mass_rows(const double2 (&Xn)[4], const double2 (&Pn)[4], const DynMass &m,
+                                                  double2 (&gu)[4]) {
+    double ad[4];
+    quad4_abs_dets(Xn, ad);
+    double2 r[4];
+    double nl[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { r[a] = make_double2(0.0, 0.0); nl[a] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double hx = 0.0, hy = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { hx += quad4_n(b, q) * Pn[b].x; hy += quad4_n(b, q) * Pn[b].y; }
+        const double w = ad[q] * m.m_off;
+        hx *= w; hy *= w;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            r[a].x += quad4_n(a, q) * hx; r[a].y += quad4_n(a, q) * hy;
+            nl[a] += quad4_n(a, q) * ad[q];
+        }
+    }
+    double e = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double wl = nl[a] * m.m_dd;
+        r[a].x = __builtin_fma(wl, Pn[a].x, r[a].x); r[a].y = __builtin_fma(wl, Pn[a].y, r[a].y);
+        gu[a].x += r[a].x; gu[a].y += r[a].y;
+        e += Pn[a].x * r[a].x + Pn[a].y * r[a].y;
+    }
+    return 0.5 * e;
+}
+
+// ---------------------------------------------------------------- q = K p (MASS: q = A p)
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
-// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).
+// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  MASS: k is the material constants times c_K.
 // LDS: xy[cap_nodes] double2 | p[cap_nodes] double2 | acc[2][cap_owned] | red[BLOCK / 64 + 2]
-template <int BLOCK, int NPT, int EPT, bool PHYS>
+template <int BLOCK, int NPT, int EPT, bool PHYS, bool MASS>
 __global__ __launch_bounds__(BLOCK) void quad4_cg_apply_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k,
+    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k, DynMass dm,
     double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out, int cap_nodes, int cap_owned) {
     if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
     extern __shared__ double2 lds[];
@@ -87,7 +131,8 @@ __global__ __launch_bounds__(BLOCK) void quad4_cg_apply_kernel(
                 Xn[j] = nd_xy[l[j]];
                 Pn[j] = nd_p[l[j]];
             }
-            const double e = quad4_element_u<PHYS>(Xn, Pn, k, gu);
+            double e = quad4_element_u<PHYS>(Xn, Pn, k, gu);
+            if constexpr (MASS) e += quad4_mass_rows(Xn, Pn, dm, gu);
             if (p & kHomeBit) e_loc += e;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -104,10 +149,11 @@ __global__ __launch_bounds__(BLOCK) void quad4_cg_apply_kernel(
 }
 
 // ---------------------------------------------------------------- block-Jacobi setup
+// MASS: the 2x2 diagonal blocks of A, the mass on xx and yy: M_e[a][a] = sum_q |det J_q| N_a(q) (m_off N_a(q) + m_dd).
 // LDS: xy[cap_nodes] double2 | acc[3][cap_owned]
-template <int BLOCK, int NPT, int EPT, bool PHYS>
+template <int BLOCK, int NPT, int EPT, bool PHYS, bool MASS>
 __global__ __launch_bounds__(BLOCK) void quad4_cg_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
-                                                              const double2 *__restrict__ x_fixed, Tri3Consts k,
+                                                              const double2 *__restrict__ x_fixed, Tri3Consts k, DynMass dm,
                                                               double *__restrict__ diag, double *__restrict__ dinv, int precond,
                                                               int cap_nodes, int cap_owned) {
     extern __shared__ double2 lds[];
@@ -136,15 +182,22 @@ __global__ __launch_bounds__(BLOCK) void quad4_cg_diag_kernel(PlanDev pd, const 
         const int l[4] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask),
                           (int)((p >> (2 * kLocalBits)) & kLocalMask), (int)(pd.elem_pack_hi[i] & kLocalMask)};
         const double2 Xn[4] = {nd_xy[l[0]], nd_xy[l[1]], nd_xy[l[2]], nd_xy[l[3]]};
+        double ad[4];                                       // |det J_q| (MASS only)
+        if constexpr (MASS) quad4_abs_dets(Xn, ad);
         // the corner blocks of one element: column c of K_aa = the gradient at u_a = e_c, u_b = 0 (b != a)
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             if (l[a] >= n_owned) continue;
+            double mm = 0.0;                                // M_e[a][a] (MASS only)
+            if constexpr (MASS) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) mm += ad[q] * quad4_n(a, q) * (dm.m_off * quad4_n(a, q) + dm.m_dd);
+            }
             double2 gu[4], hu[4];
             unit_columns<PHYS>(Xn, a, k, gu, hu);
-            unsafeAtomicAdd(&acc0[l[a]], gu[a].x);
+            unsafeAtomicAdd(&acc0[l[a]], with_mass<MASS>(gu[a].x, mm));
             unsafeAtomicAdd(&acc1[l[a]], 0.5 * (gu[a].y + hu[a].x));
-            unsafeAtomicAdd(&acc2[l[a]], hu[a].y);
+            unsafeAtomicAdd(&acc2[l[a]], with_mass<MASS>(hu[a].y, mm));
         }
     }
     __syncthreads();
@@ -160,32 +213,38 @@ __global__ __launch_bounds__(BLOCK) void quad4_cg_diag_kernel(PlanDev pd, const 
 // ---------------------------------------------------------------- launchers
 // Tile shapes: what hfem_quad4_energy_plan_ex accepts (max_nodes <= 4 * 256, max_elems <= 4 * 256; hfem_cg_create refuses the
 // rest), in the energy kernel's two register tilings: 3 nodes and 3 slots per thread (the default tile shape) or 4 and 4.
+// Each in both gradient conventions (A.phys) and without or with the mass (A.shifted).
 void launch_quad4_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                            unsigned *ticket, double *st, double *host, double *pq_out) {
     const HostPlan &h = A.plan->host;
     const PlanDev pd = plan_dev(A.plan);
-#define HFEM_Q4CG_APPLY(NPT, EPT, PH)                                                                                        \
-    hipLaunchKernelGGL((quad4_cg_apply_kernel<256, NPT, EPT, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.n_tiles,    \
-                       A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, partials, ticket, st, host, pq_out, h.max_nodes,        \
-                       h.max_owned)
-    if (h.max_nodes <= 3 * 256 && h.max_elems <= 3 * 256) {
-        if (A.phys) HFEM_Q4CG_APPLY(3, 3, true);
-        else HFEM_Q4CG_APPLY(3, 3, false);
-    } else {
-        if (A.phys) HFEM_Q4CG_APPLY(4, 4, true);
-        else HFEM_Q4CG_APPLY(4, 4, false);
-    }
+#define HFEM_Q4CG_APPLY(NPT, EPT, PH, MASS)                                                                                  \
+    hipLaunchKernelGGL((quad4_cg_apply_kernel<256, NPT, EPT, PH, MASS>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd,         \
+                       A.n_tiles, A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, A.dm, partials, ticket, st, host, pq_out,    \
+                       h.max_nodes, h.max_owned)
+#define HFEM_Q4CG_A(NPT, EPT)                                                                                                \
+    do {                                                                                                                     \
+        if (A.phys && A.shifted) HFEM_Q4CG_APPLY(NPT, EPT, true, true);                                                      \
+        else if (A.phys) HFEM_Q4CG_APPLY(NPT, EPT, true, false);                                                             \
+        else if (A.shifted) HFEM_Q4CG_APPLY(NPT, EPT, false, true);                                                          \
+        else HFEM_Q4CG_APPLY(NPT, EPT, false, false);                                                                        \
+    } while (0)
+    if (h.max_nodes <= 3 * 256 && h.max_elems <= 3 * 256) HFEM_Q4CG_A(3, 3);
+    else HFEM_Q4CG_A(4, 4);
+#undef HFEM_Q4CG_A
 #undef HFEM_Q4CG_APPLY
 }
 
 void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
     const HostPlan &h = A.plan->host;
     const PlanDev pd = plan_dev(A.plan);
-#define HFEM_Q4CG_DIAG(PH)                                                                                                   \
-    hipLaunchKernelGGL((quad4_cg_diag_kernel<256, 4, 4, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.x_free,          \
-                       A.x_fixed, A.k, diag, dinv, precond, h.max_nodes, h.max_owned)
-    if (A.phys) HFEM_Q4CG_DIAG(true);
-    else HFEM_Q4CG_DIAG(false);
+#define HFEM_Q4CG_DIAG(PH, MASS)                                                                                             \
+    hipLaunchKernelGGL((quad4_cg_diag_kernel<256, 4, 4, PH, MASS>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.x_free,    \
+                       A.x_fixed, A.k, A.dm, diag, dinv, precond, h.max_nodes, h.max_owned)
+    if (A.phys && A.shifted) HFEM_Q4CG_DIAG(true, true);
+    else if (A.phys) HFEM_Q4CG_DIAG(true, false);
+    else if (A.shifted) HFEM_Q4CG_DIAG(false, true);
+    else HFEM_Q4CG_DIAG(false, false);
 #undef HFEM_Q4CG_DIAG
 }
 

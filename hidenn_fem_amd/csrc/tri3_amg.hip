@@ -22,6 +22,8 @@
 //                         applies for QUAD4).  An inverted element or cell contributes zeros, so the matrix is exactly the
 //                         operator hfem_cg_apply applies on a hyper handle.  No atomics: bit-deterministic.
 //   amg_ns0_kernel        with u_free: the rotation column at the deformed position, (-(y + v), x + u).
+// Shifted setup (hfem_amg_setup_shifted, a Newmark step of implicit dynamics): the same numeric setup on
+// A_ff = c_K K_ff + c_M M_ff, assembled by the MASS instance of amg_assemble_kernel.
 // Everything from setup_level down is shared.  One handle may be set up by either entry point, in any order: pointers and
 // patterns never change, only values do, so a captured hfem_cg_iterate_amg graph stays valid across re-setups of either kind.
 // V-cycle (amg_cycle): Chebyshev degree 2 on D^-1 A over [lambda_hat / 30, lambda_hat], the same polynomial before and after
@@ -60,7 +62,9 @@ __device__ __forceinline__ int32_t find_slot(const int32_t *__restrict__ col, in
 }
 
 // ---------------------------------------------------------------- assembly (fine level, 2x2 blocks)
-template <int NPE, bool PHYS>
+// MASS: A_ff = c_K K_ff + c_M M_ff (implicit dynamics): the same walk, k scaled by c_K on the host, plus the
+// corner's mass row (dyn_mass_row, hfem_cg_dev.h) on xx and yy of every block.  MASS = false does not read dm.
+template <int NPE, bool PHYS, bool MASS>
 __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
                                                               const int32_t *__restrict__ fan_elem,
                                                               const int32_t *__restrict__ fan_corner,
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
                                                               const double2 *__restrict__ x_free,
                                                               const double2 *__restrict__ x_fixed,
                                                               const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
-                                                              Tri3Consts k) {
+                                                              Tri3Consts k, DynMass dm) {
     const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (r >= n) return;
     for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
@@ -78,53 +82,20 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
         const int32_t e = fan_elem[f], a = fan_corner[f];
         const int32_t *cx = conn_x + NPE * (size_t)e;
         double2 X[NPE], gu[NPE], hu[NPE];
+        double mrow[NPE];                                      // M_e[a][.] (MASS only)
 #pragma unroll
         for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
         unit_columns<PHYS>(X, a, k, gu, hu);                   // column (a, x) and (a, y) of K_e = rows (a, x) and (a, y)
+        if constexpr (MASS) dyn_mass_row(X, a, dm, mrow);
 #pragma unroll
         for (int b = 0; b < NPE; ++b) {
             const int32_t s = fan_slot[NPE * (size_t)f + b];
             if (s < 0) continue;
             double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
             double4 v = *p;
-            v.x += gu[b].x; v.y += gu[b].y; v.z += hu[b].x; v.w += hu[b].y;
-            *p = v;
-        }
-    }
-}
-
-// A_ff = c_K K_ff + c_M M_ff (implicit dynamics): amg_assemble_kernel's walk, k scaled by c_K on the host, plus the
-// corner's mass row (dyn_mass_row, hfem_cg_dev.h) on xx and yy of every block.  No atomics: bit-deterministic.
-template <int NPE, bool PHYS>
-__global__ __launch_bounds__(kBlock) void amg_assemble_shifted_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
-                                                                      const int32_t *__restrict__ fan_elem,
-                                                                      const int32_t *__restrict__ fan_corner,
-                                                                      const int32_t *__restrict__ fan_slot,
-                                                                      const int32_t *__restrict__ conn_x,
-                                                                      const double2 *__restrict__ x_free,
-                                                                      const double2 *__restrict__ x_fixed,
-                                                                      const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
-                                                                      Tri3Consts k, DynMass dm) {
-    const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
-    if (r >= n) return;
-    for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
-        *reinterpret_cast<double4 *>(a_val + 4 * (size_t)s) = make_double4(0.0, 0.0, 0.0, 0.0);
-    for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
-        const int32_t e = fan_elem[f], a = fan_corner[f];
-        const int32_t *cx = conn_x + NPE * (size_t)e;
-        double2 X[NPE], gu[NPE], hu[NPE];
-        double mrow[NPE];
-#pragma unroll
-        for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
-        unit_columns<PHYS>(X, a, k, gu, hu);
-        dyn_mass_row(X, a, dm, mrow);
-#pragma unroll
-        for (int b = 0; b < NPE; ++b) {
-            const int32_t s = fan_slot[NPE * (size_t)f + b];
-            if (s < 0) continue;
-            double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
-            double4 v = *p;
-            v.x += gu[b].x + mrow[b]; v.y += gu[b].y; v.z += hu[b].x; v.w += hu[b].y + mrow[b];
+            double xx = gu[b].x, yy = hu[b].y;
+            if constexpr (MASS) { xx += mrow[b]; yy += mrow[b]; }   // never "+ 0.0" in the plain instance
+            v.x += xx; v.y += gu[b].y; v.z += hu[b].x; v.w += yy;
             *p = v;
         }
     }
@@ -728,42 +699,38 @@ void setup_level(hfem_amg *a, size_t l, hipStream_t s) {
 
 hfem::Tri3Consts consts(const double mat[4], double W) { return hfem::make_consts(mat, W, nullptr); }
 
-void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, hipStream_t s) {
-    const DevLevel &L = a->lv[0];
-    const bool quad = a->npe == 4;
-    const hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);  // QUAD4: the 2x2 rule's weights are 1, W is not read
-#define HFEM_AMG_ASM(NPE, PH)                                                                                                 \
-    hipLaunchKernelGGL((hfem::amg_assemble_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr, a->fan_elem,  \
-                       a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed, L.a_ptr,      \
-                       L.a_val, k)
-    if (quad) {
-        if (a->phys) HFEM_AMG_ASM(4, true);
-        else HFEM_AMG_ASM(4, false);
-    } else {
-        if (a->phys) HFEM_AMG_ASM(3, true);
-        else HFEM_AMG_ASM(3, false);
-    }
-#undef HFEM_AMG_ASM
-}
+// the coefficients of the shifted operator c_k K_ff + c_m M_ff (c_m includes the density)
+struct Shift {
+    double c_k, c_m;
+    bool lumped;
+};
 
-void assemble_shifted(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, double c_k,
-                      double c_m, bool lumped, hipStream_t s) {
+// sh == nullptr: K_ff; otherwise the shifted operator, the MASS instance of the same kernel
+void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, const Shift *sh,
+              hipStream_t s) {
     const DevLevel &L = a->lv[0];
     const bool quad = a->npe == 4;
-    const hfem::Tri3Consts k = hfem::scaled_consts(consts(mat, quad ? 1.0 : W), c_k);
-    const hfem::DynMass dm = hfem::dyn_mass(quad, c_m, lumped);
-#define HFEM_AMG_ASM_SHIFTED(NPE, PH)                                                                                         \
-    hipLaunchKernelGGL((hfem::amg_assemble_shifted_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,       \
+    hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);        // QUAD4: the 2x2 rule's weights are 1, W is not read
+    hfem::DynMass dm;
+    if (sh) {
+        k = hfem::scaled_consts(k, sh->c_k);
+        dm = hfem::dyn_mass(quad, sh->c_m, sh->lumped);
+    }
+#define HFEM_AMG_ASM(NPE, PH, MASS)                                                                                           \
+    hipLaunchKernelGGL((hfem::amg_assemble_kernel<NPE, PH, MASS>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,         \
                        a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed,  \
                        L.a_ptr, L.a_val, k, dm)
-    if (quad) {
-        if (a->phys) HFEM_AMG_ASM_SHIFTED(4, true);
-        else HFEM_AMG_ASM_SHIFTED(4, false);
-    } else {
-        if (a->phys) HFEM_AMG_ASM_SHIFTED(3, true);
-        else HFEM_AMG_ASM_SHIFTED(3, false);
-    }
-#undef HFEM_AMG_ASM_SHIFTED
+#define HFEM_AMG_A(NPE)                                                                                                       \
+    do {                                                                                                                      \
+        if (a->phys && sh) HFEM_AMG_ASM(NPE, true, true);                                                                     \
+        else if (a->phys) HFEM_AMG_ASM(NPE, true, false);                                                                     \
+        else if (sh) HFEM_AMG_ASM(NPE, false, true);                                                                          \
+        else HFEM_AMG_ASM(NPE, false, false);                                                                                 \
+    } while (0)
+    if (quad) HFEM_AMG_A(4);
+    else HFEM_AMG_A(3);
+#undef HFEM_AMG_A
+#undef HFEM_AMG_ASM
 }
 
 void assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
@@ -869,7 +836,7 @@ extern "C" int hfem_amg_assemble(hfem_amg *a, const double *x_free, const double
                                  void *stream) {
     HFEM_ARG_CHECK(a && x_free && mat, "null pointer");
     if (int rc = hfem::use_device(a->device)) return rc;
-    assemble(a, x_free, x_fixed, mat, W, (hipStream_t)stream);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, (hipStream_t)stream);
     return hfem::launch_status("hfem_amg_assemble");
 }
 
@@ -878,7 +845,7 @@ extern "C" int hfem_amg_setup(hfem_amg *a, const double *x_free, const double *x
     HFEM_ARG_CHECK(a && x_free && mat && coarse_out, "null pointer");
     if (int rc = hfem::use_device(a->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    assemble(a, x_free, x_fixed, mat, W, s);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup");
@@ -898,7 +865,8 @@ extern "C" int hfem_amg_assemble_shifted(hfem_amg *a, const double *x_free, cons
     HFEM_ARG_CHECK(a && x_free && mat, "null pointer");
     HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
     if (int rc = hfem::use_device(a->device)) return rc;
-    assemble_shifted(a, x_free, x_fixed, mat, W, c_k, c_m, lumped != 0, (hipStream_t)stream);
+    const Shift sh{c_k, c_m, lumped != 0};
+    assemble(a, x_free, x_fixed, mat, W, &sh, (hipStream_t)stream);
     return hfem::launch_status("hfem_amg_assemble_shifted");
 }
 
@@ -909,7 +877,8 @@ extern "C" int hfem_amg_setup_shifted(hfem_amg *a, const double *x_free, const d
     HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
     if (int rc = hfem::use_device(a->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    assemble_shifted(a, x_free, x_fixed, mat, W, c_k, c_m, lumped != 0, s);
+    const Shift sh{c_k, c_m, lumped != 0};
+    assemble(a, x_free, x_fixed, mat, W, &sh, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup_shifted");

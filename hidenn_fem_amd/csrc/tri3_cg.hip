@@ -14,6 +14,17 @@
 //                         writes alpha = rho / p^T q.  Nothing runs once the status record says halted.
 //   tri3_cg_diag_kernel   2x2 diagonal blocks of K (block Jacobi), once per refresh: per corner a of every element the
 //                         block d2E/du_a^2 = the element gradient at u = unit vector at a, accumulated into the owner node.
+//
+// MASS = true is the shifted operator A = c_K K + c_M M of a Newmark step (hidenn_fem_amd/dynamics.py), which the
+// launchers pick once hfem_cg_setup_shifted has bound the solver: the same kernels with the mass code compiled in.  The
+// stiffness part is tri3_element on material constants the host scaled by c_K (K is linear in them, so gu and e arrive
+// scaled); the mass part is formed in the slot loop from what the element already holds -- the corner coordinates and the
+// corner values of p -- with no extra memory traffic:
+//   M_e[a][b] = |det J| (m_off + m_dd delta_ab),  consistent: m_off = m_dd = c_M / 24,  lumped: m_off = 0, m_dd = c_M / 6
+// (c_M includes the density; run-time coefficients, not instances).  Always |det J|: no gradient convention enters the mass.
+//   (M_e p)_a = |det J| (m_off (p_0 + p_1 + p_2) + m_dd p_a),   1/2 p^T M_e p = 1/2 |det J| (m_off |sum p|^2 + m_dd sum |p_a|^2)
+// The tile energy is c_K e + 1/2 c_M p^T M_e p, so apply_finish's p^T q = 2 x sum stays right.  The diag kernel adds
+// M_e[a][a] = |det J| (m_off + m_dd) to xx and yy of every block.  MASS = false takes the DynMass argument and does not read it.
 #include <hip/hip_runtime.h>
 
 #include "hfem_cg_dev.h"
@@ -21,13 +32,27 @@
 namespace hfem {
 namespace {
 
-// ---------------------------------------------------------------- q = K p
+// One element's mass part: adds (M_e p)_a to the three rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double tri3_mass_rows(const double2 X0, const double2 X1, const double2 X2, const double2 P0,
+                                                 const double2 P1, const double2 P2, const DynMass &m, double2 (&gu)[3]) {
+    const double det = (X0.x - X2.x) * (X1.y - X2.y) - (X1.x - X2.x) * (X0.y - X2.y);
+    const double A = fabs(det);
+    const double wo = A * m.m_off, wd = A * m.m_dd;
+    const double sx = wo * (P0.x + P1.x + P2.x), sy = wo * (P0.y + P1.y + P2.y);
+    const double2 r0 = make_double2(__builtin_fma(wd, P0.x, sx), __builtin_fma(wd, P0.y, sy));
+    const double2 r1 = make_double2(__builtin_fma(wd, P1.x, sx), __builtin_fma(wd, P1.y, sy));
+    const double2 r2 = make_double2(__builtin_fma(wd, P2.x, sx), __builtin_fma(wd, P2.y, sy));
+    gu[0].x += r0.x; gu[0].y += r0.y; gu[1].x += r1.x; gu[1].y += r1.y; gu[2].x += r2.x; gu[2].y += r2.y;
+    return 0.5 * (P0.x * r0.x + P0.y * r0.y + P1.x * r1.x + P1.y * r1.y + P2.x * r2.x + P2.y * r2.y);
+}
+
+// ---------------------------------------------------------------- q = K p (MASS: q = A p)
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
-// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).
-template <int BLOCK, int NPT, int EPT, bool PHYS>
+// st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  MASS: k is the material constants times c_K.
+template <int BLOCK, int NPT, int EPT, bool PHYS, bool MASS>
 __global__ __launch_bounds__(BLOCK) void tri3_cg_apply_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k,
+    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k, DynMass dm,
     double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out, int cap_nodes, int cap_owned,
     int col_stride) {
     if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
@@ -83,16 +108,20 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_apply_kernel(
             const double2 Xn = nd_xy[ln], Pn = nd_p[ln], Xc = nd_xy[lc], Pc = nd_p[lc];
             double2 sn, sc;
             {
+                const double2 Xb = nd_xy[lb], Pb = nd_p[lb];
                 double2 gx[3], gu[3];
-                const double e = tri3_element<true, false, PHYS>(Xn, nd_xy[lb], Xc, Pn, nd_p[lb], Pc, k, gx, gu);
+                double e = tri3_element<true, false, PHYS>(Xn, Xb, Xc, Pn, Pb, Pc, k, gx, gu);
+                if constexpr (MASS) e += tri3_mass_rows(Xn, Xb, Xc, Pn, Pb, Pc, dm, gu);
                 if (a & kHomeBit) e_loc += e;
                 if (lb < n_owned) add_row(lb, gu[1]);
                 sn = gu[0]; sc = gu[2];
             }
             if (b & kHasBBit) {                             // B = (n, c, d)
                 const int ld = (int)(b & kLocalMask);
+                const double2 Xd = nd_xy[ld], Pd = nd_p[ld];
                 double2 gx[3], gu[3];
-                const double e = tri3_element<true, false, PHYS>(Xn, Xc, nd_xy[ld], Pn, Pc, nd_p[ld], k, gx, gu);
+                double e = tri3_element<true, false, PHYS>(Xn, Xc, Xd, Pn, Pc, Pd, k, gx, gu);
+                if constexpr (MASS) e += tri3_mass_rows(Xn, Xc, Xd, Pn, Pc, Pd, dm, gu);
                 if (b & kHomeBBit) e_loc += e;
                 if (ld < n_owned) add_row(ld, gu[2]);
                 sn.x += gu[0].x; sn.y += gu[0].y; sc.x += gu[1].x; sc.y += gu[1].y;
@@ -108,9 +137,10 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_apply_kernel(
 }
 
 // ---------------------------------------------------------------- block-Jacobi setup
-template <int BLOCK, int NPT, int EPT, bool PHYS>
+// MASS: the 2x2 diagonal blocks of A, the mass on xx and yy: M_e[a][a] = |det J| (m_off + m_dd).
+template <int BLOCK, int NPT, int EPT, bool PHYS, bool MASS>
 __global__ __launch_bounds__(BLOCK) void tri3_cg_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
-                                                             const double2 *__restrict__ x_fixed, Tri3Consts k,
+                                                             const double2 *__restrict__ x_fixed, Tri3Consts k, DynMass dm,
                                                              double *__restrict__ diag, double *__restrict__ dinv, int precond,
                                                              int cap_nodes, int cap_owned, int col_stride) {
     extern __shared__ double2 lds[];
@@ -131,18 +161,21 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_diag_kernel(PlanDev pd, const d
         if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; }
     }
     __syncthreads();
+    const double m_aa = dm.m_off + dm.m_dd;                 // read by MASS only
     // the three corner blocks of one element: column c of K_aa = the gradient at u_a = e_c, u_b = 0 (b != a)
     auto element = [&](int l0, int l1, int l2) {
         const int ls[3] = {l0, l1, l2};
         const double2 X[3] = {nd_xy[l0], nd_xy[l1], nd_xy[l2]};
+        double mm = 0.0;                                    // M_e[a][a], the same for the three corners (MASS only)
+        if constexpr (MASS) mm = fabs((X[0].x - X[2].x) * (X[1].y - X[2].y) - (X[1].x - X[2].x) * (X[0].y - X[2].y)) * m_aa;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             if (ls[a] >= n_owned) continue;
             double2 gu[3], hu[3];
             unit_columns<PHYS>(X, a, k, gu, hu);
-            unsafeAtomicAdd(&acc0[ls[a]], gu[a].x);
+            unsafeAtomicAdd(&acc0[ls[a]], with_mass<MASS>(gu[a].x, mm));
             unsafeAtomicAdd(&acc1[ls[a]], 0.5 * (gu[a].y + hu[a].x));
-            unsafeAtomicAdd(&acc2[ls[a]], hu[a].y);
+            unsafeAtomicAdd(&acc2[ls[a]], with_mass<MASS>(hu[a].y, mm));
         }
     };
     for (int j = 0; j < EPT; ++j) {
@@ -167,19 +200,22 @@ __global__ __launch_bounds__(BLOCK) void tri3_cg_diag_kernel(PlanDev pd, const d
 
 // ---------------------------------------------------------------- launchers
 // The tile shapes of a paired plan: 512 threads (2 nodes and 2 slot rows per thread), or 256 threads with 3 | 4 nodes and
-// 3 | 4 | 6 slot rows per thread (the pair kernel's matrix: a masked row or node costs a full pass of the slot loop).
+// 3 | 4 | 6 slot rows per thread (the pair kernel's matrix: a masked row or node costs a full pass of the slot loop).  Each
+// shape in both gradient conventions (A.phys) and without or with the mass (A.shifted).
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                           unsigned *ticket, double *st, double *host, double *pq_out) {
     const HostPlan &h = A.plan->host;
     const PlanDev pd = plan_dev(A.plan);
-#define HFEM_CG_APPLY(BLOCK, NPT, EPT, PH)                                                                                    \
-    hipLaunchKernelGGL((tri3_cg_apply_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd, A.n_tiles,  \
-                       A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, partials, ticket, st, host, pq_out, h.max_nodes,         \
-                       h.max_owned, h.col_stride)
+#define HFEM_CG_APPLY(BLOCK, NPT, EPT, PH, MASS)                                                                              \
+    hipLaunchKernelGGL((tri3_cg_apply_kernel<BLOCK, NPT, EPT, PH, MASS>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd,       \
+                       A.n_tiles, A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, A.dm, partials, ticket, st, host, pq_out,     \
+                       h.max_nodes, h.max_owned, h.col_stride)
 #define HFEM_CG_A(BLOCK, NPT, EPT)                                                                                            \
     do {                                                                                                                      \
-        if (A.phys) HFEM_CG_APPLY(BLOCK, NPT, EPT, true);                                                                     \
-        else HFEM_CG_APPLY(BLOCK, NPT, EPT, false);                                                                           \
+        if (A.phys && A.shifted) HFEM_CG_APPLY(BLOCK, NPT, EPT, true, true);                                                  \
+        else if (A.phys) HFEM_CG_APPLY(BLOCK, NPT, EPT, true, false);                                                         \
+        else if (A.shifted) HFEM_CG_APPLY(BLOCK, NPT, EPT, false, true);                                                      \
+        else HFEM_CG_APPLY(BLOCK, NPT, EPT, false, false);                                                                    \
     } while (0)
     if (A.block == 512) HFEM_CG_A(512, 2, 2);
     else if (h.max_nodes <= 3 * 256) {
@@ -198,16 +234,19 @@ void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0,
 void launch_tri3_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
     const HostPlan &h = A.plan->host;
     const PlanDev pd = plan_dev(A.plan);
-#define HFEM_CG_DIAG(BLOCK, NPT, EPT, PH)                                                                                     \
-    hipLaunchKernelGGL((tri3_cg_diag_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd, A.x_free,    \
-                       A.x_fixed, A.k, diag, dinv, precond, h.max_nodes, h.max_owned, h.col_stride)
-    if (A.block == 512) {
-        if (A.phys) HFEM_CG_DIAG(512, 2, 2, true);
-        else HFEM_CG_DIAG(512, 2, 2, false);
-    } else {
-        if (A.phys) HFEM_CG_DIAG(256, 4, 6, true);
-        else HFEM_CG_DIAG(256, 4, 6, false);
-    }
+#define HFEM_CG_DIAG(BLOCK, NPT, EPT, PH, MASS)                                                                               \
+    hipLaunchKernelGGL((tri3_cg_diag_kernel<BLOCK, NPT, EPT, PH, MASS>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd,        \
+                       A.x_free, A.x_fixed, A.k, A.dm, diag, dinv, precond, h.max_nodes, h.max_owned, h.col_stride)
+#define HFEM_CG_D(BLOCK, NPT, EPT)                                                                                            \
+    do {                                                                                                                      \
+        if (A.phys && A.shifted) HFEM_CG_DIAG(BLOCK, NPT, EPT, true, true);                                                   \
+        else if (A.phys) HFEM_CG_DIAG(BLOCK, NPT, EPT, true, false);                                                          \
+        else if (A.shifted) HFEM_CG_DIAG(BLOCK, NPT, EPT, false, true);                                                       \
+        else HFEM_CG_DIAG(BLOCK, NPT, EPT, false, false);                                                                     \
+    } while (0)
+    if (A.block == 512) HFEM_CG_D(512, 2, 2);
+    else HFEM_CG_D(256, 4, 6);
+#undef HFEM_CG_D
 #undef HFEM_CG_DIAG
 }
 

@@ -10,8 +10,8 @@ solver applies at the model's CURRENT coordinates (``hfem_cg_apply``), ``M`` the
     A a+ = load(t + dt) b0 - K w - alpha_R M v~,   A = c_M M + c_K K,  c_M = 1 + gamma dt alpha_R,  c_K = beta dt^2 + gamma dt beta_R
     u+ = u~ + beta dt^2 a+                     v+ = v~ + gamma dt a+
 
-The solve is the PCG driver of the frozen-mesh solve (``csrc/cg.hip``) on its shifted element kind (``csrc/tri3_dyn_cg.hip``,
-``csrc/quad4_dyn_cg.hip``: the mass term is formed inside the slot loop of the ``K`` apply, with no second pass of gathers),
+The solve is the PCG driver of the frozen-mesh solve (``csrc/cg.hip``) on the ``MASS`` instances of its plain element kernels
+(``csrc/tri3_cg.hip``, ``csrc/quad4_cg.hip``: the mass term is formed inside the slot loop of the ``K`` apply, with no second pass of gathers),
 warm-started from the previous ``a``, preconditioned by a smoothed-aggregation hierarchy built on ``A`` itself
 (``hfem_amg_setup_shifted``), the 2x2 diagonal blocks of ``A``, or nothing; the three vector passes of a step are
 ``csrc/dynamics.hip``.  The initial acceleration solves ``M a0 = load(0) b0 - K u0 - C v0`` (``c_K = 0``).  With a lumped mass

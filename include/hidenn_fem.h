@@ -1001,11 +1001,11 @@ int hfem_block_residual(int device, const double *KX, const double *MX, const do
 int hfem_block_jacobi_apply(int device, const double *diag, const double *R, int32_t m, int64_t len, double *W, void *stream);
 
 /* ------------------------------------------------------------------ implicit transient dynamics: Newmark on A = c_M M + c_K K
- * (csrc/tri3_dyn_cg.hip, csrc/quad4_dyn_cg.hip, csrc/dynamics.hip; hidenn_fem_amd/dynamics.py).  No reference
- * counterpart.  M u'' + C u' + K u = load(t) b0 over the free u rows, C = alpha_R M + beta_R K, Newmark (beta, gamma) in the
+ * (the MASS instances of the kernels of csrc/tri3_cg.hip, csrc/quad4_cg.hip and csrc/tri3_amg.hip; csrc/dynamics.hip;
+ * hidenn_fem_amd/dynamics.py).  No reference counterpart.  M u'' + C u' + K u = load(t) b0 over the free u rows, C = alpha_R M + beta_R K, Newmark (beta, gamma) in the
  * a-form: per step one solve A a+ = load b0 - K w - alpha_R M v~ with A = c_M M + c_K K, c_M = 1 + gamma dt alpha_R,
  * c_K = beta dt^2 + gamma dt beta_R.  K is hfem_cg_apply's operator, M hfem_mass_apply's (always |det J|).
- *   cg_setup_shifted   hfem_cg_setup for the shifted element kind of the PCG driver: binds the coordinate rows and the material
+ *   cg_setup_shifted   hfem_cg_setup for the shifted operator (the MASS instances of the plain element kernels): binds the coordinate rows and the material
  *                as hfem_cg_setup does, and c_k >= 0, c_m >= 0 (c_m INCLUDES the density; both finite, not both zero), lumped != 0:
  *                the row-sum mass.  diag_out [n_u][3] (may be NULL): the 2x2 diagonal blocks of A (the mass on xx and yy).  After
  *                it hfem_cg_start / iterate / status / apply / start_amg / iterate_amg work on A; a later hfem_cg_setup returns

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Implicit dynamics at T1M / Q1M (dev tool; gates nothing): the 10^6-element TRI3 (1001 x 501 nodes) and, with `--quad`, QUAD4
 (1415 x 708 nodes) benchmark meshes, left edge clamped, fp64, physical convention, rho = 2, consistent mass
-(hidenn_fem_amd/dynamics.py, csrc/tri3_dyn_cg.hip, csrc/quad4_dyn_cg.hip, csrc/dynamics.hip).
+(hidenn_fem_amd/dynamics.py, the MASS instances of csrc/tri3_cg.hip and csrc/quad4_cg.hip, csrc/dynamics.hip).
 
 One JSON object -> `profiles/dynamics/dynamics_timing_{T1M,Q1M}.json`:
   * `apply`: the shifted apply q = (c_K K + c_M M) p against the plain apply q = K p on the same plan, and their ratio -- the

@@ -39,18 +39,28 @@ def test_dynamics_symbols_are_exported_bound_and_match_the_header():
         assert getattr(L.lib(), n).argtypes == L.PROTOTYPES[n][1]
         assert len(L.PROTOTYPES[n][1]) == counts[n], n
     from hidenn_fem_amd.csrc import build
-    for src in ("tri3_dyn_cg.hip", "quad4_dyn_cg.hip", "dynamics.hip"):
-        assert src in build.SOURCES
+    assert "dynamics.hip" in build.SOURCES
+    assert not [s for s in build.SOURCES if s.endswith("_dyn_cg.hip")]
     usage = build.resource_usage()
-    for kernel in ("tri3_dyn_cg_apply_kernel", "quad4_dyn_cg_apply_kernel", "tri3_dyn_cg_diag_kernel",
-                   "quad4_dyn_cg_diag_kernel", "amg_assemble_shifted_kernel", "newmark_predict_kernel", "newmark_rhs_kernel",
-                   "newmark_correct_kernel"):
+    # The shifted operator is the MASS instance of the plain kernels: the last template argument (Lb0E | Lb1E in the mangled
+    # name).  One instance matrix, compiled without and with the mass: TRI3 apply (512,2,2) and (256, 3|4, 3|4|6) x PHYS, TRI3
+    # diag (512,2,2), (256,4,6) x PHYS; QUAD4 apply (256,3,3), (256,4,4) x PHYS, QUAD4 diag (256,4,4) x PHYS; assembly 3|4 x PHYS.
+    for kernel, count in (("tri3_cg_apply_kernel", 14), ("tri3_cg_diag_kernel", 4), ("quad4_cg_apply_kernel", 4),
+                          ("quad4_cg_diag_kernel", 2), ("amg_assemble_kernel", 4)):
+        by_mass = {False: {}, True: {}}
+        for name, v in usage.items():
+            m = re.search(r"\d+" + kernel + r"I((?:L[ib]\d+E)+)E", name)
+            if m:
+                last = re.findall(r"L([ib])(\d+)E", m.group(1))[-1]
+                assert last[0] == "b", f"{name}: the last template argument is not the bool MASS"
+                by_mass[last[1] == "1"][name] = v
+        for mass, inst in by_mass.items():
+            assert len(inst) == count, (kernel, mass, sorted(inst))
+            assert all(v["scratch"] == 0 for v in inst.values()), (kernel, mass, inst)
+    for kernel in ("newmark_predict_kernel", "newmark_rhs_kernel", "newmark_correct_kernel"):
         inst = {k: v for k, v in usage.items() if kernel in k}
         assert inst, kernel
         assert all(v["scratch"] == 0 for v in inst.values()), (kernel, inst)
-    # the instance matrix of the plain launchers: TRI3 (512,2,2) and (256, 3|4, 3|4|6) x PHYS; QUAD4 (256,3,3), (256,4,4) x PHYS
-    assert sum("tri3_dyn_cg_apply_kernel" in k for k in usage) == sum("tri3_cg_apply_kernel" in k for k in usage) == 14
-    assert sum("quad4_dyn_cg_apply_kernel" in k for k in usage) == sum("quad4_cg_apply_kernel" in k for k in usage) == 4
 
 
 def test_dynamics_argument_errors_are_negative_codes_with_messages():

@@ -1,8 +1,9 @@
 """The kernels of implicit dynamics one by one: the shifted apply and its p^T A p, the 2x2 diagonal blocks and the
 assembled A of ``c_K K + c_M M`` against the reference matrix -- K from ``assemble_stiffness``, M element by element from
 tests/modal_reference.py with rho = 2, as tests/test_gpu_modal.py::dense_pencil, both held SPARSE (scipy CSR, the same entries:
-the larger shapes have 10^4 dofs) -- on shapes that reach every instance of the plain launchers' dispatch (restated here and
-asserted: all seven TRI3 instances, both QUAD4 ones); the three vector kernels against their formulas in ``longdouble``; the
+the larger shapes have 10^4 dofs).  The shifted operator is the ``MASS`` instance of the plain kernels (``tri3_cg.hip``,
+``quad4_cg.hip``, ``amg_assemble_kernel``), picked by the plain launchers; the shapes reach every tile shape of their dispatch
+(restated here and asserted: all seven TRI3 shapes, both QUAD4 ones) with the mass, in both conventions; the three vector kernels against their formulas in ``longdouble``; the
 V-cycle of the hierarchy built on A.
 
 Tolerances: apply, blocks and assembled A 1e-12 x max; ``p^T A p`` 1e-12 |p^T A p| (both as tests/test_gpu_solve.py holds the
@@ -46,7 +47,7 @@ def _dev():
 
 
 def tri3_cg_apply_branch(stats):
-    """Which instance launch_tri3_cg_apply / launch_tri3_dyn_cg_apply pick."""
+    """Which instance launch_tri3_cg_apply picks (without and with the mass)."""
     if stats["threads_per_tile"] == 512:
         return "<512,2,2>"
     npt = 3 if stats["max_tile_nodes"] <= 3 * 256 else 4
