@@ -150,7 +150,7 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
 
 
 def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8, E=10e9, nu=0.3, newton=False,
-                    precond="block_jacobi", quad=False, r_adapt=False, outer=10, error_estimate=False):
+                    precond="block_jacobi", quad=False, r_adapt=False, outer=10, error_estimate=False, dynamics=0, dt=None):
     """The plate at FINITE strain (``--neo-hookean``): compressible Neo-Hookean material (``NeoHookeanLoss2D``), left edge
     clamped, the right edge pulled DOWN by the dead traction ``(0, -E/500)`` -- a tip deflection of about a third
     of the height.  The mesh is frozen; the load is ramped in ``load_steps`` increments and each increment is minimised over
@@ -175,7 +175,13 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
     ``error_estimate=True`` (``--error-estimate``): after every converged load increment one line with the relative ZZ error
     indicator eta_rel, min J and the largest nodal von Mises stress of the recovered CAUCHY stress
     (``hidenn_fem_amd.post.HyperStressRecovery`` -- an indicator, not an estimate, away from small strain: DESIGN 24); with
-    ``r_adapt`` also on the frozen mesh and on the r-adapted one, all from one reused object."""
+    ``r_adapt`` also on the frozen mesh and on the r-adapted one, all from one reused object.
+
+    ``dynamics=N`` (``--dynamics N``): no ramp; a step load on the plate at rest -- a tenth of the ramp's full traction switched
+    on at t = 0 -- followed for N Newmark steps at finite strain (``hidenn_fem_amd.dynamics.HyperNewmarkSolver``: average
+    acceleration, consistent mass, unit density, one Newton-Krylov solve per step with preconditioner ``precond``), printing t,
+    the tip displacement, the Newton and CG iterations, min J and the total energy of every step; ``dt`` defaults to 1/20 of the
+    period of the lowest mode of the linearised plate.  Returns ``(model, [HyperStepInfo])``."""
     newton = newton or r_adapt
     from hidenn_fem_amd.loss import NeoHookeanLoss2D, Quad4NeoHookeanLoss2D
     from hidenn_fem_amd.optim import FusedLBFGS
@@ -199,6 +205,12 @@ def run_neo_hookean(nx=200, ny=100, steps=100, dtype=torch.float64, load_steps=8
 
     def traction(scale):
         return lambda x: torch.stack([torch.zeros_like(x[:, 0]), torch.full_like(x[:, 0], -scale * tau)], dim=1)
+
+    if dynamics:
+        if precond == "amg_tangent":
+            raise NotImplementedError("example 4: --neo-hookean --dynamics takes --precond block_jacobi or amg")
+        lin = EnergyLoss2D(E=E, nu=nu, length=length, height=height, device=dev, dtype=dtype, grad_convention="physical")
+        return _hyper_dynamics(model, loss_fn, lin, traction(0.1), dynamics, dt, precond)
 
     def minimise(scale):
         opt = FusedLBFGS([model.u_free])
@@ -357,6 +369,40 @@ def _dynamics(model, loss_fn, n_steps, dt, precond):
     return model, infos
 
 
+def _hyper_dynamics(model, loss_fn, lin_loss, t_force, n_steps, dt, precond):
+    import time
+    from hidenn_fem_amd.dynamics import HyperNewmarkSolver
+    from hidenn_fem_amd.modal import vibration_modes
+    if dt is None:
+        lam = vibration_modes(model, lin_loss, n_modes=1, precond=precond, max_iter=200 if precond == "amg" else 5000).eigenvalues[0].item()
+        dt = 2.0 * 3.141592653589793 / lam ** 0.5 / 20.0
+        print(f"lowest mode of the linearised plate: period {20.0 * dt:.6e}; dt = period / 20 = {dt:.6e}")
+    with torch.no_grad():
+        model.u_free.zero_()
+    solver = HyperNewmarkSolver(model, loss_fn, dt, precond=precond, t_force=t_force)
+    solver.set_state()
+    x = model.coords.detach()[model._idx_ufree.to(model.coords.device)]                 # node of every free u row (storage order)
+    tip = int(torch.argmax(x[:, 0] - 1e-3 * (x[:, 1] - 0.5 * x[:, 1].max()).abs()))     # right edge, nearest mid-height
+    print(f"step load from rest at finite strain (consistent mass, density 1, beta 1/4, gamma 1/2, {precond}); tip = free row "
+          f"{tip} at ({x[tip, 0].item():.3f}, {x[tip, 1].item():.3f})")
+    infos = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n_steps):
+        info = solver.step(1)[0]
+        infos.append(info)
+        if info.reason in ("inverted", "line_search"):
+            print(f"t {info.t:.6e}: the step stopped with {info.reason!r}; the state is the one before it")
+            break
+        u = solver.u[tip]
+        print(f"t {info.t:.6e}: tip u ({u[0].item():+.6e}, {u[1].item():+.6e}) Newton {info.newton_iterations:2d} CG "
+              f"{info.iterations:5d} ({info.reason}) min J {info.min_J:.4f} energy {solver.energy()['total']:+.9e}")
+    torch.cuda.synchronize()
+    print(f"{len(infos)} steps, {sum(i.newton_iterations for i in infos)} Newton and {sum(i.iterations for i in infos)} CG "
+          f"iterations, {time.perf_counter() - t0:.3f} s")
+    return model, infos
+
+
 def _print_error(model, loss_fn, when, recovery=None):
     """One line with the relative ZZ error estimate; returns the ``StressRecovery`` (reusable: the connectivity never changes)."""
     from hidenn_fem_amd.post import StressRecovery
@@ -421,7 +467,8 @@ if __name__ == "__main__":
                          "--precond block_jacobi|amg) and stop")
     ap.add_argument("--dynamics", type=int, default=0, metavar="N",
                     help="a step load on the plate at rest, N Newmark steps (t, tip displacement, CG iterations and total "
-                         "energy per step; with --dt, --quad and --precond block_jacobi|amg) and stop")
+                         "energy per step; with --dt, --quad and --precond block_jacobi|amg) and stop; with --neo-hookean: at "
+                         "finite strain (a Newton-Krylov solve per step; also Newton iterations and min J)")
     ap.add_argument("--dt", type=float, default=None, help="time step of --dynamics (default: 1/20 of the lowest mode's period)")
     ap.add_argument("--newton", action="store_true",
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
@@ -431,6 +478,7 @@ if __name__ == "__main__":
         ap.error("--precond amg_tangent needs --neo-hookean with --newton or --r-adapt (with or without --quad)")
     if a.neo_hookean:
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad,
+                        dynamics=a.dynamics, dt=a.dt,
                         r_adapt=a.r_adapt, outer=a.outer or 10, error_estimate=a.error_estimate)
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,

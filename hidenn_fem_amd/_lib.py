@@ -202,6 +202,9 @@ PROTOTYPES = {
     "hfem_newmark_predict": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "hfem_newmark_rhs": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp]),
     "hfem_newmark_correct": (C.c_int, [C.c_int, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "hfem_cg_setup_hyper_shifted": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp]),
+    "hfem_newmark_trial": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "hfem_newmark_residual": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

@@ -5,7 +5,8 @@
 // on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
 // cg_apply and cg_diag.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
 // hidenn_fem_amd/dynamics.py) is no element kind of its own: it is the MASS instance of the kernels of tri3_cg.hip and
-// quad4_cg.hip, picked by their launchers.  The residual r = -dE/du comes from the graded energy kernel, called by the host
+// quad4_cg.hip, picked by their launchers; likewise c_K K_T + c_M M of a finite-strain step (after
+// hfem_cg_setup_hyper_shifted) is the MASS instance of the tangent kernels.  The residual r = -dE/du comes from the graded energy kernel, called by the host
 // once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
 //                   order, forms beta, and applies the stopping test (START: r = -g0, z = D^-1 r, |f|).
@@ -180,7 +181,9 @@ struct hfem_cg {
     // bound by hfem_cg_setup
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     hfem::Tri3Consts k{};
-    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; the MASS instances of tri3_cg.hip / quad4_cg.hip)
+    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; the MASS instances of tri3_cg.hip / quad4_cg.hip), or
+    // by hfem_cg_setup_hyper_shifted: A = c_K K_T + c_M M (hk's lambda and mu carry c_K; the MASS instances of
+    // tri3_hyper_cg.hip / quad4_hyper_cg.hip)
     bool shifted = false;
     hfem::DynMass dm{};
     // bound by hfem_cg_setup_hyper
@@ -418,31 +421,64 @@ extern "C" int hfem_cg_setup_shifted(hfem_cg *c, const double *x_free, const dou
     return 0;
 }
 
-extern "C" int hfem_cg_setup_hyper(hfem_cg *c, const double *x_free, const double *x_fixed, const double *u_lin_free,
-                                   const double *u_fixed, const double lame[2], double W, int32_t precond, double *diag_out,
-                                   double *info_out, void *stream) {
-    HFEM_ARG_CHECK(c && x_free && lame && (u_lin_free || c->n_u == 0), "null pointer");
-    HFEM_ARG_CHECK(c->hyper, "this solver was created by hfem_cg_create: hfem_cg_setup binds it");
-    HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+// The bindings and checks of the two hyper setups.  shifted: A = c_K K_T + c_M M -- lambda and mu times c_K (K_T is linear in
+// them, tri3_hyper_cg.hip) and the mass coefficients; otherwise plain K_T.  Nothing of the handle changes before every check
+// has passed.
+static int cg_setup_hyper(hfem_cg *c, const double *x_free, const double *x_fixed, const double *u_lin_free, const double *u_fixed,
+                          const double lame[2], double W, bool shifted, double c_k, double c_m, int32_t lumped, int32_t precond,
+                          double *diag_out, double *info_out, void *stream, const char *who) {
+    // the messages carry the public entry point's name, not this function's
+#define HFEM_WHO_CHECK(cond, msg)                                                                                             \
+    do {                                                                                                                      \
+        if (!(cond)) {                                                                                                        \
+            hfem::set_error(std::string(who) + ": " + (msg));                                                                 \
+            return -1;                                                                                                        \
+        }                                                                                                                     \
+    } while (0)
+    HFEM_WHO_CHECK(c && x_free && lame && (u_lin_free || c->n_u == 0), "null pointer");
+    HFEM_WHO_CHECK(c->hyper, shifted ? "this solver was created by hfem_cg_create: hfem_cg_setup_shifted binds its shifted operator"
+                                     : "this solver was created by hfem_cg_create: hfem_cg_setup binds it");
+    HFEM_WHO_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
     bool fixed_x = false, fixed_u = false;
     const hfem::HostPlan &h = c->plan->host;
     for (size_t i = 0; i + 1 < h.node_src.size(); i += 2) {
         fixed_x = fixed_x || h.node_src[i] < 0;
         fixed_u = fixed_u || h.node_src[i + 1] < 0;
     }
-    HFEM_ARG_CHECK(x_fixed || !fixed_x, "the plan reads fixed coordinate rows: x_fixed must be given");
-    HFEM_ARG_CHECK(u_fixed || !fixed_u, "the plan reads Dirichlet rows: u_fixed must be given");
-    HFEM_ARG_CHECK(u_lin_free || !h.tiles.size(), "u_lin_free must be given");
+    HFEM_WHO_CHECK(x_fixed || !fixed_x, "the plan reads fixed coordinate rows: x_fixed must be given");
+    HFEM_WHO_CHECK(u_fixed || !fixed_u, "the plan reads Dirichlet rows: u_fixed must be given");
+    HFEM_WHO_CHECK(u_lin_free || !h.tiles.size(), "u_lin_free must be given");
     if (int rc = hfem::use_device(c->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->u_lin = (const double2 *)u_lin_free; c->u_fixed = (const double2 *)u_fixed;
     c->hk = hfem::HyperConsts{};
-    c->hk.lambda = lame[0]; c->hk.mu = lame[1]; c->hk.W = c->quad ? 1.0 : W;   // QUAD4: the 2x2 rule's weights are 1, W is not read
+    c->hk.lambda = c_k * lame[0]; c->hk.mu = c_k * lame[1];
+    c->hk.W = c->quad ? 1.0 : W;                                      // QUAD4: the 2x2 rule's weights are 1, W is not read
+    c->shifted = shifted; c->dm = shifted ? hfem::dyn_mass(c->quad, c_m, lumped != 0) : hfem::DynMass{};
     cg_diag(c, diag_out, precond, info_out, s);
-    if (int rc = hfem::launch_status("hfem_cg_setup_hyper")) return rc;
+    if (int rc = hfem::launch_status(who)) return rc;
     c->ready = true;
     return 0;
+#undef HFEM_WHO_CHECK
+}
+
+extern "C" int hfem_cg_setup_hyper(hfem_cg *c, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                                   const double *u_fixed, const double lame[2], double W, int32_t precond, double *diag_out,
+                                   double *info_out, void *stream) {
+    return cg_setup_hyper(c, x_free, x_fixed, u_lin_free, u_fixed, lame, W, false, 1.0, 0.0, 0, precond, diag_out, info_out, stream,
+                          "hfem_cg_setup_hyper");
+}
+
+// hfem_cg_setup_hyper for A(u) = c_K K_T(u) + c_M M (c_K = 0 allowed: the pure mass operator of the initial acceleration and
+// of an explicit step).  A later hfem_cg_setup_hyper returns the handle to plain K_T.
+extern "C" int hfem_cg_setup_hyper_shifted(hfem_cg *c, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                                           const double *u_fixed, const double lame[2], double W, double c_k, double c_m,
+                                           int32_t lumped, int32_t precond, double *diag_out, double *info_out, void *stream) {
+    HFEM_ARG_CHECK(std::isfinite(c_k) && std::isfinite(c_m) && c_k >= 0.0 && c_m >= 0.0 && (c_k > 0.0 || c_m > 0.0),
+                   "c_k and c_m must be finite, >= 0 and not both zero");
+    return cg_setup_hyper(c, x_free, x_fixed, u_lin_free, u_fixed, lame, W, true, c_k, c_m, lumped, precond, diag_out, info_out,
+                          stream, "hfem_cg_setup_hyper_shifted");
 }
 
 extern "C" int hfem_cg_start(hfem_cg *c, const double *g0, const double *g_zero, double rtol, double atol, int64_t max_iter,

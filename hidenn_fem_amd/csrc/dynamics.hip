@@ -6,6 +6,11 @@
 //   newmark_rhs_kernel       rhs = load b0 - K w - alpha_R M v~;   g_zero = rhs,   g0 = A a - rhs  (what hfem_cg_start takes:
 //                            r = -g0 is the residual of the warm start a, |g_zero| the norm of the stopping test)
 //   newmark_correct_kernel   u = u~ + beta dt^2 a+,   v = v~ + gamma dt a+
+// and, for the Newton loop of a finite-strain step (HyperNewmarkSolver, DESIGN 27: A = c_M M + c_K K_T(u), the MASS instances
+// of tri3_hyper_cg.hip, quad4_hyper_cg.hip), two more:
+//   newmark_trial_kernel     a_t = a + s d,   u_t = u~ + c_K a_t,   (M a)_t = M a + s M d   (M is linear: M d is formed once per
+//                            Newton iteration, a line-search trial costs this pass and one energy launch)
+//   newmark_residual_kernel  R = c_M (M a) + alpha_R (M v~) + f_int - load b_ext,   and -R
 // One row (16 bytes) per access, grid-stride under a fixed grid cap, launch-only (capturable).  Every output entry is one or
 // two FMAs of its own row: bit-reproducible, no reduction, no atomics.
 #include <hip/hip_runtime.h>
@@ -63,6 +68,41 @@ __global__ __launch_bounds__(kDynBlock) void newmark_correct_kernel(int64_t n, c
         const double2 p = ut[i], q = vt[i], ai = a[i];
         u[i] = make_double2(__builtin_fma(c_u, ai.x, p.x), __builtin_fma(c_u, ai.y, p.y));
         v[i] = make_double2(__builtin_fma(c_v, ai.x, q.x), __builtin_fma(c_v, ai.y, q.y));
+    }
+}
+
+// every output may be its input of the same role (a_t = a, ma_t = ma): each row is read before it is written
+__global__ __launch_bounds__(kDynBlock) void newmark_trial_kernel(int64_t n, const double2 *a, const double2 *__restrict__ d,
+                                                                  const double2 *__restrict__ ut, const double2 *ma,
+                                                                  const double2 *__restrict__ md, double s, double c_k,
+                                                                  double2 *a_t, double2 *__restrict__ u_t, double2 *ma_t) {
+    for (int64_t i = (int64_t)blockIdx.x * kDynBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDynBlock) {
+        const double2 ai = a[i], di = d[i], ui = ut[i], mi = ma[i], ni = md[i];
+        const double2 at = make_double2(__builtin_fma(s, di.x, ai.x), __builtin_fma(s, di.y, ai.y));
+        a_t[i] = at;
+        u_t[i] = make_double2(__builtin_fma(c_k, at.x, ui.x), __builtin_fma(c_k, at.y, ui.y));
+        ma_t[i] = make_double2(__builtin_fma(s, ni.x, mi.x), __builtin_fma(s, ni.y, mi.y));
+    }
+}
+
+// mv == NULL: no mass-proportional damping (alpha_R = 0); neg_r == NULL: only R
+__global__ __launch_bounds__(kDynBlock) void newmark_residual_kernel(int64_t n, const double2 *__restrict__ ma,
+                                                                     const double2 *__restrict__ mv,
+                                                                     const double2 *__restrict__ fint,
+                                                                     const double2 *__restrict__ b, double c_m, double alpha_r,
+                                                                     double load, double2 *__restrict__ r,
+                                                                     double2 *__restrict__ neg_r) {
+    for (int64_t i = (int64_t)blockIdx.x * kDynBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kDynBlock) {
+        const double2 m = ma[i], f = fint[i], bi = b[i];
+        double2 v = make_double2(__builtin_fma(c_m, m.x, __builtin_fma(-load, bi.x, f.x)),
+                                 __builtin_fma(c_m, m.y, __builtin_fma(-load, bi.y, f.y)));
+        if (mv) {
+            const double2 w = mv[i];
+            v.x = __builtin_fma(alpha_r, w.x, v.x);
+            v.y = __builtin_fma(alpha_r, w.y, v.y);
+        }
+        r[i] = v;
+        if (neg_r) neg_r[i] = make_double2(-v.x, -v.y);
     }
 }
 
@@ -134,5 +174,43 @@ extern "C" int hfem_newmark_correct(int device, const double *u_pred, const doub
     const int64_t n = len / 2;
     hipLaunchKernelGGL(newmark_correct_kernel, dyn_grid(n), dim3(kDynBlock), 0, (hipStream_t)stream, n, (const double2 *)u_pred,
                        (const double2 *)v_pred, (const double2 *)a, beta * dt * dt, gamma * dt, (double2 *)u, (double2 *)v);
+    return launch_status(who);
+}
+
+extern "C" int hfem_newmark_trial(int device, const double *a, const double *d, const double *u_pred, const double *ma,
+                                  const double *md, int64_t len, double s, double c_k, double *a_t, double *u_t, double *ma_t,
+                                  void *stream) {
+    const char *who = "hfem_newmark_trial";
+    if (int rc = dyn_check(who, device, len, a && d && u_pred && ma && md && a_t && u_t && ma_t, std::isfinite(s) && std::isfinite(c_k)))
+        return rc < 0 ? rc : 0;
+    if (a_t == u_t || a_t == ma_t || u_t == ma_t || a_t == d || a_t == u_pred || a_t == ma || a_t == md || u_t == a || u_t == d ||
+        u_t == u_pred || u_t == ma || u_t == md || ma_t == a || ma_t == d || ma_t == u_pred || ma_t == md) {
+        set_error(std::string(who) + ": a_t may alias a and ma_t may alias ma, nothing else");
+        return -1;
+    }
+    if (int rc = use_device(device)) return rc;
+    const int64_t n = len / 2;
+    hipLaunchKernelGGL(newmark_trial_kernel, dyn_grid(n), dim3(kDynBlock), 0, (hipStream_t)stream, n, (const double2 *)a,
+                       (const double2 *)d, (const double2 *)u_pred, (const double2 *)ma, (const double2 *)md, s, c_k, (double2 *)a_t,
+                       (double2 *)u_t, (double2 *)ma_t);
+    return launch_status(who);
+}
+
+extern "C" int hfem_newmark_residual(int device, const double *ma, const double *mv, const double *f_int, const double *b_ext,
+                                     int64_t len, double c_m, double alpha_r, double load, double *r, double *neg_r, void *stream) {
+    const char *who = "hfem_newmark_residual";
+    if (int rc = dyn_check(who, device, len, ma && f_int && b_ext && r,
+                           std::isfinite(c_m) && std::isfinite(alpha_r) && std::isfinite(load)))
+        return rc < 0 ? rc : 0;
+    if (r == neg_r || r == ma || r == mv || r == f_int || r == b_ext || (neg_r && (neg_r == ma || neg_r == mv || neg_r == f_int ||
+                                                                                  neg_r == b_ext))) {
+        set_error(std::string(who) + ": the two outputs must differ from each other and from the inputs");
+        return -1;
+    }
+    if (int rc = use_device(device)) return rc;
+    const int64_t n = len / 2;
+    hipLaunchKernelGGL(newmark_residual_kernel, dyn_grid(n), dim3(kDynBlock), 0, (hipStream_t)stream, n, (const double2 *)ma,
+                       (const double2 *)mv, (const double2 *)f_int, (const double2 *)b_ext, c_m, alpha_r, load, (double2 *)r,
+                       (double2 *)neg_r);
     return launch_status(who);
 }

@@ -4,10 +4,11 @@
 // the element: the iteration state, one gathered p row, the write-out of q and p, the p^T q epilogue with alpha and the breakdown halt, and the Jacobi
 // block store.  For the diag kernels and the AMG fine-level assembly (tri3_amg.hip): the unit-displacement columns of one
 // element, 3 or 4 corners, and the x row code.  For the shifted operator of implicit dynamics (the MASS instances of the
-// kernels of tri3_cg.hip and quad4_cg.hip and of amg_assemble_kernel, tri3_amg.hip): the mass coefficients, the QUAD4 Gauss
-// point determinants and shape values, and one element's mass row.  Last, the launchers of the element kernels, which the PCG
+// kernels of tri3_cg.hip, quad4_cg.hip, tri3_hyper_cg.hip and quad4_hyper_cg.hip and of amg_assemble_kernel, tri3_amg.hip): the
+// mass coefficients, the QUAD4 Gauss point determinants and shape values, one element's mass row, and one element's mass
+// part of an apply.  Last, the launchers of the element kernels, which the PCG
 // driver (cg.hip) calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the
-// index loads, the staging of coordinates and p, the slot loop, and the mass part of the slot loop.
+// index loads, the staging of coordinates and p, and the slot loop.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -257,6 +258,55 @@ __device__ __forceinline__ void dyn_mass_row(const double2 (&X)[4], int a, const
     }
 }
 
+// One element's mass part in the slot loop of an apply kernel (tri3_cg.hip, quad4_cg.hip and the Neo-Hookean tangent's
+// tri3_hyper_cg.hip, quad4_hyper_cg.hip): from the corner coordinates and the corner values of p the slot already holds.
+// TRI3: adds (M_e p)_a to the three rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double tri3_mass_rows(const double2 X0, const double2 X1, const double2 X2, const double2 P0,
+                                                 const double2 P1, const double2 P2, const DynMass &m, double2 (&gu)[3]) {
+    const double det = (X0.x - X2.x) * (X1.y - X2.y) - (X1.x - X2.x) * (X0.y - X2.y);
+    const double A = fabs(det);
+    const double wo = A * m.m_off, wd = A * m.m_dd;
+    const double sx = wo * (P0.x + P1.x + P2.x), sy = wo * (P0.y + P1.y + P2.y);
+    const double2 r0 = make_double2(__builtin_fma(wd, P0.x, sx), __builtin_fma(wd, P0.y, sy));
+    const double2 r1 = make_double2(__builtin_fma(wd, P1.x, sx), __builtin_fma(wd, P1.y, sy));
+    const double2 r2 = make_double2(__builtin_fma(wd, P2.x, sx), __builtin_fma(wd, P2.y, sy));
+    gu[0].x += r0.x; gu[0].y += r0.y; gu[1].x += r1.x; gu[1].y += r1.y; gu[2].x += r2.x; gu[2].y += r2.y;
+    return 0.5 * (P0.x * r0.x + P0.y * r0.y + P1.x * r1.x + P1.y * r1.y + P2.x * r2.x + P2.y * r2.y);
+}
+
+// QUAD4: adds (M_e p)_a to the four rows, returns 1/2 p^T M_e p.
+__device__ __forceinline__ double quad4_mass_rows(const double2 (&Xn)[4], const double2 (&Pn)[4], const DynMass &m,
+                                                  double2 (&gu)[4]) {
+    double ad[4];
+    quad4_abs_dets(Xn, ad);
+    double2 r[4];
+    double nl[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { r[a] = make_double2(0.0, 0.0); nl[a] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double hx = 0.0, hy = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { hx += quad4_n(b, q) * Pn[b].x; hy += quad4_n(b, q) * Pn[b].y; }
+        const double w = ad[q] * m.m_off;
+        hx *= w; hy *= w;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            r[a].x += quad4_n(a, q) * hx; r[a].y += quad4_n(a, q) * hy;
+            nl[a] += quad4_n(a, q) * ad[q];
+        }
+    }
+    double e = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double wl = nl[a] * m.m_dd;
+        r[a].x = __builtin_fma(wl, Pn[a].x, r[a].x); r[a].y = __builtin_fma(wl, Pn[a].y, r[a].y);
+        gu[a].x += r[a].x; gu[a].y += r[a].y;
+        e += Pn[a].x * r[a].x + Pn[a].y * r[a].y;
+    }
+    return 0.5 * e;
+}
+
 // ---------------------------------------------------------------- element launchers (tri3_cg.hip, quad4_cg.hip)
 // What the driver binds of a solve, by value.  block: threads per tile of a paired TRI3 plan (QUAD4 tiles are 256).
 struct CgElemArgs {
@@ -274,7 +324,8 @@ struct CgElemArgs {
     // linearisation writes it, its apply launches read it instead of calling log1p
     double *cq = nullptr;
     // shifted: the operator A = c_K K + c_M M (the MASS instances of tri3_cg.hip, quad4_cg.hip): k carries c_K, dm the mass
-    // coefficients
+    // coefficients; on the Neo-Hookean tangent A = c_K K_T + c_M M (the MASS instances of tri3_hyper_cg.hip,
+    // quad4_hyper_cg.hip): hk's lambda and mu carry c_K
     bool shifted = false;
     DynMass dm{};
 };

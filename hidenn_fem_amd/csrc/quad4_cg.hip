@@ -31,39 +31,6 @@
 namespace hfem {
 namespace {
 
-// One element's mass part: adds (M_e p)_a to the four rows, returns 1/2 p^T M_e p.
-__device__ __forceinline__ double quad4_mass_rows(const double2 (&Xn)[4], const double2 (&Pn)[4], const DynMass &m,
-                                                  double2 (&gu)[4]) {
-    double ad[4];
-    quad4_abs_dets(Xn, ad);
-    double2 r[4];
-    double nl[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) { r[a] = make_double2(0.0, 0.0); nl[a] = 0.0; }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double hx = 0.0, hy = 0.0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { hx += quad4_n(b, q) * Pn[b].x; hy += quad4_n(b, q) * Pn[b].y; }
-        const double w = ad[q] * m.m_off;
-        hx *= w; hy *= w;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            r[a].x += quad4_n(a, q) * hx; r[a].y += quad4_n(a, q) * hy;
-            nl[a] += quad4_n(a, q) * ad[q];
-        }
-    }
-    double e = 0.0;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const double wl = nl[a] * m.m_dd;
-        r[a].x = __builtin_fma(wl, Pn[a].x, r[a].x); r[a].y = __builtin_fma(wl, Pn[a].y, r[a].y);
-        gu[a].x += r[a].x; gu[a].y += r[a].y;
-        e += Pn[a].x * r[a].x + Pn[a].y * r[a].y;
-    }
-    return 0.5 * e;
-}
-
 // ---------------------------------------------------------------- q = K p (MASS: q = A p)
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
 // st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  MASS: k is the material constants times c_K.

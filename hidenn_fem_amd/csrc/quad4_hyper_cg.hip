@@ -19,6 +19,16 @@
 // per slot in the driver's memory, laid out so that lanes read consecutive doubles), and the apply reads them instead of
 // calling log1p four times per cell (Q1M: 52.5 -> 45.6 us per apply).  -DHFEM_QUAD4_TANGENT_RECOMPUTE builds the
 // apply that recomputes them (build.py --tag: the A/B build scripts/newton_timing.py --lib-tag measures).
+//
+// MASS = true is the operator A(u) = c_K K_T(u) + c_M M of an implicit finite-strain Newmark step (hidenn_fem_amd/dynamics.py,
+// HyperNewmarkSolver), picked by the launchers once hfem_cg_setup_hyper_shifted has bound the solver (the pattern
+// of quad4_cg.hip).  c_K is on the host: lambda and mu arrive times c_K.  Exact, because every term of dP carries exactly one
+// factor out of {mu, c_q = mu - lambda L_q, lambda}, each linear in (lambda, mu), and nothing else of the point's state
+// depends on the material: the stored c_q of a shifted linearisation is c_K times the plain one, written and read by the
+// same binding.  The mass part is quad4_mass_rows (hfem_cg_dev.h) on the corner rows of xy and p the slot already holds (its
+// |det J_q| are the determinants the tangent forms from the same bilinear coefficients): no second gather, the same LDS.  It
+// does not see the cell's inversion select: an inverted cell contributes zeros to K_T and its full mass to M.
+// MASS = false takes the DynMass argument and does not read it.
 #include <hip/hip_runtime.h>
 
 #include "hfem_cg_dev.h"
@@ -35,12 +45,12 @@ constexpr int kBlock = kQuad4HyperCgBlock, kNpt = 4, kEpt = 3;
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | p[cap_nodes] double2 | acc[2][cap_owned] | red[BLOCK / 64 + 2]
 // STORED: c_q = mu - lambda L_q of every slot and point is read from cq (written by the diag launch of this linearisation,
 // tile t at cq + 4 t elem_stride, point q at + q elem_stride: lanes read consecutive doubles) instead of calling log1p.
-template <int BLOCK, int NPT, int EPT, bool STORED>
+template <int BLOCK, int NPT, int EPT, bool STORED, bool MASS>
 __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_apply_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
     const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, const double2 *__restrict__ z, double2 *pbuf0,
-    double2 *pbuf1, double2 *__restrict__ q, Quad4HyperConsts k, double *__restrict__ partials, unsigned *ticket, double *st,
-    double *host, double *pq_out, const double *__restrict__ cq, int cap_nodes, int cap_owned) {
+    double2 *pbuf1, double2 *__restrict__ q, Quad4HyperConsts k, DynMass dm, double *__restrict__ partials, unsigned *ticket,
+    double *st, double *host, double *pq_out, const double *__restrict__ cq, int cap_nodes, int cap_owned) {
     static_assert(NPT * BLOCK >= kMaxLocal, "the row maps of a whole tile (<= 1024 local nodes) are held in registers");
     if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
     extern __shared__ double2 lds[];
@@ -104,7 +114,12 @@ __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_apply_kernel(
         bool inv;
         const double pq = STORED ? quad4_hyper_tangent_apply(Xn, Un, Pn, k, qe, jm1, inv, nullptr, c)
                                  : quad4_hyper_tangent_apply(Xn, Un, Pn, k, qe, jm1, inv);
-        if (p & kHomeBit) e_loc += 0.5 * pq;
+        if constexpr (MASS) {
+            const double em = quad4_mass_rows(Xn, Pn, dm, qe);
+            if (p & kHomeBit) e_loc += 0.5 * pq + em;       // 1/2 p_e . q_e of the sum
+        } else {
+            if (p & kHomeBit) e_loc += 0.5 * pq;
+        }
         add_row(l0, qe[0]);
         add_row(l1, qe[1]);
         add_row(l2, qe[2]);
@@ -121,11 +136,14 @@ __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_apply_kernel(
 
 // ---------------------------------------------------------------- block-Jacobi setup + inversion report
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | acc[3][cap_owned] | red[2][BLOCK / 64]
-template <int BLOCK, int NPT>
+// MASS: the blocks of A, the mass on xx and yy: M_e[a][a] = sum_q |det J_q| N_a(q) (m_off N_a(q) + m_dd), of every cell,
+// inverted or not.
+template <int BLOCK, int NPT, bool MASS>
 __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_diag_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, Quad4HyperConsts k, double *__restrict__ diag,
-    double *__restrict__ dinv, int precond, double *__restrict__ work, double *__restrict__ cq, int cap_nodes, int cap_owned) {
+    const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, Quad4HyperConsts k, DynMass dm,
+    double *__restrict__ diag, double *__restrict__ dinv, int precond, double *__restrict__ work, double *__restrict__ cq,
+    int cap_nodes, int cap_owned) {
     static_assert(NPT * BLOCK >= kMaxLocal, "the row maps of a whole tile (<= 1024 local nodes) are held in registers");
     extern __shared__ double2 lds[];
     double2 *nd_xy = lds, *nd_uv = lds + cap_nodes;
@@ -161,6 +179,8 @@ __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_diag_kernel(
         double blk[4][3], jm1, c[4];
         bool inv;
         quad4_hyper_tangent_blocks(Xn, Un, k, blk, jm1, inv, c);
+        double ad[4];                                       // |det J_q| (MASS only)
+        if constexpr (MASS) quad4_abs_dets(Xn, ad);
         if (cq) {                                           // every slot, home or halo: the apply reads it by slot
 #pragma unroll
             for (int g = 0; g < 4; ++g) cq[((size_t)slot * 4 + g) * pd.elem_stride + i] = c[g];
@@ -172,9 +192,14 @@ __global__ __launch_bounds__(BLOCK) void quad4_hyper_cg_diag_kernel(
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             if (l[a] >= n_owned) continue;
-            unsafeAtomicAdd(&acc0[l[a]], blk[a][0]);
+            double mm = 0.0;                                // M_e[a][a] (MASS only)
+            if constexpr (MASS) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) mm += ad[q] * quad4_n(a, q) * (dm.m_off * quad4_n(a, q) + dm.m_dd);
+            }
+            unsafeAtomicAdd(&acc0[l[a]], with_mass<MASS>(blk[a][0], mm));
             unsafeAtomicAdd(&acc1[l[a]], blk[a][1]);
-            unsafeAtomicAdd(&acc2[l[a]], blk[a][2]);
+            unsafeAtomicAdd(&acc2[l[a]], with_mass<MASS>(blk[a][2], mm));
         }
     }
     {
@@ -222,17 +247,26 @@ void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 
 #else
     constexpr bool stored = true;
 #endif
-    hipLaunchKernelGGL((quad4_hyper_cg_apply_kernel<kBlock, kNpt, kEpt, stored>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s,
-                       plan_dev(A.plan), A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, z, pbuf0, pbuf1, q, quad4_consts(A),
-                       partials, ticket, st, host, pq_out, A.cq, h.max_nodes, h.max_owned);
+#define HFEM_Q4HCG_APPLY(MASS)                                                                                                \
+    hipLaunchKernelGGL((quad4_hyper_cg_apply_kernel<kBlock, kNpt, kEpt, stored, MASS>), dim3(A.n_tiles), dim3(kBlock), A.lds, \
+                       A.s, plan_dev(A.plan), A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, z, pbuf0, pbuf1, q,    \
+                       quad4_consts(A), A.dm, partials, ticket, st, host, pq_out, A.cq, h.max_nodes, h.max_owned)
+    if (A.shifted) HFEM_Q4HCG_APPLY(true);
+    else HFEM_Q4HCG_APPLY(false);
+#undef HFEM_Q4HCG_APPLY
 }
 
 void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info) {
     const HostPlan &h = A.plan->host;
-    if (A.n_tiles > 0)
-        hipLaunchKernelGGL((quad4_hyper_cg_diag_kernel<kBlock, kNpt>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s, plan_dev(A.plan),
-                           A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, quad4_consts(A), diag, dinv, precond, work, A.cq,
-                           h.max_nodes, h.max_owned);
+#define HFEM_Q4HCG_DIAG(MASS)                                                                                                 \
+    hipLaunchKernelGGL((quad4_hyper_cg_diag_kernel<kBlock, kNpt, MASS>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s,           \
+                       plan_dev(A.plan), A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, quad4_consts(A), A.dm, diag, dinv, \
+                       precond, work, A.cq, h.max_nodes, h.max_owned)
+    if (A.n_tiles > 0) {
+        if (A.shifted) HFEM_Q4HCG_DIAG(true);
+        else HFEM_Q4HCG_DIAG(false);
+    }
+#undef HFEM_Q4HCG_DIAG
     if (info) launch_hyper_info(work, A.n_tiles, info, A.s);
 }
 

@@ -32,20 +32,6 @@
 namespace hfem {
 namespace {
 
-// One element's mass part: adds (M_e p)_a to the three rows, returns 1/2 p^T M_e p.
-__device__ __forceinline__ double tri3_mass_rows(const double2 X0, const double2 X1, const double2 X2, const double2 P0,
-                                                 const double2 P1, const double2 P2, const DynMass &m, double2 (&gu)[3]) {
-    const double det = (X0.x - X2.x) * (X1.y - X2.y) - (X1.x - X2.x) * (X0.y - X2.y);
-    const double A = fabs(det);
-    const double wo = A * m.m_off, wd = A * m.m_dd;
-    const double sx = wo * (P0.x + P1.x + P2.x), sy = wo * (P0.y + P1.y + P2.y);
-    const double2 r0 = make_double2(__builtin_fma(wd, P0.x, sx), __builtin_fma(wd, P0.y, sy));
-    const double2 r1 = make_double2(__builtin_fma(wd, P1.x, sx), __builtin_fma(wd, P1.y, sy));
-    const double2 r2 = make_double2(__builtin_fma(wd, P2.x, sx), __builtin_fma(wd, P2.y, sy));
-    gu[0].x += r0.x; gu[0].y += r0.y; gu[1].x += r1.x; gu[1].y += r1.y; gu[2].x += r2.x; gu[2].y += r2.y;
-    return 0.5 * (P0.x * r0.x + P0.y * r0.y + P1.x * r1.x + P1.y * r1.y + P2.x * r2.x + P2.y * r2.y);
-}
-
 // ---------------------------------------------------------------- q = K p (MASS: q = A p)
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
 // st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).  MASS: k is the material constants times c_K.

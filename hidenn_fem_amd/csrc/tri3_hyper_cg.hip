@@ -12,6 +12,17 @@
 //                                can be indefinite) and three partials per tile over its home elements {unused, min J,
 //                                inverted count}; hyper_info_kernel reduces them, so the host learns whether the
 //                                linearisation point has an inverted element without a second element launch.
+//
+// MASS = true is the operator A(u) = c_K K_T(u) + c_M M of an implicit finite-strain Newmark step (hidenn_fem_amd/dynamics.py,
+// HyperNewmarkSolver), which the launchers pick once hfem_cg_setup_hyper_shifted has bound the solver: the same
+// kernels with the mass code compiled in (the pattern of tri3_cg.hip).  c_K is on the host: HyperConsts::lambda and mu arrive
+// times c_K.  That is exact, not an approximation: every term of dP = mu dH + (mu - lambda L) T dH^T T + lambda (T : dH) T
+// carries exactly one factor out of {mu, c = mu - lambda L, lambda}, each linear in (lambda, mu), while T, L, J^-1 and A depend
+// on the state alone -- so K_T(c_K lambda, c_K mu) = c_K K_T(lambda, mu) and no instruction is added.  The mass part is
+// tri3_mass_rows (hfem_cg_dev.h) on the corner rows of xy and p the slot has already read from LDS: no second gather, the
+// same LDS.  It reads neither HyperTangent::sA (0 for an inverted element, and it carries the loss's W) nor W: an inverted
+// element contributes zeros to K_T and its full |det J_ref| (m_off + m_dd delta_ab) to M.  min J and the inverted count do
+// not change.  MASS = false takes the DynMass argument and does not read it.
 #include <hip/hip_runtime.h>
 
 #include "hfem_cg_dev.h"
@@ -26,12 +37,12 @@ constexpr int kBlock = 512, kNpt = 2, kEpt = 4, kInfoBlock = 256;
 // st != NULL: an iteration (p = z + beta p_old gathered, p stored to the other ping-pong buffer, alpha written);
 // st == NULL: the standalone apply (p = z as given, pq_out[0] = p^T q).
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | p[cap_nodes] double2 | acc[2][cap_owned] | red[BLOCK / 64 + 2]
-template <int BLOCK, int NPT, int EPT>
+template <int BLOCK, int NPT, int EPT, bool MASS>
 __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_apply_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
     const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, const double2 *__restrict__ z, double2 *pbuf0,
-    double2 *pbuf1, double2 *__restrict__ q, HyperConsts k, double *__restrict__ partials, unsigned *ticket, double *st,
-    double *host, double *pq_out, int cap_nodes, int cap_owned) {
+    double2 *pbuf1, double2 *__restrict__ q, HyperConsts k, DynMass dm, double *__restrict__ partials, unsigned *ticket,
+    double *st, double *host, double *pq_out, int cap_nodes, int cap_owned) {
     static_assert(NPT * BLOCK >= kMaxLocal, "the row maps of a whole tile (<= 1024 local nodes) are held in registers");
     if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
     extern __shared__ double2 lds[];
@@ -76,7 +87,12 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_apply_kernel(
         const HyperTangent t = hyper_tangent_state(nd_xy[l0], nd_xy[l1], nd_xy[l2], nd_uv[l0], nd_uv[l1], nd_uv[l2], k);
         double2 qe[3];
         const double pq = hyper_tangent_apply(t, k, nd_p[l0], nd_p[l1], nd_p[l2], qe);
-        if (p & kHomeBit) e_loc += 0.5 * pq;
+        if constexpr (MASS) {                               // the same LDS rows again: no store lies between, they are not re-read
+            const double em = tri3_mass_rows(nd_xy[l0], nd_xy[l1], nd_xy[l2], nd_p[l0], nd_p[l1], nd_p[l2], dm, qe);
+            if (p & kHomeBit) e_loc += 0.5 * pq + em;       // 1/2 p_e . q_e of the sum
+        } else {
+            if (p & kHomeBit) e_loc += 0.5 * pq;
+        }
         if (l0 < n_owned) { unsafeAtomicAdd(&acc0[l0], qe[0].x); unsafeAtomicAdd(&acc1[l0], qe[0].y); }
         if (l1 < n_owned) { unsafeAtomicAdd(&acc0[l1], qe[1].x); unsafeAtomicAdd(&acc1[l1], qe[1].y); }
         if (l2 < n_owned) { unsafeAtomicAdd(&acc0[l2], qe[2].x); unsafeAtomicAdd(&acc1[l2], qe[2].y); }
@@ -92,11 +108,12 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_apply_kernel(
 
 // ---------------------------------------------------------------- block-Jacobi setup + inversion report
 // LDS: xy[cap_nodes] double2 | uv[cap_nodes] double2 | acc[3][cap_owned] | red[2][BLOCK / 64]
-template <int BLOCK, int NPT>
+// MASS: the blocks of A, the mass on xx and yy: M_e[a][a] = |det J_ref| (m_off + m_dd), of every element, inverted or not.
+template <int BLOCK, int NPT, bool MASS>
 __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_diag_kernel(
     PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, HyperConsts k, double *__restrict__ diag,
-    double *__restrict__ dinv, int precond, double *__restrict__ work, int cap_nodes, int cap_owned) {
+    const double2 *__restrict__ u_free, const double2 *__restrict__ u_fixed, HyperConsts k, DynMass dm,
+    double *__restrict__ diag, double *__restrict__ dinv, int precond, double *__restrict__ work, int cap_nodes, int cap_owned) {
     extern __shared__ double2 lds[];
     double2 *nd_xy = lds, *nd_uv = lds + cap_nodes;
     double *acc0 = reinterpret_cast<double *>(lds + 2 * cap_nodes), *acc1 = acc0 + cap_owned, *acc2 = acc1 + cap_owned;
@@ -125,6 +142,11 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_diag_kernel(
         if (p & kSkipBit) continue;
         const int l[3] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask), (int)((p >> (2 * kLocalBits)) & kLocalMask)};
         const HyperTangent t = hyper_tangent_state(nd_xy[l[0]], nd_xy[l[1]], nd_xy[l[2]], nd_uv[l[0]], nd_uv[l[1]], nd_uv[l[2]], k);
+        double mm = 0.0;                                    // M_e[a][a], the same for the three corners (MASS only)
+        if constexpr (MASS) {
+            const double2 X0 = nd_xy[l[0]], X1 = nd_xy[l[1]], X2 = nd_xy[l[2]];
+            mm = fabs((X0.x - X2.x) * (X1.y - X2.y) - (X1.x - X2.x) * (X0.y - X2.y)) * (dm.m_off + dm.m_dd);
+        }
         if (p & kHomeBit) {
             j_min = fmin(j_min, 1.0 + t.j);
             n_inv += t.j > -1.0 ? 0.0 : 1.0;
@@ -137,9 +159,9 @@ __global__ __launch_bounds__(BLOCK) void tri3_hyper_cg_diag_kernel(
             double2 gu[3], hu[3];
             hyper_tangent_apply(t, k, a == 0 ? ex : o, a == 1 ? ex : o, a == 2 ? ex : o, gu);
             hyper_tangent_apply(t, k, a == 0 ? ey : o, a == 1 ? ey : o, a == 2 ? ey : o, hu);
-            unsafeAtomicAdd(&acc0[l[a]], gu[a].x);
+            unsafeAtomicAdd(&acc0[l[a]], with_mass<MASS>(gu[a].x, mm));
             unsafeAtomicAdd(&acc1[l[a]], 0.5 * (gu[a].y + hu[a].x));
-            unsafeAtomicAdd(&acc2[l[a]], hu[a].y);
+            unsafeAtomicAdd(&acc2[l[a]], with_mass<MASS>(hu[a].y, mm));
         }
     }
     {
@@ -192,17 +214,26 @@ void launch_tri3_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *
                                 double *partials, unsigned *ticket, double *st, double *host, double *pq_out) {
     const HostPlan &h = A.plan->host;
     if (A.n_tiles <= 0) return;
-    hipLaunchKernelGGL((tri3_hyper_cg_apply_kernel<kBlock, kNpt, kEpt>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s, plan_dev(A.plan),
-                       A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, z, pbuf0, pbuf1, q, A.hk, partials, ticket, st, host,
-                       pq_out, h.max_nodes, h.max_owned);
+#define HFEM_HCG_APPLY(MASS)                                                                                                  \
+    hipLaunchKernelGGL((tri3_hyper_cg_apply_kernel<kBlock, kNpt, kEpt, MASS>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s,     \
+                       plan_dev(A.plan), A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, z, pbuf0, pbuf1, q, A.hk, A.dm, \
+                       partials, ticket, st, host, pq_out, h.max_nodes, h.max_owned)
+    if (A.shifted) HFEM_HCG_APPLY(true);
+    else HFEM_HCG_APPLY(false);
+#undef HFEM_HCG_APPLY
 }
 
 void launch_tri3_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info) {
     const HostPlan &h = A.plan->host;
-    if (A.n_tiles > 0)
-        hipLaunchKernelGGL((tri3_hyper_cg_diag_kernel<kBlock, kNpt>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s, plan_dev(A.plan),
-                           A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, A.hk, diag, dinv, precond, work, h.max_nodes,
-                           h.max_owned);
+#define HFEM_HCG_DIAG(MASS)                                                                                                   \
+    hipLaunchKernelGGL((tri3_hyper_cg_diag_kernel<kBlock, kNpt, MASS>), dim3(A.n_tiles), dim3(kBlock), A.lds, A.s,            \
+                       plan_dev(A.plan), A.n_tiles, A.x_free, A.x_fixed, A.u_lin_free, A.u_fixed, A.hk, A.dm, diag, dinv,     \
+                       precond, work, h.max_nodes, h.max_owned)
+    if (A.n_tiles > 0) {
+        if (A.shifted) HFEM_HCG_DIAG(true);
+        else HFEM_HCG_DIAG(false);
+    }
+#undef HFEM_HCG_DIAG
     if (info) launch_hyper_info(work, A.n_tiles, info, A.s);
 }
 

@@ -188,8 +188,16 @@ class _NewtonSolverBase:
         if self._key is None or self._key != self._state_key():
             self.refresh()
 
-    # ---- launches (``_energy(u, g)`` is the element's: self._out = {Pi, min J, inverted count} and g = dPi/du_free at u, one
-    # launch of the energy kernel + its finish)
+    def _internal_tables(self):
+        """The force tables of the launch with NO forces (zero body table, no edges): ``_energy(u, g, tables)`` then gives the
+        internal energy ``Pi_int`` and ``f_int = dPi_int/du_free`` alone (``dynamics.HyperNewmarkSolver``)."""
+        body = self._body()
+        if body is not None:
+            body = type(body)()                             # zero-initialised ctypes array of the same length
+        return (body, None, (C.c_double * 4)(), HFEM_FLAG_NO_GX | HFEM_FLAG_NO_EDGES)
+
+    # ---- launches (``_energy(u, g, tables=None)`` is the element's: self._out = {Pi, min J, inverted count} and g = dPi/du_free
+    # at u, one launch of the energy kernel + its finish; ``tables``: force tables other than the refresh's)
     def _linearise(self):
         """Bind the driver to ``self._u`` and build the preconditioner there (one diag launch + the info reduction)."""
         check(_lib.lib().hfem_cg_setup_hyper(
@@ -403,8 +411,8 @@ class NewtonKrylovSolver(_NewtonSolverBase):
     def _body(self):
         return (C.c_double * 6)(*self.loss_fn._body_table(self.b_force))
 
-    def _energy(self, u, g):
-        bk, te, tc, flags = self._tables
+    def _energy(self, u, g, tables=None):
+        bk, te, tc, flags = self._tables if tables is None else tables
         check(_lib.lib().hfem_tri3_hyper_energy_plan(
             self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
             ptr(self._ufix) if self._ufix.numel() else None, self._lame, float(self.loss_fn._W), bk, ptr(te), tc,
@@ -438,8 +446,8 @@ class Quad4NewtonKrylovSolver(_NewtonSolverBase):
         bq = self.loss_fn._quad4_body(self.b_force)
         return None if bq is None else (C.c_double * 8)(*bq)
 
-    def _energy(self, u, g):
-        bq, te, tc, flags = self._tables
+    def _energy(self, u, g, tables=None):
+        bq, te, tc, flags = self._tables if tables is None else tables
         check(_lib.lib().hfem_quad4_hyper_energy_plan(
             self.plan.handle, 0, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, ptr(u),
             ptr(self._ufix) if self._ufix.numel() else None, self._lame, bq, ptr(te), tc, self._out.data_ptr(),

@@ -767,8 +767,19 @@ int hfem_cg_apply(hfem_cg *cg, const double *p, double *q, double *pq_out, void 
  *                 not copied: writing a new point into the same buffers and calling setup_hyper again re-linearises, and a
  *                 captured hfem_cg_iterate graph stays valid.
  * hfem_cg_start / iterate / status / apply / start_amg / iterate_amg work on such a solver unchanged; hfem_cg_setup refuses
- * it, and hfem_cg_setup_hyper refuses a solver of hfem_cg_create.                                                        */
+ * it, and hfem_cg_setup_hyper refuses a solver of hfem_cg_create.
+ *   setup_hyper_shifted  setup_hyper for the operator A(u) = c_k K_T(u) + c_m M of an implicit finite-strain Newmark step
+ *                 (DESIGN 27): the same bindings and checks, c_k and c_m as hfem_cg_setup_shifted (finite, >= 0, not both zero;
+ *                 c_k = 0 is the pure mass operator; c_m includes the density; lumped != 0: the row-sum mass).  The MASS
+ *                 instances of the tangent kernels: c_k scales lambda and mu on the host (K_T is linear in them), the mass term
+ *                 is formed in the slot loop from the corner rows the element already holds, always with |det J| of the
+ *                 coordinates.  An inverted element contributes zeros to K_T and its full mass to M; info_out is setup_hyper's.
+ *                 diag_out: the blocks of A.  An argument error leaves the solver as it was.  A later setup_hyper returns it to
+ *                 plain K_T; hfem_cg_setup_shifted keeps refusing such a solver.                                           */
 int hfem_cg_create_hyper(hfem_plan *plan, int64_t n_u, hfem_cg **out);
+int hfem_cg_setup_hyper_shifted(hfem_cg *cg, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                                const double *u_fixed, const double lame[2], double W, double c_k, double c_m, int32_t lumped,
+                                int32_t precond, double *diag_out, double *info_out, void *stream);
 int hfem_cg_setup_hyper(hfem_cg *cg, const double *x_free, const double *x_fixed, const double *u_lin_free,
                         const double *u_fixed, const double lame[2], double W, int32_t precond, double *diag_out,
                         double *info_out, void *stream);
@@ -1017,7 +1028,12 @@ int hfem_block_jacobi_apply(int device, const double *diag, const double *R, int
  *   newmark_rhs      rhs = load b0 - kw - alpha_r mv (mv may be NULL: no such term); g_zero = rhs, g0 = aa - rhs with aa = A a of
  *                the warm start a: the two vectors hfem_cg_start takes.
  *   newmark_correct  u = u_pred + beta dt^2 a, v = v_pred + gamma dt a (u may be u_pred, v may be v_pred).
- * The three vector entry points work on fp64 rows, len = 2 n_u doubles (even), are elementwise (one or two FMAs per entry:
+ *   newmark_trial    (finite strain) a_t = a + s d, u_t = u_pred + c_k a_t, ma_t = ma + s md in one pass: the trial
+ *                state of a Newton line search with M a carried along (ma = M a, md = M d).  a_t may be a, ma_t may be ma.
+ *   newmark_residual (finite strain) r = c_m ma + alpha_r mv + f_int - load b_ext (mv may be NULL: no such term), neg_r = -r (may
+ *                be NULL).  hfem_cg_start with g0 = g_zero = r starts the Newton system A d = -r; neg_r is its right-hand side
+ *                as a vector (what hfem_block_jacobi_apply takes where A is block diagonal).
+ * The five vector entry points work on fp64 rows, len = 2 n_u doubles (even), are elementwise (a few FMAs per entry:
  * bitwise reproducible), launch-only (capturable) and check their arguments before they touch a device. */
 int hfem_cg_setup_shifted(hfem_cg *cg, const double *x_free, const double *x_fixed, const double mat[4], double W, double c_k,
                           double c_m, int32_t lumped, int32_t precond, double *diag_out, void *stream);
@@ -1031,6 +1047,10 @@ int hfem_newmark_rhs(int device, const double *b0, const double *kw, const doubl
                      double alpha_r, double *g0, double *g_zero, void *stream);
 int hfem_newmark_correct(int device, const double *u_pred, const double *v_pred, const double *a, int64_t len, double dt,
                          double beta, double gamma, double *u, double *v, void *stream);
+int hfem_newmark_trial(int device, const double *a, const double *d, const double *u_pred, const double *ma, const double *md,
+                       int64_t len, double s, double c_k, double *a_t, double *u_t, double *ma_t, void *stream);
+int hfem_newmark_residual(int device, const double *ma, const double *mv, const double *f_int, const double *b_ext, int64_t len,
+                          double c_m, double alpha_r, double load, double *r, double *neg_r, void *stream);
 
 #ifdef __cplusplus
 }
