@@ -12,7 +12,8 @@ from src.models import PiecewiseLinearShapeNN2D
 
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
-        r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0, dynamics=0, dt=None):
+        r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0, dynamics=0, dt=None,
+        buckling=0):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -43,9 +44,18 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     for N Newmark steps (``hidenn_fem_amd.dynamics.NewmarkSolver``: average acceleration, consistent mass, unit density,
     preconditioner ``precond``), printing t, the tip displacement, the CG iterations and the total energy of every step;
     ``dt`` (``--dt``) defaults to 1/20 of the lowest mode's period (one ``vibration_modes`` solve).  Physical convention;
-    returns ``(model, [StepInfo])``; nothing else runs."""
+    returns ``(model, [StepInfo])``; nothing else runs.
+    ``buckling=N`` (``--buckling N``, N <= 8): the default traction REVERSED into compression; the frozen-mesh solve under it,
+    then the N smallest buckling load factors about that state (``hidenn_fem_amd.buckling.linear_buckling``: block LOBPCG on
+    ``K_G phi = theta K phi``, preconditioner ``precond``), printing ``lambda_j`` and the critical load
+    ``P_cr = lambda_1 |sum b_x|`` from the nodal load actually applied.  Physical convention, and for the triangles
+    ``gauss_order=1`` (weights that sum to the triangle's area), where the factors are those of the elastic plate; one GPU;
+    returns ``(model, BucklingInfo)``; nothing else runs."""
     import os
     import torch.distributed as dist
+    if buckling and (sharded or modes or dynamics):
+        raise NotImplementedError("example 4: buckling=N / --buckling N runs on one GPU and on its own; drop --sharded / --modes "
+                                  "/ --dynamics")
     if modes and sharded:
         raise NotImplementedError("example 4: modes=N / --modes N runs on one GPU (the modal solver is not sharded); drop "
                                   "sharded=True / --sharded")
@@ -61,9 +71,10 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
     if quad:
-        if not r_adapt and not modes and not dynamics:
-            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes or the dynamics only (pass "
-                                      "r_adapt=True / --r-adapt, modes=N / --modes N or dynamics=N / --dynamics N)")
+        if not r_adapt and not modes and not dynamics and not buckling:
+            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes, the dynamics or the buckling "
+                                      "analysis only (pass r_adapt=True / --r-adapt, modes=N / --modes N, dynamics=N / "
+                                      "--dynamics N or buckling=N / --buckling N)")
         from hidenn_fem_amd.mesh import structured_quad_mesh
         nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
     else:
@@ -76,7 +87,10 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype,
-                           grad_convention="physical" if (error_estimate or modes or dynamics) else None)
+                           grad_convention="physical" if (error_estimate or modes or dynamics or buckling) else None,
+                           **(dict(gauss_order=1) if buckling else {}))
+    if buckling:
+        return _buckling(model, loss_fn, buckling, precond)
     if modes:
         return _modes(model, loss_fn, modes, precond, rank0)
     if dynamics:
@@ -339,6 +353,29 @@ def _modes(model, loss_fn, n_modes, precond, rank0=True):
     return model, info
 
 
+def _buckling(model, loss_fn, n_modes, precond):
+    import time
+    from hidenn_fem_amd.buckling import linear_buckling
+    from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver
+    t_force = lambda x: -loss_fn.uniform_edge_force(x)                     # the default traction reversed into compression
+    cls = Quad4FrozenMeshSolver if getattr(model, "nodes_per_element", 3) == 4 else FrozenMeshSolver
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    static = cls(model, loss_fn, t_force=t_force, precond=precond, rtol=1e-10)
+    sinfo = static.solve()                                                 # writes u_free: the prestress state
+    load_x = float(static._gz[:, 0].sum().abs())                           # g_zero = dE/du at u = 0 = minus the nodal load b
+    info = linear_buckling(model, loss_fn, n_modes=n_modes, precond=precond, max_iter=200 if precond == "amg" else 5000)
+    torch.cuda.synchronize()
+    print(f"linear buckling under the reversed traction ({precond}): {sinfo.iterations} CG iterations ({sinfo.reason}), "
+          f"{info.iterations} LOBPCG iterations, converged {info.converged}, {info.n_buckling} of {n_modes} modes buckle, "
+          f"{time.perf_counter() - t0:.3f} s")
+    for j in range(n_modes):
+        th, lam, r = info.theta[j].item(), info.load_factors[j].item(), info.residual_norms[j].item()
+        print(f"mode {j + 1}: load factor {lam:.6e} (theta {th:.6e}, |K_G x - theta K x| {r:.3e})")
+    print(f"nodal load |sum b_x| = {load_x:.6e}; critical load P_cr = lambda_1 |sum b_x| = {info.load_factors[0].item() * load_x:.6e}")
+    return model, info
+
+
 def _dynamics(model, loss_fn, n_steps, dt, precond):
     import time
     from hidenn_fem_amd.dynamics import NewmarkSolver
@@ -470,6 +507,9 @@ if __name__ == "__main__":
                          "energy per step; with --dt, --quad and --precond block_jacobi|amg) and stop; with --neo-hookean: at "
                          "finite strain (a Newton-Krylov solve per step; also Newton iterations and min J)")
     ap.add_argument("--dt", type=float, default=None, help="time step of --dynamics (default: 1/20 of the lowest mode's period)")
+    ap.add_argument("--buckling", type=int, default=0, metavar="N",
+                    help="reverse the default traction into compression, solve, print the N smallest buckling load factors and "
+                         "the critical load (block LOBPCG, N <= 8; with --quad and --precond block_jacobi|amg) and stop")
     ap.add_argument("--newton", action="store_true",
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
@@ -483,4 +523,5 @@ if __name__ == "__main__":
         raise SystemExit(0)
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,
-        precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes, dynamics=a.dynamics, dt=a.dt)
+        precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes, dynamics=a.dynamics, dt=a.dt,
+        buckling=a.buckling)

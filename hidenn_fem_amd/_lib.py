@@ -205,6 +205,8 @@ PROTOTYPES = {
     "hfem_cg_setup_hyper_shifted": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp]),
     "hfem_newmark_trial": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "hfem_newmark_residual": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "hfem_geom_setup": (C.c_int, [C.c_int, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_geom_apply": (C.c_int, [C.c_int, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

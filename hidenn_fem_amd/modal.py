@@ -124,12 +124,14 @@ class ModalSolver:
     weights sum to 1/4), which halves every lambda; ``gauss_order=1`` (weights sum to 1/2) gives the plate's own.  Rigid-body
     modes are out of scope: the model needs Dirichlet rows."""
 
+    _who = "ModalSolver"                 # the name in error messages (BucklingSolver iterates the same loop on another pencil)
+
     def __init__(self, model, loss_fn, n_modes: int = 6, density: float = 1.0, mass: str = "consistent", precond: str = "amg",
                  rtol: float = 1e-8, max_iter: int = 200, block=None, seed: int = 0):
-        require_linear(loss_fn, "ModalSolver")
+        require_linear(loss_fn, self._who)
         npe = getattr(model, "nodes_per_element", 3)
         if npe not in (3, 4) or not hasattr(model, "_conn32"):
-            raise NotImplementedError("ModalSolver: TRI3 and QUAD4 mesh models")
+            raise NotImplementedError(f"{self._who}: TRI3 and QUAD4 mesh models")
         if mass not in ("consistent", "lumped"):
             raise ValueError("mass must be 'consistent' or 'lumped'")
         if precond not in ("amg", "block_jacobi"):
@@ -137,16 +139,16 @@ class ModalSolver:
         n_modes = int(n_modes)
         block = min(MAX_BLOCK, n_modes + 2) if block is None else int(block)
         if not 1 <= n_modes <= block <= MAX_BLOCK:
-            raise ValueError(f"ModalSolver: 1 <= n_modes <= block <= {MAX_BLOCK} (got n_modes={n_modes}, block={block})")
+            raise ValueError(f"{self._who}: 1 <= n_modes <= block <= {MAX_BLOCK} (got n_modes={n_modes}, block={block})")
         if not float(density) > 0.0:
             raise ValueError("density must be > 0")
         if rtol <= 0 or int(max_iter) < 1:
             raise ValueError("rtol must be > 0 and max_iter >= 1")
         if int(model._idx_udir.shape[0]) == 0:
-            raise ValueError("ModalSolver needs Dirichlet rows: without them K_ff is singular (rigid-body modes are out of scope)")
+            raise ValueError(f"{self._who} needs Dirichlet rows: without them K_ff is singular (rigid-body modes are out of scope)")
         n_u = int(model.u_free.shape[0])
         if 2 * n_u < 3 * block:
-            raise ValueError(f"ModalSolver: the basis [X P W] of 3 x block = {3 * block} vectors needs at least as many free "
+            raise ValueError(f"{self._who}: the basis [X P W] of 3 x block = {3 * block} vectors needs at least as many free "
                              f"dofs (the model has {2 * n_u}); lower block or n_modes")
         cls = _frozen_class(npe)
         self.solver = cls(model, loss_fn, precond=precond)          # refuses a CPU model: there is no CPU fallback
@@ -200,6 +202,13 @@ class ModalSolver:
         h, s = self.solver._h, stream_ptr(self.device)
         for k in range(m):
             check(_lib.lib().hfem_cg_apply(h, ptr(V[k]), ptr(out[k]), ptr(self._pq), s), "hfem_cg_apply")
+
+    # the two operators of the pencil A x = lambda B x as the loop of _iterate() reaches them: here (K, M)
+    def _a_into(self, V, out, m):
+        self._stiffness_into(V, out, m)
+
+    def _b_into(self, V, out, m):
+        self._mass_into(V, out, m)
 
     def mass_apply(self, V: torch.Tensor) -> torch.Tensor:
         """``M_ff V`` for a block ``[m, n_u, 2]`` (fp64, storage order).  For tests and measurements."""
@@ -261,7 +270,13 @@ class ModalSolver:
         v = torch.from_numpy(rng.standard_normal((self.n_u, self.block, 2)))      # rows in the caller's order
         return self.model.from_caller_order(v, "u").transpose(0, 1).contiguous().to(self.device)
 
-    def solve(self) -> ModalInfo:
+    def _ritz_order(self, b, at, ms, norms, lam):
+        """The basis columns of a Ritz step in the order their Gram matrix is factored: X, W, P, all of them."""
+        return list(range(b)) + list(range(at, ms)) + list(range(b, at))
+
+    def _iterate(self):
+        """The LOBPCG loop on the pencil (``_a_into``, ``_b_into``): ``(lambda [block], modes [n_modes, n_u, 2], residual norms
+        [n_modes], iterations, converged)``."""
         self._refresh()
         b, nm, n = self.block, self.n_modes, self.n_u
         self.restarts = 0                                     # Ritz steps of this solve that had to drop basis columns
@@ -272,13 +287,13 @@ class ModalSolver:
             nxt = [torch.zeros((3 * b, n, 2), **z) for _ in range(3)]
             S, KS, MS = cur
             S[:b].copy_(self._initial_block())
-            self._stiffness_into(S, KS, b)
-            self._mass_into(S, MS, b)
+            self._a_into(S, KS, b)
+            self._b_into(S, MS, b)
             self._grams(S, KS, MS, b)
             gk, gm, _ = self._read(b)
             rr = rayleigh_ritz(gk, gm, b)
             if rr is None:
-                raise RuntimeError("ModalSolver: the initial block is not linearly independent in the mass inner product")
+                raise RuntimeError(f"{self._who}: the initial block is not linearly independent in the inner product of the pencil")
             lam, coef, _ = rr
             self._combine(coef, lam, cur, nxt, b, b)
             cur, nxt = nxt, cur
@@ -296,8 +311,8 @@ class ModalSolver:
                 else:
                     self._residual_into(KS, MS, W, b)
                     self._precondition_into(W, W, b)
-                self._stiffness_into(W, KS[at:ms], b)
-                self._mass_into(W, MS[at:ms], b)
+                self._a_into(W, KS[at:ms], b)
+                self._b_into(W, MS[at:ms], b)
                 self._grams(S, KS, MS, ms)
                 gk, gm, norms = self._read(ms)               # the host synchronisation of the iteration
                 rnorm = norms[:nm, 0].copy()
@@ -306,11 +321,12 @@ class ModalSolver:
                     break
                 # the mass Gram is factored in the order X, W, P: a W or P column that depends on the ones before it is left
                 # out of this step (all of P left out = the classical restart).  X itself dependent: stop with the last good X.
-                rr = rayleigh_ritz(gk, gm, b, n_required=b, order=list(range(b)) + list(range(at, ms)) + list(range(b, at)))
+                order = self._ritz_order(b, at, ms, norms, lam)
+                rr = rayleigh_ritz(gk, gm, b, n_required=b, order=order)
                 if rr is None:
                     break
                 lam, cx, dropped = rr
-                self.restarts += int(dropped > 0)
+                self.restarts += int(dropped > ms - len(order))
                 cp = cx.copy()
                 cp[:b] = 0.0                                  # P = the part of the new X that is not in the old X
                 self._combine(np.concatenate([cx, cp], axis=1), lam, cur, nxt, ms, 2 * b)
@@ -318,6 +334,11 @@ class ModalSolver:
                 have_p = True
                 it += 1
             modes = cur[0][:nm].clone()
+        return lam, modes, rnorm, it, converged
+
+    def solve(self) -> ModalInfo:
+        lam, modes, rnorm, it, converged = self._iterate()
+        nm = self.n_modes
         lam_t = torch.from_numpy(lam[:nm].copy())
         info = ModalInfo(eigenvalues=lam_t, frequencies=torch.sqrt(lam_t.clamp_min(0.0)) / (2.0 * math.pi), modes=modes,
                          residual_norms=torch.from_numpy(rnorm), iterations=it, converged=converged)

@@ -1052,6 +1052,31 @@ int hfem_newmark_trial(int device, const double *a, const double *d, const doubl
 int hfem_newmark_residual(int device, const double *ma, const double *mv, const double *f_int, const double *b_ext, int64_t len,
                           double c_m, double alpha_r, double load, double *r, double *neg_r, void *stream);
 
+/* ------------------------------------------------------------------ linearised buckling: the geometric stiffness operator
+ * (csrc/buckling.hip; hidenn_fem_amd/buckling.py).  (K + lambda K_G(sigma_0)) phi = 0 as K_G phi = theta K phi,
+ * theta = -1 / lambda, by the block LOBPCG of the modal entry points above with K_G in the role of K and K in the role of M.
+ * No reference counterpart.
+ *   v^T K_G v = sum_e sum_q w_q |det J_q| sum_{i in x, y} (grad v_i)^T S_0(q) (grad v_i),  S_0 = [[s_xx, s_xy], [s_xy, s_yy]],
+ *   sigma = C eps(u_0) at the point; grad is the shape-function gradient of the convention (flags: HFEM_FLAG_PHYSICAL_GRAD or 0,
+ *   as hfem_cg_create), npe 3: constant gradients and the weight W |det J| (mat, W as hfem_cg_setup), npe 4: the 2x2 Gauss rule
+ *   with weights 1 (W is not read for the weights but must be > 0).  K_G acts per component (G x I_2).  fp64, bitwise
+ *   reproducible (no floating-point atomics, fixed-order sums); arguments are checked before a device is touched (negative codes,
+ *   message through hfem_last_error); launches only.
+ *   geom_setup   G [ne][npe][npe] (full rows, row-major): G_e[a][b] = sum_q w_q |det J_q| (g_a . S_0 g_b).  One thread per
+ *                element.  X [nn][2]: coordinates by node id; u_0 of a node n: u_free[node_row[n]] where node_row[n] >= 0, else
+ *                u_fixed[fixed_row[n]] (u_free [n_u][2], u_fixed [n_fix][2]; node_row, fixed_row [nn]; an index outside its
+ *                table reads as 0).
+ *   geom_apply   GV[k] = K_G V[k], k < m <= 8, over the free u rows: one thread per row walks the row's node fan (adj_ptr / adj,
+ *                row_node, node_row as hfem_mass_apply), reads row c of G_e and gathers the columns at the element's corners
+ *                (node_row -1 = Dirichlet: contributes 0).  One launch per call, in a register tile of 1, 2, 4 or 8 columns (a
+ *                ragged tile reads its last column again and does not store the surplus).  GV must not alias V.             */
+int hfem_geom_setup(int device, int32_t npe, int32_t flags, const double *X, const int32_t *conn, int64_t ne, int64_t nn,
+                    const double *u_free, int64_t n_u, const double *u_fixed, int64_t n_fix, const int32_t *node_row,
+                    const int32_t *fixed_row, const double mat[4], double W, double *G, void *stream);
+int hfem_geom_apply(int device, int32_t npe, const double *G, const int32_t *conn, int64_t ne, int64_t nn, const int32_t *adj_ptr,
+                    const int32_t *adj, const int32_t *row_node, const int32_t *node_row, int64_t n_u, const double *V, int32_t m,
+                    double *GV, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
