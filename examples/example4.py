@@ -13,7 +13,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
         r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0, dynamics=0, dt=None,
-        buckling=0):
+        buckling=0, harmonic=0):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -50,12 +50,21 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     ``K_G phi = theta K phi``, preconditioner ``precond``), printing ``lambda_j`` and the critical load
     ``P_cr = lambda_1 |sum b_x|`` from the nodal load actually applied.  Physical convention, and for the triangles
     ``gauss_order=1`` (weights that sum to the triangle's area), where the factors are those of the elastic plate; one GPU;
-    returns ``(model, BucklingInfo)``; nothing else runs."""
+    returns ``(model, BucklingInfo)``; nothing else runs.
+    ``harmonic=N`` (``--harmonic N``, N >= 2): the steady-state response of the plate to the default traction oscillating at N
+    frequencies from half the first natural frequency to 1.1 times the third (one ``vibration_modes`` solve for the three),
+    with Rayleigh damping of 2 % at the first and the third (``hidenn_fem_amd.harmonic.HarmonicSolver``: COCG on
+    ``K + i omega C - omega^2 M``, consistent mass, unit density, preconditioner ``precond``, each frequency warm-started from
+    the previous one), printing omega, the tip amplitude and phase and the iterations of every frequency.  Physical convention;
+    one GPU; returns ``(model, [HarmonicInfo])``; nothing else runs."""
     import os
     import torch.distributed as dist
     if buckling and (sharded or modes or dynamics):
         raise NotImplementedError("example 4: buckling=N / --buckling N runs on one GPU and on its own; drop --sharded / --modes "
                                   "/ --dynamics")
+    if harmonic and (sharded or modes or dynamics or buckling):
+        raise NotImplementedError("example 4: harmonic=N / --harmonic N runs on one GPU and on its own; drop --sharded / --modes "
+                                  "/ --dynamics / --buckling")
     if modes and sharded:
         raise NotImplementedError("example 4: modes=N / --modes N runs on one GPU (the modal solver is not sharded); drop "
                                   "sharded=True / --sharded")
@@ -71,10 +80,10 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
     if quad:
-        if not r_adapt and not modes and not dynamics and not buckling:
-            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes, the dynamics or the buckling "
-                                      "analysis only (pass r_adapt=True / --r-adapt, modes=N / --modes N, dynamics=N / "
-                                      "--dynamics N or buckling=N / --buckling N)")
+        if not r_adapt and not modes and not dynamics and not buckling and not harmonic:
+            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes, the dynamics, the buckling or "
+                                      "the harmonic analysis only (pass r_adapt=True / --r-adapt, modes=N / --modes N, dynamics=N "
+                                      "/ --dynamics N, buckling=N / --buckling N or harmonic=N / --harmonic N)")
         from hidenn_fem_amd.mesh import structured_quad_mesh
         nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
     else:
@@ -87,10 +96,12 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype,
-                           grad_convention="physical" if (error_estimate or modes or dynamics or buckling) else None,
+                           grad_convention="physical" if (error_estimate or modes or dynamics or buckling or harmonic) else None,
                            **(dict(gauss_order=1) if buckling else {}))
     if buckling:
         return _buckling(model, loss_fn, buckling, precond)
+    if harmonic:
+        return _harmonic(model, loss_fn, harmonic, precond)
     if modes:
         return _modes(model, loss_fn, modes, precond, rank0)
     if dynamics:
@@ -376,6 +387,38 @@ def _buckling(model, loss_fn, n_modes, precond):
     return model, info
 
 
+def _harmonic(model, loss_fn, n_freq, precond):
+    import cmath
+    import time
+    from hidenn_fem_amd.harmonic import HarmonicSolver
+    from hidenn_fem_amd.modal import vibration_modes
+    if n_freq < 2:
+        raise ValueError("example 4: harmonic=N / --harmonic N needs N >= 2 frequencies")
+    lam = vibration_modes(model, loss_fn, n_modes=3, precond=precond, max_iter=200 if precond == "amg" else 5000).eigenvalues
+    w1, w2, w3 = (lam[j].item() ** 0.5 for j in range(3))
+    zeta = 0.02
+    rayleigh = (2.0 * zeta * w1 * w3 / (w1 + w3), 2.0 * zeta / (w1 + w3))    # zeta at omega_1 and omega_3
+    print(f"natural frequencies omega_1..3 = {w1:.6e}, {w2:.6e}, {w3:.6e}; Rayleigh damping {zeta:.0%} at omega_1 and omega_3: "
+          f"alpha_R {rayleigh[0]:.6e}, beta_R {rayleigh[1]:.6e}")
+    solver = HarmonicSolver(model, loss_fn, rayleigh=rayleigh, precond=precond)
+    x = model.coords.detach()[model._idx_ufree.to(model.coords.device)]                 # node of every free u row (storage order)
+    tip = int(torch.argmax(x[:, 0] - 1e-3 * (x[:, 1] - 0.5 * x[:, 1].max()).abs()))     # right edge, nearest mid-height
+    print(f"harmonic response to the default traction (consistent mass, density 1, {precond}); tip = free row {tip} at "
+          f"({x[tip, 0].item():.3f}, {x[tip, 1].item():.3f})")
+    omegas = [0.5 * w1 + (1.1 * w3 - 0.5 * w1) * k / (n_freq - 1) for k in range(n_freq)]
+
+    def show(omega, u, info):
+        ux = complex(u[tip, 0].item())
+        print(f"omega {omega:.6e} ({omega / w1:6.3f} omega_1): tip |u_x| {abs(ux):.6e} phase {cmath.phase(ux):+.4f} |u_y| "
+              f"{abs(complex(u[tip, 1].item())):.6e} COCG {info.iterations:5d} ({info.reason})")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _, infos = solver.sweep(omegas, rows=[tip], callback=show)
+    torch.cuda.synchronize()
+    print(f"{n_freq} frequencies, {sum(i.iterations for i in infos)} COCG iterations, {time.perf_counter() - t0:.3f} s")
+    return model, infos
+
+
 def _dynamics(model, loss_fn, n_steps, dt, precond):
     import time
     from hidenn_fem_amd.dynamics import NewmarkSolver
@@ -510,12 +553,17 @@ if __name__ == "__main__":
     ap.add_argument("--buckling", type=int, default=0, metavar="N",
                     help="reverse the default traction into compression, solve, print the N smallest buckling load factors and "
                          "the critical load (block LOBPCG, N <= 8; with --quad and --precond block_jacobi|amg) and stop")
+    ap.add_argument("--harmonic", type=int, default=0, metavar="N",
+                    help="the tip amplitude of the steady-state response to the default traction at N frequencies spanning the "
+                         "first three modes, 2 %% Rayleigh damping (COCG; with --quad and --precond block_jacobi|amg) and stop")
     ap.add_argument("--newton", action="store_true",
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
     a = ap.parse_args()
     if a.precond == "amg_tangent" and not (a.neo_hookean and (a.newton or a.r_adapt)):
         ap.error("--precond amg_tangent needs --neo-hookean with --newton or --r-adapt (with or without --quad)")
+    if a.harmonic and a.neo_hookean:
+        ap.error("--harmonic is a linear analysis: drop --neo-hookean")
     if a.neo_hookean:
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad,
                         dynamics=a.dynamics, dt=a.dt,
@@ -524,4 +572,4 @@ if __name__ == "__main__":
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,
         precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes, dynamics=a.dynamics, dt=a.dt,
-        buckling=a.buckling)
+        buckling=a.buckling, harmonic=a.harmonic)

@@ -207,6 +207,13 @@ PROTOTYPES = {
     "hfem_newmark_residual": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
     "hfem_geom_setup": (C.c_int, [C.c_int, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _vp]),
     "hfem_geom_apply": (C.c_int, [C.c_int, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "hfem_harm_create": (C.c_int, [_vp, _i64, _i32, C.POINTER(_vp)]),
+    "hfem_harm_destroy": (C.c_int, [_vp]),
+    "hfem_harm_setup": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _i32, _vp]),
+    "hfem_harm_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "hfem_harm_start": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _i64, _vp]),
+    "hfem_harm_iterate": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "hfem_harm_status": (C.c_int, [_vp, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

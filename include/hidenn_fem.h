@@ -1077,6 +1077,50 @@ int hfem_geom_apply(int device, int32_t npe, const double *G, const int32_t *con
                     const int32_t *adj, const int32_t *row_node, const int32_t *node_row, int64_t n_u, const double *V, int32_t m,
                     double *GV, void *stream);
 
+/* ------------------------------------------------------------------ harmonic frequency response: complex shifted operator and COCG
+ * (csrc/harmonic.hip; hidenn_fem_amd/harmonic.py).  No reference counterpart.  The steady state of
+ * M u'' + C u' + K u = Re(b e^{i w t}), C = alpha_R M + beta_R K (+ structural damping i eta K), over the free u rows:
+ *   A x = b,   A = z_k K + z_m M,   z_k = 1 + i (w beta_R + eta),   z_m = rho (-w^2 + i w alpha_R)
+ * K is hfem_cg_apply's operator, M hfem_mass_apply's at unit density (z_m INCLUDES the density), always |det J|.  A is complex
+ * symmetric; its real part is indefinite above the first resonance.  A complex vector is an fp64 block vector [2][n_u][2]: plane
+ * 0 real, plane 1 imaginary, each in the storage order of u_free (a plane is what hfem_amg_vcycle takes, both are what
+ * hfem_block_jacobi_apply takes at m = 2); `len` = 4 n_u doubles.  The solver is preconditioned COCG (conjugate orthogonal
+ * conjugate gradients) with a REAL SPD preconditioner T applied to each plane: every inner product unconjugated, the stopping
+ * test |r|_2 <= max(rtol |b|_2, atol) in the Hermitian norm; all scalars reduced and consumed on the device in a fixed order.
+ * Once halted (converged, max_iter, breakdown: a non-finite scalar, or |p^T A p| = 0 or |r^T z| = 0 before x moves) later
+ * launches write nothing: x keeps the last good iterate.  Launches per iteration: 3 (apply; update of x and r with z = T r,
+ * rho, beta and the stopping test; p = z + beta p) with T = none or block Jacobi, 6 with AMG (apply; update; one V-cycle per
+ * plane; rho and beta; p).
+ *   create   plan and flags as hfem_cg_create (a paired TRI3 plan or a QUAD4 plan).  Refused: a host-only plan, the
+ *            one-element-per-slot TRI3 plan of the Neo-Hookean tangent, and a plan with a tile whose apply needs more than 64 KiB
+ *            of LDS:  48 x (max local nodes of a tile) + 32 x (max owned rows of a tile) + 8 x (2 x threads / 64 + 2) bytes,
+ *            threads = 256 (512 for a 512-thread paired plan); the message carries the numbers.  The plan must outlive the solver.
+ *   setup    binds the coordinate rows (fp64; they must stay allocated and unchanged while iterating), the material (mat, W as
+ *            hfem_cg_setup: UNSCALED) and the mass kind (lumped != 0: the row sum), and stores zk[2] = (Re, Im) z_k, zm[2] =
+ *            (Re, Im) z_m (HOST pointers) in device memory on `stream`: finite, not all zero, any sign.  A captured
+ *            hfem_harm_iterate reads them there, so it stays valid across setups.
+ *   apply    standalone Q = A P and pq_out[2] (device) = (Re, Im) of the unconjugated P^T Q; not during iterate.  Q != P.
+ *   start    r = b - A x0 (x0 NULL: r = b), z = T r, p = z; resets the status record.  T: amg != NULL: one V-cycle of that
+ *            hierarchy per plane (hfem_amg_setup_shifted on a REAL SPD operator, e.g. K + w^2 rho M); diag != NULL: the inverses
+ *            of the 2x2 blocks diag [n_u][3] (hfem_cg_setup_shifted's diag_out; a block that is not positive definite is the
+ *            identity); both NULL: none; both given is an argument error.
+ *   iterate  n_iter > 0 iterations on x, which must hold x0 (zeros when x0 was NULL) at the first call after start; amg: the
+ *            hierarchy start was given (NULL when it was given none).  Launch only: capturable in a hipGraph.
+ *   status   synchronises the stream; status_host[16] = {iterations, |r|, |b|, Re rho, reason (0 running, 1 rtol, 2 atol,
+ *            3 max_iter, 4 breakdown), Re alpha, Re beta, Re mu, tolerance, max_iter, halted, rtol-wins, Im rho, Im alpha, Im beta,
+ *            Im mu}, rho = r^T z, mu = p^T A p, the last ones formed.
+ * Every entry point checks its arguments before it touches a device (negative code, message through hfem_last_error).       */
+typedef struct hfem_harm hfem_harm;
+int hfem_harm_create(hfem_plan *plan, int64_t n_u, int32_t flags, hfem_harm **out);
+int hfem_harm_destroy(hfem_harm *harm);
+int hfem_harm_setup(hfem_harm *harm, const double *x_free, const double *x_fixed, const double mat[4], double W, const double zk[2],
+                    const double zm[2], int32_t lumped, void *stream);
+int hfem_harm_apply(hfem_harm *harm, const double *P, double *Q, int64_t len, double *pq_out, void *stream);
+int hfem_harm_start(hfem_harm *harm, hfem_amg *amg, const double *diag, const double *b, const double *x0, int64_t len, double rtol,
+                    double atol, int64_t max_iter, void *stream);
+int hfem_harm_iterate(hfem_harm *harm, hfem_amg *amg, double *x, int64_t len, int32_t n_iter, void *stream);
+int hfem_harm_status(hfem_harm *harm, double *status_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
