@@ -13,7 +13,7 @@ from src.models import PiecewiseLinearShapeNN2D
 
 def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=False, sharded=False, solve_first=False,
         r_adapt=False, outer=20, precond="block_jacobi", quad=False, error_estimate=False, modes=0, dynamics=0, dt=None,
-        buckling=0, harmonic=0):
+        buckling=0, harmonic=0, topopt=0):
     """``sharded=True``: the same loop OWNER-SHARDED over the ranks of the process group (one process per GPU:
     ``python -m torch.distributed.run --nproc-per-node N examples/example4.py --sharded``; a single process works too): elements
     are split into per-rank tile ranges and L-BFGS itself is node-sharded (``hidenn_fem_amd.optim.ShardedLBFGS``: every rank keeps
@@ -56,12 +56,20 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     with Rayleigh damping of 2 % at the first and the third (``hidenn_fem_amd.harmonic.HarmonicSolver``: COCG on
     ``K + i omega C - omega^2 M``, consistent mass, unit density, preconditioner ``precond``, each frequency warm-started from
     the previous one), printing omega, the tip amplitude and phase and the iterations of every frequency.  Physical convention;
-    one GPU; returns ``(model, [HarmonicInfo])``; nothing else runs."""
+    one GPU; returns ``(model, [HarmonicInfo])``; nothing else runs.
+    ``topopt=N`` (``--topopt N``): N design iterations of density-based (SIMP) compliance minimisation of the plate under the
+    default traction (``hidenn_fem_amd.topopt.TopologyOptimizer``: volume fraction 0.4, penal 3, density filter of 1.5 mean
+    element sizes, optimality-criteria update with its bisection on the device, preconditioner ``precond``), printing the
+    compliance, the volume, the change, the PCG iterations and the multiplier of every iteration.  Physical convention; one
+    GPU; ``quad=True`` gives the QUAD4 plate; returns ``(model, TopologyOptimizer, [TopOptInfo])``; nothing else runs."""
     import os
     import torch.distributed as dist
     if buckling and (sharded or modes or dynamics):
         raise NotImplementedError("example 4: buckling=N / --buckling N runs on one GPU and on its own; drop --sharded / --modes "
                                   "/ --dynamics")
+    if topopt and (sharded or modes or dynamics or buckling or harmonic):
+        raise NotImplementedError("example 4: topopt=N / --topopt N runs on one GPU and on its own; drop --sharded / --modes "
+                                  "/ --dynamics / --buckling / --harmonic")
     if harmonic and (sharded or modes or dynamics or buckling):
         raise NotImplementedError("example 4: harmonic=N / --harmonic N runs on one GPU and on its own; drop --sharded / --modes "
                                   "/ --dynamics / --buckling")
@@ -80,10 +88,11 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     holes = [(0.5, 0.7, 0.12), (1.0, 0.3, 0.15), (1.4, 0.6, 0.1)]
     sides = {"up": 0, "down": 0, "right": 2, "left": 1}
     if quad:
-        if not r_adapt and not modes and not dynamics and not buckling and not harmonic:
-            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes, the dynamics, the buckling or "
-                                      "the harmonic analysis only (pass r_adapt=True / --r-adapt, modes=N / --modes N, dynamics=N "
-                                      "/ --dynamics N, buckling=N / --buckling N or harmonic=N / --harmonic N)")
+        if not r_adapt and not modes and not dynamics and not buckling and not harmonic and not topopt:
+            raise NotImplementedError("example 4: quad=True runs the r-adaptive solve, the modes, the dynamics, the buckling, "
+                                      "the harmonic analysis or the topology optimisation only (pass r_adapt=True / --r-adapt, "
+                                      "modes=N / --modes N, dynamics=N / --dynamics N, buckling=N / --buckling N, harmonic=N / "
+                                      "--harmonic N or topopt=N / --topopt N)")
         from hidenn_fem_amd.mesh import structured_quad_mesh
         nodes, conn, geom, bc, mn, edges = structured_quad_mesh(nx, ny, length=length, height=height, boundaries=sides)
     else:
@@ -96,12 +105,14 @@ def run(nx=200, ny=100, steps=30, dtype=torch.float32, log_every=5, fused_lbfgs=
     model = PiecewiseLinearShapeNN2D(nodes.to(dtype), conn, boundary_mask=geom, dirichlet_mask=bc, u_fixed=0.0,
                                      neumann_edges=edges).to(dev)
     loss_fn = EnergyLoss2D(E=10e9, nu=0.3, length=length, height=height, device=dev, dtype=dtype,
-                           grad_convention="physical" if (error_estimate or modes or dynamics or buckling or harmonic) else None,
+                           grad_convention="physical" if (error_estimate or modes or dynamics or buckling or harmonic or topopt) else None,
                            **(dict(gauss_order=1) if buckling else {}))
     if buckling:
         return _buckling(model, loss_fn, buckling, precond)
     if harmonic:
         return _harmonic(model, loss_fn, harmonic, precond)
+    if topopt:
+        return _topopt(model, loss_fn, topopt, precond)
     if modes:
         return _modes(model, loss_fn, modes, precond, rank0)
     if dynamics:
@@ -419,6 +430,30 @@ def _harmonic(model, loss_fn, n_freq, precond):
     return model, infos
 
 
+def _topopt(model, loss_fn, n_iter, precond):
+    import time
+    from hidenn_fem_amd.topopt import TopologyOptimizer
+    with torch.no_grad():
+        model.u_free.zero_()
+    opt = TopologyOptimizer(model, loss_fn, 0.4, precond=precond)
+    print(f"SIMP compliance minimisation under the default traction: volume fraction 0.4, penal 3, filter radius "
+          f"{opt.filter_radius:.4e} (1.5 mean element sizes), e_min {opt.e_min:g}, move {opt.move:g}, {precond}")
+    total = float(opt.volumes.sum())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    infos = []
+    for k in range(n_iter):
+        info = opt.step()
+        infos.append(info)
+        print(f"iteration {k + 1:4d}: compliance {info.compliance:.6e} volume fraction {info.volume / total:.6f} change "
+              f"{info.change:.4f} PCG {info.iterations:5d} lambda {info.lam:.4e}" + ("" if info.feasible else " INFEASIBLE"))
+    torch.cuda.synchronize()
+    rf = opt.filtered_density
+    print(f"{n_iter} design iterations, {sum(i.iterations for i in infos)} PCG iterations, {time.perf_counter() - t0:.3f} s; "
+          f"grey elements (0.1 < rho~ < 0.9): {int(((rf > 0.1) & (rf < 0.9)).sum())} of {rf.numel()}")
+    return model, opt, infos
+
+
 def _dynamics(model, loss_fn, n_steps, dt, precond):
     import time
     from hidenn_fem_amd.dynamics import NewmarkSolver
@@ -556,6 +591,9 @@ if __name__ == "__main__":
     ap.add_argument("--harmonic", type=int, default=0, metavar="N",
                     help="the tip amplitude of the steady-state response to the default traction at N frequencies spanning the "
                          "first three modes, 2 %% Rayleigh damping (COCG; with --quad and --precond block_jacobi|amg) and stop")
+    ap.add_argument("--topopt", type=int, default=0, metavar="N",
+                    help="N design iterations of SIMP compliance topology optimisation under the default traction (volume "
+                         "fraction 0.4, OC update; with --quad and --precond block_jacobi|amg) and stop")
     ap.add_argument("--newton", action="store_true",
                     help="with --neo-hookean: solve every load increment with NewtonKrylovSolver (with --quad: "
                          "Quad4NewtonKrylovSolver) instead of FusedLBFGS")
@@ -564,6 +602,8 @@ if __name__ == "__main__":
         ap.error("--precond amg_tangent needs --neo-hookean with --newton or --r-adapt (with or without --quad)")
     if a.harmonic and a.neo_hookean:
         ap.error("--harmonic is a linear analysis: drop --neo-hookean")
+    if a.topopt and a.neo_hookean:
+        ap.error("--topopt is a linear analysis: drop --neo-hookean")
     if a.neo_hookean:
         run_neo_hookean(a.nx, a.ny, a.steps or 100, load_steps=a.load_steps, newton=a.newton, precond=a.precond, quad=a.quad,
                         dynamics=a.dynamics, dt=a.dt,
@@ -572,4 +612,4 @@ if __name__ == "__main__":
     run(a.nx, a.ny, a.steps or 30, torch.float64 if a.fp64 else torch.float32, fused_lbfgs=a.fused_lbfgs, sharded=a.sharded,
         solve_first=a.solve_first, r_adapt=a.r_adapt, outer=a.outer or 20,
         precond=a.precond, quad=a.quad, error_estimate=a.error_estimate, modes=a.modes, dynamics=a.dynamics, dt=a.dt,
-        buckling=a.buckling, harmonic=a.harmonic)
+        buckling=a.buckling, harmonic=a.harmonic, topopt=a.topopt)

@@ -214,6 +214,17 @@ PROTOTYPES = {
     "hfem_harm_start": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _i64, _vp]),
     "hfem_harm_iterate": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "hfem_harm_status": (C.c_int, [_vp, _vp, _vp]),
+    "hfem_cg_setup_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _i32, _vp, _vp]),
+    "hfem_amg_assemble_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp]),
+    "hfem_amg_setup_scaled": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp]),
+    "hfem_topt_create": (C.c_int, [_vp, _vp, _vp, _i64, _f64, C.POINTER(_vp)]),
+    "hfem_topt_destroy": (C.c_int, [_vp]),
+    "hfem_topt_slots": (_i64, [_vp]),
+    "hfem_topt_weights": (C.c_int, [_vp, _vp, _f64, _f64, _vp, _vp, _vp]),
+    "hfem_topt_filter": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "hfem_topt_energy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _f64, _f64, _vp, _vp, _vp]),
+    "hfem_topt_oc": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _f64, _i32, _vp, _vp, _vp]),
+    "hfem_topt_status": (C.c_int, [_vp, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

@@ -3,7 +3,8 @@
 // element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
 // (the model's own QUAD4 plan), tri3_hyper_cg.hip or quad4_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point,
 // on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
-// cg_apply and cg_diag.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
+// cg_apply and cg_diag.  The element-scaled operator K(w) = sum_e w_e K_e (after hfem_cg_setup_scaled) is a fifth kind: the
+// sibling kernels of topopt.hip on the plain kernels' plans.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
 // hidenn_fem_amd/dynamics.py) is no element kind of its own: it is the MASS instance of the kernels of tri3_cg.hip and
 // quad4_cg.hip, picked by their launchers; likewise c_K K_T + c_M M of a finite-strain step (after
 // hfem_cg_setup_hyper_shifted) is the MASS instance of the tangent kernels.  The residual r = -dE/du comes from the graded energy kernel, called by the host
@@ -186,6 +187,9 @@ struct hfem_cg {
     // tri3_hyper_cg.hip / quad4_hyper_cg.hip)
     bool shifted = false;
     hfem::DynMass dm{};
+    // bound by hfem_cg_setup_scaled: K(w) = sum_e w_e K_e, one weight record per slot of the plan (the kernels of topopt.hip)
+    bool scaled = false;
+    const double *w_slot = nullptr;
     // bound by hfem_cg_setup_hyper
     const double2 *u_lin = nullptr, *u_fixed = nullptr;
     hfem::HyperConsts hk{};
@@ -199,6 +203,7 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     A.k = c->k; A.lds = lds; A.s = s;
     A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq;
     A.shifted = c->shifted; A.dm = c->dm;
+    A.w_slot = c->w_slot;
     return A;
 }
 
@@ -208,6 +213,8 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
     const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->scaled && c->quad) hfem::launch_quad4_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->scaled) hfem::launch_tri3_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
@@ -216,6 +223,8 @@ void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStrea
     const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
     if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    else if (c->scaled && c->quad) hfem::launch_quad4_scaled_diag(A, diag, c->dinv, precond);
+    else if (c->scaled) hfem::launch_tri3_scaled_diag(A, diag, c->dinv, precond);
     else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }
@@ -392,8 +401,33 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);   // QUAD4: the 2x2 rule's weights are 1 (hfem_quad4_energy_plan_ex)
     c->shifted = false; c->dm = hfem::DynMass{};
+    c->scaled = false; c->w_slot = nullptr;
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup")) return rc;
+    c->ready = true;
+    return 0;
+}
+
+// hfem_cg_setup for K(w) = sum_e w_e K_e: the same bindings plus the slot-ordered weights, bound as a POINTER (new weights in
+// the same buffer and another call re-linearise; a captured iterate graph stays valid, as after hfem_cg_setup_hyper)
+extern "C" int hfem_cg_setup_scaled(hfem_cg *c, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                    const double *w_slot, int32_t precond, double *diag_out, void *stream) {
+    HFEM_ARG_CHECK(c && x_free && mat, "null pointer");
+    HFEM_ARG_CHECK(w_slot, "w_slot must be given (one weight record per slot of the plan)");
+    HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+    HFEM_ARG_CHECK(!c->hyper, "this solver was created by hfem_cg_create_hyper: the scaled operator exists for hfem_cg_create");
+    bool fixed_rows = false;
+    const hfem::HostPlan &h = c->plan->host;
+    for (size_t i = 0; i < h.node_src.size(); i += 2) fixed_rows = fixed_rows || h.node_src[i] < 0;
+    HFEM_ARG_CHECK(x_fixed || !fixed_rows, "the plan reads fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
+    c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);
+    c->shifted = false; c->dm = hfem::DynMass{};
+    c->scaled = true; c->w_slot = w_slot;
+    cg_diag(c, diag_out, precond, nullptr, s);
+    if (int rc = hfem::launch_status("hfem_cg_setup_scaled")) return rc;
     c->ready = true;
     return 0;
 }
@@ -415,6 +449,7 @@ extern "C" int hfem_cg_setup_shifted(hfem_cg *c, const double *x_free, const dou
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::scaled_consts(hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr), c_k);
     c->shifted = true; c->dm = hfem::dyn_mass(c->quad, c_m, lumped != 0);
+    c->scaled = false; c->w_slot = nullptr;
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup_shifted")) return rc;
     c->ready = true;

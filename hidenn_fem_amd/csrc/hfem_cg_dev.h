@@ -328,6 +328,9 @@ struct CgElemArgs {
     // quad4_hyper_cg.hip): hk's lambda and mu carry c_K
     bool shifted = false;
     DynMass dm{};
+    // the element-scaled operator K(w) = sum_e w_e K_e (topopt.hip): one weight record per slot of the plan, addressed as
+    // elem_pack (a paired TRI3 plan: double2 {w_A, w_B}; a QUAD4 plan: one double)
+    const double *w_slot = nullptr;
 };
 // q = K p, or q = A p where A.shifted (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
@@ -350,5 +353,13 @@ constexpr int kQuad4HyperCgBlock = 256;
 void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
                                  double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
+// The element-scaled operator K(w) (topopt.hip; A.w_slot bound): siblings of the four plain launchers on the same tile plans
+// and the same dispatch, the same LDS sizes
+void launch_tri3_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
+                              unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_quad4_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
+                               unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_tri3_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
+void launch_quad4_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 
 }  // namespace hfem

@@ -579,6 +579,44 @@ __global__ __launch_bounds__(kBlock) void amg_coarse_gemv_kernel(int32_t N, cons
 
 inline dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 
+// K(w)_ff = sum_e w_e K_e,ff (hfem_amg_assemble_scaled): amg_assemble_kernel's walk with the element's weight,
+// read by global element id, multiplied into its four block entries.  One thread per row, no atomics: bit-reproducible.
+// The scaled setup (hfem_amg_setup_scaled: a design iteration or a multi-material solve) is the numeric setup above on these
+// values.  Defined behind the file's last kernel: the compiler's resource reports name source lines, and no kernel above moves.
+template <int NPE, bool PHYS>
+__global__ __launch_bounds__(kBlock) void amg_assemble_scaled_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
+                                                                     const int32_t *__restrict__ fan_elem,
+                                                                     const int32_t *__restrict__ fan_corner,
+                                                                     const int32_t *__restrict__ fan_slot,
+                                                                     const int32_t *__restrict__ conn_x,
+                                                                     const double2 *__restrict__ x_free,
+                                                                     const double2 *__restrict__ x_fixed,
+                                                                     const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
+                                                                     Tri3Consts k, const double *__restrict__ w_elem) {
+    const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (r >= n) return;
+    for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
+        *reinterpret_cast<double4 *>(a_val + 4 * (size_t)s) = make_double4(0.0, 0.0, 0.0, 0.0);
+    for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
+        const int32_t e = fan_elem[f], a = fan_corner[f];
+        const int32_t *cx = conn_x + NPE * (size_t)e;
+        const double w = w_elem[e];
+        double2 X[NPE], gu[NPE], hu[NPE];
+#pragma unroll
+        for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
+        unit_columns<PHYS>(X, a, k, gu, hu);
+#pragma unroll
+        for (int b = 0; b < NPE; ++b) {
+            const int32_t s = fan_slot[NPE * (size_t)f + b];
+            if (s < 0) continue;
+            double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
+            double4 v = *p;
+            v.x += w * gu[b].x; v.y += w * gu[b].y; v.z += w * hu[b].x; v.w += w * hu[b].y;
+            *p = v;
+        }
+    }
+}
+
 }  // namespace
 }  // namespace hfem
 
@@ -733,6 +771,23 @@ void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const do
 #undef HFEM_AMG_ASM
 }
 
+// K(w)_ff: w_elem[ne] by global element id (device)
+void assemble_scaled(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, const double *w_elem,
+                     hipStream_t s) {
+    const DevLevel &L = a->lv[0];
+    const bool quad = a->npe == 4;
+    const hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);
+#define HFEM_AMG_ASM_SCALED(NPE, PH)                                                                                          \
+    hipLaunchKernelGGL((hfem::amg_assemble_scaled_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,        \
+                       a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed,  \
+                       L.a_ptr, L.a_val, k, w_elem)
+    if (quad && a->phys) HFEM_AMG_ASM_SCALED(4, true);
+    else if (quad) HFEM_AMG_ASM_SCALED(4, false);
+    else if (a->phys) HFEM_AMG_ASM_SCALED(3, true);
+    else HFEM_AMG_ASM_SCALED(3, false);
+#undef HFEM_AMG_ASM_SCALED
+}
+
 void assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
                     const double lame[2], double W, hipStream_t s) {
     const DevLevel &L = a->lv[0];
@@ -882,6 +937,30 @@ extern "C" int hfem_amg_setup_shifted(hfem_amg *a, const double *x_free, const d
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup_shifted");
+}
+
+// The pair on K(w) = sum_e w_e K_e: the hierarchy's patterns and aggregates are the mesh's; only the values are rebuilt.
+extern "C" int hfem_amg_assemble_scaled(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                        const double *w_elem, void *stream) {
+    HFEM_ARG_CHECK(a && x_free && mat, "null pointer");
+    HFEM_ARG_CHECK(w_elem, "w_elem must be given (one weight per element)");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    assemble_scaled(a, x_free, x_fixed, mat, W, w_elem, (hipStream_t)stream);
+    return hfem::launch_status("hfem_amg_assemble_scaled");
+}
+
+extern "C" int hfem_amg_setup_scaled(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                                     const double *w_elem, double *coarse_out, void *stream) {
+    HFEM_ARG_CHECK(a && x_free && mat && coarse_out, "null pointer");
+    HFEM_ARG_CHECK(w_elem, "w_elem must be given (one weight per element)");
+    HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
+    if (int rc = hfem::use_device(a->device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    assemble_scaled(a, x_free, x_fixed, mat, W, w_elem, s);
+    hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
+                       (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
+    return setup_levels(a, coarse_out, s, "hfem_amg_setup_scaled");
 }
 
 extern "C" int hfem_amg_assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free,

@@ -108,9 +108,77 @@ class _FrozenSolverBase:
         self._amg = None
         if precond == "amg":
             self._amg = _AmgDevice(amg_host(model), dev, self.phys)
+        self._scale = None            # set_element_scale: an ElementWeights (the operator is K(w)), or None
 
     def __del__(self):
         _lib.destroy_handle(self, "hfem_cg_destroy")
+
+    def set_element_scale(self, scale: Optional[torch.Tensor]):
+        """Solve with ``K(w) = sum_e w_e K_e`` instead of ``K``: ``scale`` is an fp64 ``[ne]`` device tensor of per-element
+        stiffness factors in the model's element order (two materials; the SIMP weights of a density design), finite and
+        ``> 0`` (``ValueError`` otherwise).  ``None`` restores the homogeneous solve exactly: the same calls as before this
+        method existed.  The values are copied; call again after changing them.
+
+        With a scale set the matrix-vector product, the block-Jacobi blocks and the AMG fine level are the scaled sibling
+        kernels (``csrc/topopt.hip``, ``amg_assemble_scaled_kernel``), and ``solve()`` forms its first residual as
+        ``g0 = g_zero + K(w) u_0`` with one standalone scaled apply instead of the energy launch at ``u_0``.  The Dirichlet
+        lift of the homogeneous energy launch would be wrong for ``K(w)``, so a scale requires ``u_fixed == 0``
+        (``ValueError`` at the next refresh otherwise).  The energy losses themselves stay homogeneous: ``loss_fn(model)`` and
+        the stress recovery do not see the scale."""
+        if scale is None:
+            self.bind_element_weights(None)
+            return
+        ne = int(self.model.connectivity.shape[0])
+        scale = _lib.require_gpu_tensor(scale.detach(), "scale", F64)
+        if tuple(scale.shape) != (ne,):
+            raise ValueError(f"set_element_scale: scale must have shape [{ne}] (one factor per element), got {tuple(scale.shape)}")
+        if not bool((torch.isfinite(scale) & (scale > 0)).all()):
+            raise ValueError("set_element_scale: every factor must be finite and > 0")
+        weights = self._scale if self._scale is not None else ElementWeights(self.plan, ne, self.device)
+        weights.set(scale)
+        self.bind_element_weights(weights)
+
+    def bind_element_weights(self, weights):
+        """Make ``weights`` (an ``ElementWeights`` on this solver's plan, or None) the operator's weights: the one place that
+        keeps the invalidation rule.  A switch between K and K(w) drops the captured iterations (they hold the other
+        operator's kernels); any binding makes the next ``solve`` / ``apply`` / ``relinearise`` refresh."""
+        if weights is not None and weights.plan is not self.plan:
+            raise ValueError("bind_element_weights: the weights were built on another tile plan")
+        if (weights is None) != (self._scale is None):
+            self._graph = None
+        self._scale = weights
+        self._key = None
+
+    def relinearise(self):
+        """New values in the bound weight buffers: rebuild the blocks / the AMG values only (one setup), or do the whole
+        ``refresh`` when the coordinates, ``u_fixed`` or the binding changed since the last one."""
+        if self._key is None or self._key != self._state_key():
+            self.refresh()
+        else:
+            self._setup_operator(self._tables[0])
+
+    def element_energy_inputs(self):
+        """What ``ElementWeights.energy`` reads of the last refresh and solve: (fp64 free and fixed coordinate rows, the fp64
+        displacement of the last ``solve``, the material table, W, physical convention?)."""
+        return self._xf, self._xfix, self._u, self._tables[0], float(self.loss_fn._W), self.phys
+
+    def _setup_operator(self, mat):
+        """Bind the operator of this refresh: K, or K(w) once ``set_element_scale`` has given weights."""
+        lf, dev = self.loss_fn, self.device
+        xfix = ptr(self._xfix) if self._xfix.numel() else None
+        pre = 1 if self.precond == "block_jacobi" else 0
+        if self._scale is None:
+            check(_lib.lib().hfem_cg_setup(self._h, ptr(self._xf), xfix, mat, float(lf._W), pre, ptr(self.diag),
+                                           stream_ptr(dev)), "hfem_cg_setup")
+            if self._amg is not None:
+                self._amg.setup(self._xf, self._xfix, mat, float(lf._W))
+            return
+        if self._ufix.numel() and bool((self._ufix != 0).any()):
+            raise ValueError("set_element_scale needs u_fixed == 0: the Dirichlet lift comes from the homogeneous energy launch")
+        check(_lib.lib().hfem_cg_setup_scaled(self._h, ptr(self._xf), xfix, mat, float(lf._W), ptr(self._scale.w_slot), pre,
+                                              ptr(self.diag), stream_ptr(dev)), "hfem_cg_setup_scaled")
+        if self._amg is not None:
+            self._amg.setup_scaled(self._xf, self._xfix, mat, float(lf._W), self._scale.w_elem)
 
     # ---- what the right-hand side and K depend on
     def _state_key(self):
@@ -128,11 +196,7 @@ class _FrozenSolverBase:
             self._xfix.copy_(m.node_coords_fixed.detach())
             self._ufix.copy_(m.u_fixed_rows().detach())
         mat = (C.c_double * 4)(*lf._mat)
-        check(_lib.lib().hfem_cg_setup(self._h, ptr(self._xf), ptr(self._xfix) if self._xfix.numel() else None, mat,
-                                       float(lf._W), 1 if self.precond == "block_jacobi" else 0, ptr(self.diag),
-                                       stream_ptr(dev)), "hfem_cg_setup")
-        if self._amg is not None:
-            self._amg.setup(self._xf, self._xfix, mat, float(lf._W))
+        self._setup_operator(mat)
         # force tables exactly as EnergyLoss2D builds them (the coordinates are frozen: a position-dependent traction is a
         # constant table here)
         flags = HFEM_FLAG_NO_GX | (HFEM_FLAG_PHYSICAL_GRAD if self.phys else 0)
@@ -170,8 +234,14 @@ class _FrozenSolverBase:
             self.refresh()
         with torch.no_grad():
             self._u.copy_(m.u_free.detach())
-            self._gradient(self._u, self._g0)
-            self._gradient(self._zero, self._gz)
+            if self._scale is None:
+                self._gradient(self._u, self._g0)
+                self._gradient(self._zero, self._gz)
+            else:                                            # g0 = g_zero + K(w) u_0: the energy launch is homogeneous
+                self._gradient(self._zero, self._gz)
+                check(_lib.lib().hfem_cg_apply(self._h, ptr(self._u), ptr(self._g0), ptr(self._loss), stream_ptr(self.device)),
+                      "hfem_cg_apply")
+                self._g0.add_(self._gz)
             self._start(self.rtol, self.atol, self.max_iter)
             st = self._read_status()
             while not st[ST_HALTED] and st[ST_ITER] < self.max_iter:
@@ -407,6 +477,25 @@ class _AmgDevice:
         self.seconds = time.perf_counter() - t0
         self.setups += 1
 
+    def assemble_scaled(self, xf, xfix, mat, W, w_elem):
+        """Level-0 A values = K(w)_ff = sum_e w_e K_e,ff; ``w_elem`` fp64 ``[ne]`` by element id."""
+        check(_lib.lib().hfem_amg_assemble_scaled(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W, ptr(w_elem),
+                                                  stream_ptr(self.device)), "hfem_amg_assemble_scaled")
+
+    def setup_scaled(self, xf, xfix, mat, W, w_elem):
+        """``setup`` on the assembled ``K(w)_ff`` (SPD for w > 0: the coarse inverse as in ``setup``)."""
+        import time
+        torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        check(_lib.lib().hfem_amg_setup_scaled(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, mat, W, ptr(w_elem),
+                                               ptr(self.coarse), stream_ptr(self.device)), "hfem_amg_setup_scaled")
+        inv = torch.linalg.inv(self.coarse)
+        self.coarse_inv.copy_(0.5 * (inv + inv.T))
+        check(_lib.lib().hfem_amg_set_coarse(self._h, ptr(self.coarse_inv)), "hfem_amg_set_coarse")
+        torch.cuda.synchronize(self.device)
+        self.seconds = time.perf_counter() - t0
+        self.setups += 1
+
     def assemble_hyper(self, xf, xfix, u, ufix, lame, W):
         """Level-0 A values = the Neo-Hookean tangent K_T,ff at the coordinates and the displacement rows."""
         check(_lib.lib().hfem_amg_assemble_hyper(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, ptr(u),
@@ -457,10 +546,74 @@ class _AmgDevice:
                     numeric_setup_seconds=self.seconds, numeric_setups=self.setups)
 
 
-def assemble_stiffness(model, loss_fn) -> torch.Tensor:
+class ElementWeights:
+    """Per-element weights of ``K(w)`` on one tile plan (``csrc/topopt.hip``, ``hfem_topt``): ``w_elem`` fp64 ``[ne]`` by
+    element id (what the AMG assembly reads) and ``w_slot``, the same weights once per slot of the plan in the order of its
+    element records (what the scaled apply and diag kernels read; entries without an element 0).  Both buffers are
+    allocated once, so the pointer a solver bound stays valid across ``set`` / ``simp``.  ``centroids`` / ``volumes`` (fp64
+    ``[ne, 2]`` / ``[ne]``, any device) and ``radius > 0`` add the linear density filter (``filter``)."""
+
+    def __init__(self, plan, ne, device, centroids=None, volumes=None, radius=0.0):
+        self.plan, self.ne, self.device = plan, int(ne), device
+        h = C.c_void_p()
+        c = v = None
+        if volumes is not None:                                  # the volume constraint of ``oc`` needs them, filter or not
+            v = np.ascontiguousarray(volumes.detach().cpu().numpy(), dtype=np.float64)
+        if radius > 0:
+            c = np.ascontiguousarray(centroids.detach().cpu().numpy(), dtype=np.float64)
+            if c.shape != (self.ne, 2) or v is None or v.shape != (self.ne,):
+                raise ValueError("ElementWeights: centroids must be [ne, 2] and volumes [ne]")
+        check(_lib.lib().hfem_topt_create(plan.handle, None if c is None else c.ctypes.data, None if v is None else v.ctypes.data,
+                                          self.ne, float(radius), C.byref(h)), "hfem_topt_create")
+        self._h = h
+        n = int(_lib.lib().hfem_topt_slots(h))
+        self.w_elem = torch.ones(self.ne, dtype=F64, device=device)
+        self.w_slot = torch.zeros(n, dtype=F64, device=device)
+
+    def __del__(self):
+        _lib.destroy_handle(self, "hfem_topt_destroy")
+
+    def simp(self, rho, penal, e_min):
+        """``w_e = e_min + rho_e^penal (1 - e_min)`` into both buffers (one launch)."""
+        rho = _lib.require_gpu_tensor(rho, "rho", F64)
+        check(_lib.lib().hfem_topt_weights(self._h, ptr(rho), float(penal), float(e_min), ptr(self.w_elem), ptr(self.w_slot),
+                                           stream_ptr(self.device)), "hfem_topt_weights")
+
+    def set(self, w):
+        """The weights themselves (``penal = 1``, ``e_min = 0`` passes them through bit for bit)."""
+        self.simp(w, 1.0, 0.0)
+
+    def filter(self, x, transpose=False):
+        """``F x`` or ``F^T x`` of the density filter (the identity without a radius); fp64 ``[ne]``."""
+        x = _lib.require_gpu_tensor(x, "x", F64)
+        out = torch.empty_like(x)
+        check(_lib.lib().hfem_topt_filter(self._h, ptr(x), ptr(out), 1 if transpose else 0, stream_ptr(self.device)),
+              "hfem_topt_filter")
+        return out
+
+    def energy(self, xf, xfix, u, mat, W, phys, rho_f, penal, e_min, ce, dc):
+        """``ce[e] = u_e^T K_e u_e`` (unscaled) and ``dc[e] = -penal rho_f[e]^(penal-1) (1 - e_min) ce[e]``: one launch."""
+        check(_lib.lib().hfem_topt_energy(self._h, ptr(xf), ptr(xfix) if xfix.numel() else None, ptr(u), mat, float(W),
+                                          HFEM_FLAG_PHYSICAL_GRAD if phys else 0, ptr(rho_f), float(penal), float(e_min), ptr(ce),
+                                          ptr(dc), stream_ptr(self.device)), "hfem_topt_energy")
+
+    def oc(self, rho, dc, dv, vol_target, move, n_bisect, rho_new, rho_f_new):
+        """The optimality-criteria update (launches only: capturable)."""
+        check(_lib.lib().hfem_topt_oc(self._h, ptr(rho), ptr(dc), ptr(dv), float(vol_target), float(move), int(n_bisect),
+                                      ptr(rho_new), ptr(rho_f_new), stream_ptr(self.device)), "hfem_topt_oc")
+
+    def status(self):
+        """``hfem_topt_status`` of the last update: dict of lambda_lo, lambda_hi, volume (at lambda_hi), steps, feasible."""
+        st = (C.c_double * 16)()
+        check(_lib.lib().hfem_topt_status(self._h, st, stream_ptr(self.device)), "hfem_topt_status")
+        return dict(lambda_lo=st[0], lambda_hi=st[1], volume=st[2], steps=int(st[3]), feasible=bool(st[4]))
+
+
+def assemble_stiffness(model, loss_fn, elem_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K_ff of the model at its current coordinates: fp64 ``torch.sparse_bsr_tensor`` with 2x2 blocks over the free u rows in
     storage order (Dirichlet columns dropped), from the AMG assembly kernel (one thread per row, deterministic).  The gradient
-    convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 and QUAD4 models."""
+    convention follows ``loss_fn`` / ``model`` as the energy does.  TRI3 and QUAD4 models.  ``elem_scale`` (fp64 ``[ne]``
+    device tensor, the model's element order): ``K(w)_ff = sum_e w_e K_e,ff`` instead."""
     require_linear(loss_fn, "assemble_stiffness")
     _lib.require_gpu_tensor(model.node_coords_free, "node_coords_free", dtype=None)
     dev = model.u_free.device
@@ -469,7 +622,13 @@ def assemble_stiffness(model, loss_fn) -> torch.Tensor:
     a = _AmgDevice(host, dev, phys)
     xf = model.node_coords_free.detach().to(F64).contiguous()
     xfix = model.node_coords_fixed.detach().to(F64).contiguous()
-    a.assemble(xf, xfix, (C.c_double * 4)(*loss_fn._mat), float(loss_fn._W))
+    if elem_scale is None:
+        a.assemble(xf, xfix, (C.c_double * 4)(*loss_fn._mat), float(loss_fn._W))
+    else:
+        w = _lib.require_gpu_tensor(elem_scale.detach(), "elem_scale", F64)
+        if tuple(w.shape) != (int(model.connectivity.shape[0]),):
+            raise ValueError("assemble_stiffness: elem_scale must hold one factor per element")
+        a.assemble_scaled(xf, xfix, (C.c_double * 4)(*loss_fn._mat), float(loss_fn._W), w)
     vals = a.values(0, 0).view(-1, 2, 2).clone()
     n = host.levels[0][0]
     i64 = dict(dtype=torch.int64, device=dev)

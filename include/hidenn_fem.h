@@ -1121,6 +1121,78 @@ int hfem_harm_start(hfem_harm *harm, hfem_amg *amg, const double *diag, const do
 int hfem_harm_iterate(hfem_harm *harm, hfem_amg *amg, double *x, int64_t len, int32_t n_iter, void *stream);
 int hfem_harm_status(hfem_harm *harm, double *status_host, void *stream);
 
+/* ------------------------------------------------------------------ element-scaled stiffness K(w) = sum_e w_e K_e
+ * (csrc/topopt.hip, csrc/cg.hip, csrc/tri3_amg.hip; hidenn_fem_amd/solve.py set_element_scale).  No reference
+ * counterpart.  One weight per element -- two materials, or the SIMP interpolation of a density design -- through the
+ * matrix-free PCG solve, the block-Jacobi blocks and the AMG fine level.
+ *   hfem_cg_setup_scaled      hfem_cg_setup for K(w), for a solver of hfem_cg_create (a solver of hfem_cg_create_hyper is
+ *                             refused).  w_slot (device, fp64): one weight record per slot of the solver's plan, n_tiles x
+ *                             elem_stride records addressed as the plan's elem_pack: a paired TRI3 plan: two doubles {w_A, w_B};
+ *                             a QUAD4 plan: one double (hfem_topt_weights writes it; hfem_topt_slots gives its length in
+ *                             doubles).  The record of a slot without an element, and w_B of a slot with one element, are never
+ *                             used.  w_slot is bound as a POINTER: it must stay allocated; writing new weights into the same
+ *                             buffer and calling this again re-linearises (the blocks are rebuilt), and a captured
+ *                             hfem_cg_iterate stays valid, as after hfem_cg_setup_hyper.  hfem_cg_start / iterate / status /
+ *                             apply / start_amg / iterate_amg then work on K(w) unchanged.  A later hfem_cg_setup or
+ *                             hfem_cg_setup_shifted returns the solver to the unscaled operator.  NULL w_slot: argument error.
+ *   hfem_amg_assemble_scaled  hfem_amg_assemble / hfem_amg_setup with w_elem[ne] (device, fp64, by global element id: the row
+ *   hfem_amg_setup_scaled     order of the connectivity hfem_amg_host_create_ex was given) multiplied into every element's
+ *                             blocks.  One thread per row, no atomics: bit-reproducible.  The hierarchy's patterns and
+ *                             aggregates are the mesh's and are not rebuilt, only the values.
+ * The design handle maps a density design onto those weights and holds the density filter:
+ *   create    plan: the solver's (a paired TRI3 plan or a QUAD4 plan, on a device); its elem_gid / elem_gid_b are uploaded.
+ *             centroids[ne][2], volumes[ne] (HOST, fp64): the filter's geometry, read when radius > 0.  The filter's CSR is
+ *             built here on the host with a uniform grid: per row e every j with H_ej = radius - |x_e - x_j| > 0, columns
+ *             ascending, and s_e = sum_j H_ej v_j.  radius <= 0: the identity filter (centroids and volumes may be NULL).  More
+ *             than 2^31 - 1 entries: argument error, the message gives the count.
+ *   slots     doubles of a w_slot buffer of this plan (n_tiles x elem_stride, x 2 for a paired TRI3 plan); < 0 on NULL.
+ *   weights   w_e = e_min + rho_f[e]^penal (1 - e_min) (penal >= 1, 0 <= e_min < 1; penal = 1, e_min = 0 passes rho_f
+ *             through bit for bit): once by element id into w_elem[ne], once per slot into w_slot (entries without an element
+ *             0).  Either output may be NULL.  One launch.
+ *   filter    out = F in (transpose = 0: out_e = sum_j H_ej v_j in_j / s_e) or out = F^T in (transpose = 1:
+ *             out_j = v_j sum_e H_je in_e / s_e); one thread per element gathers its row: bit-reproducible.  out != in.
+ *   energy    one launch on the tile plan (the apply's gather and slot loop, no accumulation): at each element's home slot
+ *             ce_out[e] = u_e^T K_e u_e (UNSCALED: twice the element's strain energy; mat, W, flags as hfem_cg_setup /
+ *             hfem_cg_create) and, when dc_out is given, dc_out[e] = -penal rho_f[e]^(penal-1) (1 - e_min) ce_out[e].  Every
+ *             element is written exactly once; fixed u rows read as 0.
+ *   oc        the optimality-criteria update, launches only (capturable, no host synchronisation):
+ *               rho_new,e(lambda) = clamp(rho_e sqrt(r_e / lambda), max(0, rho_e - move), min(1, rho_e + move)),
+ *               r_e = max(0, -dc_e / dv_e),
+ *             lambda by bisection so that V(lambda) = sum_e v_e (F rho_new(lambda))_e <= vol_target.  The bracket, the
+ *             midpoint and every decision live in a device status record.  The upper end starts at R = max_e r_e (there no
+ *             entry grows, so the update is feasible whenever the current design is); the first launch evaluates V there, and
+ *             while it is not feasible the bracket moves up (lambda_lo = lambda_hi, lambda_hi x 4), one launch each.  Then one
+ *             launch per halving at m = (lambda_lo + lambda_hi) / 2: V(m) <= vol_target moves lambda_hi, else lambda_lo; a
+ *             bracket one ulp wide is left alone.  n_bisect + 1 step launches in all, each with the filter gather evaluating
+ *             the neighbours' updates on the fly and V summed in block order by a ticket workgroup.  A last launch writes
+ *             rho_new = the update at lambda_hi (the feasible end) and rho_f_new = F rho_new.  Needs a handle created with
+ *             volumes.  rho_new, rho_f_new and rho must be three different buffers.
+ *   status    synchronises the stream; status_host[16] = {lambda_lo, lambda_hi, V(lambda_hi), step launches that evaluated V,
+ *             feasible (1: V(lambda_hi) <= vol_target was seen), phase (0 moving up, 1 halving), vol_target, R, V(lambda_lo),
+ *             0 ...} of the last hfem_topt_oc.  V at an end of the bracket that was never evaluated is NaN: V(lambda_lo) while
+ *             lambda_lo = 0, and V(lambda_hi) when the last launch moved the bracket up without reaching a feasible end
+ *             (only with feasible = 0).
+ * Every entry point checks its arguments before it touches a device (negative code, message through hfem_last_error).       */
+typedef struct hfem_topt hfem_topt;
+int hfem_cg_setup_scaled(hfem_cg *cg, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                         const double *w_slot, int32_t precond, double *diag_out, void *stream);
+int hfem_amg_assemble_scaled(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                             const double *w_elem, void *stream);
+int hfem_amg_setup_scaled(hfem_amg *amg, const double *x_free, const double *x_fixed, const double mat[4], double W,
+                          const double *w_elem, double *coarse_out, void *stream);
+int hfem_topt_create(hfem_plan *plan, const double *centroids, const double *volumes, int64_t ne, double radius, hfem_topt **out);
+int hfem_topt_destroy(hfem_topt *topt);
+int64_t hfem_topt_slots(const hfem_topt *topt);
+int hfem_topt_weights(hfem_topt *topt, const double *rho_f, double penal, double e_min, double *w_elem, double *w_slot,
+                      void *stream);
+int hfem_topt_filter(hfem_topt *topt, const double *in, double *out, int32_t transpose, void *stream);
+int hfem_topt_energy(hfem_topt *topt, const double *x_free, const double *x_fixed, const double *u_free, const double mat[4],
+                     double W, int32_t flags, const double *rho_f, double penal, double e_min, double *ce_out, double *dc_out,
+                     void *stream);
+int hfem_topt_oc(hfem_topt *topt, const double *rho, const double *dc, const double *dv, double vol_target, double move,
+                 int32_t n_bisect, double *rho_new, double *rho_f_new, void *stream);
+int hfem_topt_status(hfem_topt *topt, double *status_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

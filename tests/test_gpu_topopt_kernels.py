@@ -1,0 +1,372 @@
+"""The kernels of element-scaled stiffness and SIMP topology optimisation one by one, against
+tests/topopt_reference.py (numpy / scipy, K_e from ``buckling_reference.element_points``).
+
+Operator: every tile shape of the plain apply's dispatch (``TRI3_SHAPES`` / ``QUAD4_SHAPES`` of
+tests/test_gpu_dynamics_kernels.py, the branch asserted as that file does), both conventions, weights log-uniform in
+[1e-9, 1].  Tolerances are the project's for the unscaled and shifted operators: apply, blocks and assembled K(w) 1e-12 x max,
+``p^T K(w) p`` 1e-12 relative.  Poison: every padded, skipped or hasB = 0 entry of ``w_slot`` overwritten by NaN must change
+nothing -- what fails when the slot indexing is off by a row or a column.
+
+Weights: ``pow`` and numpy's ``**`` are each within 1 ulp and the device forms ``fma(rho^p, 1 - e_min, e_min)`` where numpy
+rounds twice: 4 ulp of w.  Filter: 1e-13 x max against the brute-force matrix.  OC: ``rho_new`` against the formula at the
+device's own ``lambda_hi`` 1e-14 entrywise; volumes recomputed in numpy with the worst-case rounding allowance of the sums,
+``4 ne 2^-53`` relative."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import test_gpu_dynamics_kernels as DK
+import topopt_reference as TR
+from test_gpu_dynamics_kernels import QUAD4_SHAPES, TRI3_SHAPES
+
+pytestmark = pytest.mark.gpu
+F64 = torch.float64
+CONVS = ["reference", "physical"]
+ALL_SHAPES = [("tri3", s) for s in TRI3_SHAPES] + [("quad4", s) for s in QUAD4_SHAPES]
+IDS = [f"{k}-{s}" for k, s in ALL_SHAPES]
+
+
+def _dev():
+    return DK._dev()
+
+
+def _numpy_mesh(m):
+    X = m.coords.detach().double().cpu().numpy()
+    conn = m.connectivity.cpu().numpy().astype(np.int64)
+    return X, conn, TR.node_rows(m._idx_ufree.cpu().numpy(), X.shape[0])
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, shape, conv):
+    """(model, loss, plan, K_e, element dofs, weights) of one shape and convention: built once, never modified."""
+    m, lf, plan = DK._tri3_model(shape, conv) if kind == "tri3" else DK._quad4_model(shape, conv)
+    X, conn, node_row = _numpy_mesh(m)
+    Ke = TR.element_matrices(X, conn, lf._mat, lf._W, conv)
+    dofs = TR.element_dofs(conn, node_row)
+    w = 10.0 ** np.random.default_rng(17).uniform(-9.0, 0.0, conn.shape[0])
+    return m, lf, plan, Ke, dofs, w
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_cases():
+    yield
+    _case.cache_clear()
+
+
+def _solver(m, lf, **kw):
+    from hidenn_fem_amd.solve import FrozenMeshSolver, Quad4FrozenMeshSolver
+    cls = Quad4FrozenMeshSolver if getattr(m, "nodes_per_element", 3) == 4 else FrozenMeshSolver
+    kw.setdefault("precond", "block_jacobi")
+    return cls(m, lf, **kw)
+
+
+def _slot_ids(plan, n_slots):
+    """(elem_gid, elem_gid_b or None) of the plan's slot records, n_tiles x elem_stride of them."""
+    ga = plan.export("elem_gid")[:n_slots]
+    gb = plan.export("elem_gid_b")[:n_slots] if plan.stats["paired"] else None
+    return ga, gb
+
+
+@pytest.mark.parametrize("conv", CONVS)
+@pytest.mark.parametrize("kind,shape", ALL_SHAPES, ids=IDS)
+def test_scaled_apply_blocks_and_assembly_against_the_sparse_operator(kind, shape, conv):
+    from hidenn_fem_amd.solve import assemble_stiffness
+    m, lf, plan, Ke, dofs, w = _case(kind, shape, conv)
+    s = _solver(m, lf)
+    assert s.plan is plan                                    # the branch asserted on `plan` is the one that runs
+    n = s.n_u
+    p = torch.randn(n, 2, dtype=F64, generator=torch.Generator().manual_seed(5)).to(_dev())
+    pn = p.cpu().numpy().reshape(-1)
+    qk, pqk = s.apply(p)                                     # the unscaled operator, before any scale
+    wd = torch.from_numpy(w).to(_dev())
+    A = TR.scaled_stiffness(Ke, dofs, w, 2 * n)
+    want = A @ pn
+    s.set_element_scale(wd)
+    q, pq = s.apply(p)
+    err = np.abs(q.cpu().numpy().reshape(-1) - want).max() / np.abs(want).max()
+    err_pq = abs(pq.item() - pn @ want) / abs(pn @ want)
+    d0, up, lo = A.diagonal(0), A.diagonal(1), A.diagonal(-1)
+    wb = np.stack([d0[0::2], 0.5 * (up[0::2] + lo[0::2]), d0[1::2]], axis=1)
+    blocks = s.diag.cpu().numpy()
+    err_b = np.abs(blocks - wb).max() / np.abs(wb).max()
+    Ad, Ad2 = assemble_stiffness(m, lf, elem_scale=wd), assemble_stiffness(m, lf, elem_scale=wd)
+    err_a = abs(DK._scipy(Ad) - A).max() / abs(A).max()
+    print(f"{kind} {shape} {conv}: apply {err:.2e} p^T K(w) p {err_pq:.2e} blocks {err_b:.2e} assembled {err_a:.2e}")
+    assert err <= 1e-12
+    assert err_pq <= 1e-12
+    assert err_b <= 1e-12
+    assert err_a <= 1e-12
+    assert torch.equal(Ad.values(), Ad2.values())            # one thread per row, no atomics: bit-identical
+    # poison: every weight entry no element stands behind
+    ws = s._scale.w_slot
+    n_slots = ws.numel() // (2 if kind == "tri3" else 1)
+    ga, gb = _slot_ids(plan, n_slots)
+    dead = torch.from_numpy(ga < 0).to(_dev())
+    if kind == "tri3":
+        v = ws.view(n_slots, 2)
+        assert (gb[ga < 0] < 0).all()
+        v[dead] = float("nan")
+        v[:, 1][torch.from_numpy(gb < 0).to(_dev())] = float("nan")
+    else:
+        ws[dead] = float("nan")
+    assert torch.isnan(ws).any()
+    q2, pq2 = s.apply(p)
+    assert torch.isfinite(q2).all() and torch.isfinite(pq2)
+    assert (q2 - q).abs().max().item() <= 1e-12 * q.abs().max().item()
+    assert abs(pq2.item() - pq.item()) <= 1e-12 * abs(pq.item())
+    s._setup_operator(s._tables[0])                          # the blocks again, from the poisoned records
+    assert torch.isfinite(s.diag).all()
+    assert np.abs(s.diag.cpu().numpy() - wb).max() <= 1e-12 * np.abs(wb).max()
+    # w = 1 is the unscaled operator
+    s.set_element_scale(torch.ones_like(wd))
+    q1, pq1 = s.apply(p)
+    assert (q1 - qk).abs().max().item() <= 1e-12 * qk.abs().max().item()
+    assert abs(pq1.item() - pqk.item()) <= 1e-12 * abs(pqk.item())
+    # and None returns to the plain kernels
+    s.set_element_scale(None)
+    q0, _ = s.apply(p)
+    assert (q0 - qk).abs().max().item() <= 1e-12 * qk.abs().max().item()
+
+
+@pytest.mark.parametrize("kind,shape", [("tri3", "b"), ("quad4", "S600")])
+def test_a_later_plain_setup_returns_the_solver_to_k_and_a_hyper_solver_is_refused(kind, shape):
+    from hidenn_fem_amd import _lib
+    from hidenn_fem_amd.plan import model_plan
+    m, lf, plan, Ke, dofs, w = _case(kind, shape, "physical")
+    s = _solver(m, lf)
+    n = s.n_u
+    p = torch.randn(n, 2, dtype=F64, generator=torch.Generator().manual_seed(9)).to(_dev())
+    pn = p.cpu().numpy().reshape(-1)
+    s.set_element_scale(torch.from_numpy(w).to(_dev()))
+    q, _ = s.apply(p)
+    want = TR.scaled_stiffness(Ke, dofs, w, 2 * n) @ pn
+    assert np.abs(q.cpu().numpy().reshape(-1) - want).max() <= 1e-12 * np.abs(want).max()
+    lib, st = _lib.lib(), _lib.stream_ptr(_dev())
+    mat, W = (C.c_double * 4)(*lf._mat), float(lf._W)
+    xf, xfix = s._xf, s._xfix
+    xfix_p = xfix.data_ptr() if xfix.numel() else None
+    _lib.check(lib.hfem_cg_setup(s._h, xf.data_ptr(), xfix_p, mat, W, 1, s.diag.data_ptr(), st), "hfem_cg_setup")
+    q = torch.empty_like(p)
+    pq = torch.empty((), dtype=F64, device=_dev())
+    _lib.check(lib.hfem_cg_apply(s._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), st), "hfem_cg_apply")
+    K = TR.scaled_stiffness(Ke, dofs, np.ones_like(w), 2 * n)
+    want = K @ pn
+    assert np.abs(q.cpu().numpy().reshape(-1) - want).max() <= 1e-12 * np.abs(want).max()
+    d0 = K.diagonal(0)
+    assert np.abs(s.diag.cpu().numpy()[:, 0] - d0[0::2]).max() <= 1e-12 * np.abs(d0).max()
+    # a null w_slot is an argument error; a solver of hfem_cg_create_hyper is refused, with a message
+    assert lib.hfem_cg_setup_scaled(s._h, xf.data_ptr(), xfix_p, mat, W, None, 1, None, st) < 0
+    assert b"w_slot must be given" in lib.hfem_last_error()
+    hp = model_plan(m, lf.tile_elems, paired=False) if kind == "tri3" else plan
+    h = C.c_void_p()
+    _lib.check(lib.hfem_cg_create_hyper(hp.handle, n, C.byref(h)), "hfem_cg_create_hyper")
+    try:
+        rc = lib.hfem_cg_setup_scaled(h, xf.data_ptr(), xfix_p, mat, W, s.diag.data_ptr(), 1, None, st)
+        assert rc < 0 and b"hfem_cg_create_hyper" in lib.hfem_last_error()
+    finally:
+        lib.hfem_cg_destroy(h)
+
+
+@pytest.mark.parametrize("kind,shape", ALL_SHAPES, ids=IDS)
+def test_weights_by_element_and_by_slot_match_the_formula(kind, shape):
+    from hidenn_fem_amd.solve import ElementWeights
+    m, lf, plan, Ke, dofs, w = _case(kind, shape, "physical")
+    ne = len(w)
+    ew = ElementWeights(plan, ne, _dev())
+    rho = np.random.default_rng(2).uniform(0.0, 1.0, ne)
+    rho[:3] = (0.0, 1.0, 0.5)
+    ew.w_elem.fill_(float("nan"))
+    ew.w_slot.fill_(float("nan"))
+    ew.simp(torch.from_numpy(rho).to(_dev()), 3.0, 1e-9)
+    want = TR.simp(rho, 3.0, 1e-9)
+    got = ew.w_elem.cpu().numpy()
+    assert (np.abs(got - want) <= 4 * np.spacing(want)).all()
+    paired = kind == "tri3"
+    n_slots = ew.w_slot.numel() // (2 if paired else 1)
+    ga, gb = _slot_ids(plan, n_slots)
+    ws = ew.w_slot.cpu().numpy().reshape(n_slots, 2 if paired else 1)
+    for col, g in ((0, ga),) + (((1, gb),) if paired else ()):
+        assert np.array_equal(ws[g >= 0, col], got[g[g >= 0]])          # the same function of the same input: the same bits
+        assert (ws[g < 0, col] == 0.0).all()                             # padded or absent entries
+    # every element stands in at least one slot
+    seen = np.zeros(ne, bool)
+    seen[ga[ga >= 0]] = True
+    if paired:
+        seen[gb[gb >= 0]] = True
+    assert seen.all()
+    ew.set(torch.from_numpy(rho + 0.5).to(_dev()))           # penal = 1, e_min = 0: bit for bit
+    assert np.array_equal(ew.w_elem.cpu().numpy(), rho + 0.5)
+
+
+@pytest.mark.parametrize("conv", CONVS)
+@pytest.mark.parametrize("kind,shape", ALL_SHAPES, ids=IDS)
+def test_element_energies_and_sensitivities(kind, shape, conv):
+    from hidenn_fem_amd.solve import ElementWeights
+    m, lf, plan, Ke, dofs, w = _case(kind, shape, conv)
+    s = _solver(m, lf)
+    s.refresh()
+    ne, n = len(w), s.n_u
+    ew = ElementWeights(plan, ne, _dev())
+    u = torch.randn(n, 2, dtype=F64, generator=torch.Generator().manual_seed(3)).to(_dev())
+    rho = np.random.default_rng(4).uniform(0.05, 1.0, ne)
+    ce = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+    dc = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+    penal, e_min = 3.0, 1e-9
+    ew.energy(s._xf, s._xfix, u, s._tables[0], lf._W, s.phys, torch.from_numpy(rho).to(_dev()), penal, e_min, ce, dc)
+    assert torch.isfinite(ce).all() and torch.isfinite(dc).all()          # every element written
+    want = TR.element_energies(Ke, dofs, u.cpu().numpy().reshape(-1))
+    want_dc = -penal * rho ** (penal - 1.0) * (1.0 - e_min) * want
+    err = np.abs(ce.cpu().numpy() - want).max() / np.abs(want).max()
+    err_dc = np.abs(dc.cpu().numpy() - want_dc).max() / np.abs(want_dc).max()
+    print(f"{kind} {shape} {conv}: ce {err:.2e} dc {err_dc:.2e}")
+    assert err <= 1e-12 and err_dc <= 1e-12
+
+
+# ---------------------------------------------------------------- filter and OC on the plates of tests/test_gpu_modal.py
+@functools.lru_cache(maxsize=None)
+def _plate(kind):
+    import test_gpu_modal as TM
+    from hidenn_fem_amd.topopt import element_geometry
+    m, lf = TM.make_model(kind), TM.make_loss("physical")
+    s = _solver(m, lf)
+    cen, vol = element_geometry(m)
+    X, conn, _ = _numpy_mesh(m)
+    cn, vn = TR.geometry(X, conn)
+    assert np.abs(cen.cpu().numpy() - cn).max() <= 1e-14 and np.abs(vol.cpu().numpy() - vn).max() <= 1e-15
+    return m, lf, s, cen, vol
+
+
+def _weights(kind, radius):
+    from hidenn_fem_amd.solve import ElementWeights
+    m, lf, s, cen, vol = _plate(kind)
+    return ElementWeights(s.plan, vol.numel(), _dev(), centroids=cen, volumes=vol, radius=radius), cen.cpu().numpy(), vol.cpu().numpy()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_plates():
+    yield
+    _plate.cache_clear()
+
+
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_filter_forward_and_transpose_against_the_brute_force_matrix(kind):
+    cen, vol = (t.cpu().numpy() for t in _plate(kind)[3:])
+    ne = len(vol)
+    x = np.random.default_rng(1).standard_normal(ne)
+    xd = torch.from_numpy(x).to(_dev())
+    d = np.sqrt(((cen[:, None, :] - cen[None, :, :]) ** 2).sum(axis=2))
+    dmin = d[d > 0].min()
+    for radius in (1.5 * np.sqrt(vol.mean()), 3.7 * np.sqrt(vol.mean())):
+        ew, _, _ = _weights(kind, radius)
+        F = TR.filter_matrix(cen, vol, radius)
+        for tr, ref in ((False, F @ x), (True, F.T @ x)):
+            got = ew.filter(xd, transpose=tr)
+            assert np.abs(got.cpu().numpy() - ref).max() <= 1e-13 * np.abs(ref).max()
+            assert torch.equal(got, ew.filter(xd, transpose=tr))          # a row gather: bit-identical
+    for radius in (0.5 * dmin, 0.0):                          # below the smallest centroid distance, and none: the identity
+        ew, _, _ = _weights(kind, radius)
+        for tr in (False, True):
+            got = ew.filter(xd, transpose=tr).cpu().numpy()
+            assert np.abs(got - x).max() <= 4 * np.spacing(np.abs(x).max())
+    # spanning the plate: with radius = d_max / eps every H_ej / radius lies in [1 - eps, 1], so the rows are the volume-weighted
+    # mean up to 2 eps max|x - mean| (weights off by eps, normalisation off by eps)
+    eps = 1e-8
+    ew, _, _ = _weights(kind, d.max() / eps)
+    got = ew.filter(xd).cpu().numpy()
+    mean = (vol @ x) / vol.sum()
+    assert np.abs(got - mean).max() <= 2 * eps * np.abs(x - mean).max() + 1e-13 * np.abs(x).max()
+
+
+def _oc_inputs(kind, seed, lo=0.05):
+    cen, vol = (t.cpu().numpy() for t in _plate(kind)[3:])
+    rng = np.random.default_rng(seed)
+    ne = len(vol)
+    rho = rng.uniform(lo, 1.0, ne)
+    dc = -(10.0 ** rng.uniform(-4.0, 2.0, ne))
+    return cen, vol, rho, dc
+
+
+@pytest.mark.parametrize("radius_cells", [1.5, 0.0])
+@pytest.mark.parametrize("frac", [0.4, 0.62])
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_oc_update_against_the_formula_at_the_devices_multiplier(kind, frac, radius_cells):
+    """frac 0.4: the random design (mean 0.52) is infeasible, so the bracket has to move up first; frac 0.62: it is feasible."""
+    cen, vol, rho, dc = _oc_inputs(kind, 6)
+    ne = len(vol)
+    radius = radius_cells * np.sqrt(vol.mean())
+    ew, _, _ = _weights(kind, radius)
+    F = TR.filter_matrix(cen, vol, radius)
+    dv = F.T @ vol
+    target, move, n_bisect = frac * vol.sum(), 0.2, 60
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+    rd, dcd, dvd = t(rho), t(dc), t(dv)
+
+    def run():
+        rn = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+        rf = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+        ew.oc(rd, dcd, dvd, target, move, n_bisect, rn, rf)
+        return rn, rf, ew.status()
+
+    rn, rf, st = run()
+    lo, hi = st["lambda_lo"], st["lambda_hi"]
+    assert st["feasible"] and 0.0 <= lo < hi and st["steps"] <= n_bisect + 1
+    want = TR.oc_value(rho, dc, dv, hi, move)
+    got = rn.cpu().numpy()
+    assert np.abs(got - want).max() <= 1e-14
+    assert (got >= np.maximum(0.0, rho - move)).all() and (got <= np.minimum(1.0, rho + move)).all()
+    assert np.abs(rf.cpu().numpy() - F @ got).max() <= 1e-13
+    tol = 4 * ne * 2.0 ** -53
+    v_hi = vol @ (F @ want)
+    assert v_hi <= target * (1 + tol), (v_hi, target)
+    assert abs(st["volume"] - v_hi) <= tol * target
+    if lo > 0.0:
+        assert vol @ (F @ TR.oc_value(rho, dc, dv, lo, move)) >= target * (1 - tol)
+    # the reference bisection with the device's rule lands on the same bracket up to the rounding of V at a decision
+    _, rlo, rhi, rok = TR.oc_bisect(rho, dc, dv, F, vol, target, move, n_bisect)
+    print(f"{kind} frac {frac} radius {radius_cells}: lambda_hi {hi:.6e} (reference {rhi:.6e}) steps {st['steps']} "
+          f"V/target - 1 {v_hi / target - 1:.1e}")
+    assert rok
+    rn2, rf2, st2 = run()
+    assert torch.equal(rn, rn2) and torch.equal(rf, rf2) and st == st2     # fixed-order sums: bit-identical
+    # one update captured in a graph equals the eager one bitwise
+    gn = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+    gf = torch.full((ne,), float("nan"), dtype=F64, device=_dev())
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        ew.oc(rd, dcd, dvd, target, move, n_bisect, gn, gf)
+    g.replay()
+    st3 = ew.status()
+    torch.cuda.synchronize()
+    assert torch.equal(gn, rn) and torch.equal(gf, rf) and st3 == st
+
+
+@pytest.mark.parametrize("kind", ["tri3", "quad4"])
+def test_oc_update_that_cannot_be_feasible_says_so(kind):
+    """A target below the smallest volume the move limit allows (rho >= 0.3, move 0.2: at least 0.1 sum v): every step launch
+    moves the bracket up, the flag stays 0, V(lambda_hi) was never evaluated (NaN), V(lambda_lo) is the last one evaluated,
+    and the returned design is still the formula's at lambda_hi."""
+    import math
+    cen, vol, rho, dc = _oc_inputs(kind, 9, lo=0.3)
+    ne = len(vol)
+    radius = 1.5 * np.sqrt(vol.mean())
+    ew, _, _ = _weights(kind, radius)
+    F = TR.filter_matrix(cen, vol, radius)
+    dv = F.T @ vol
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+    rn, rf = (torch.full((ne,), float("nan"), dtype=F64, device=_dev()) for _ in range(2))
+    ew.oc(t(rho), t(dc), t(dv), 0.01 * vol.sum(), 0.2, 3, rn, rf)
+    st = ew.status()
+    R = np.maximum(0.0, -dc / dv).max()
+    assert not st["feasible"] and st["steps"] == 4 and math.isnan(st["volume"])
+    assert st["lambda_hi"] == 4.0 * st["lambda_lo"] and abs(st["lambda_hi"] / (R * 4.0 ** 4) - 1.0) <= 1e-14
+    want = TR.oc_value(rho, dc, dv, st["lambda_hi"], 0.2)
+    assert np.abs(rn.cpu().numpy() - want).max() <= 1e-14 and np.abs(rf.cpu().numpy() - F @ want).max() <= 1e-13
+    raw = (C.c_double * 16)()
+    from hidenn_fem_amd import _lib
+    _lib.check(_lib.lib().hfem_topt_status(ew._h, raw, _lib.stream_ptr(_dev())), "hfem_topt_status")
+    v_lo = vol @ (F @ TR.oc_value(rho, dc, dv, st["lambda_lo"], 0.2))
+    assert abs(raw[8] - v_lo) <= 4 * ne * 2.0 ** -53 * v_lo and raw[8] > raw[6] == 0.01 * vol.sum()
