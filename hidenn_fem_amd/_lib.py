@@ -225,6 +225,14 @@ PROTOTYPES = {
     "hfem_topt_energy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _f64, _f64, _vp, _vp, _vp]),
     "hfem_topt_oc": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _f64, _i32, _vp, _vp, _vp]),
     "hfem_topt_status": (C.c_int, [_vp, _vp, _vp]),
+    "hfem_j2_create": (C.c_int, [_vp, _i64, _vp, _f64, C.POINTER(_vp)]),
+    "hfem_j2_destroy": (C.c_int, [_vp]),
+    "hfem_j2_slots": (_i64, [_vp]),
+    "hfem_j2_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp]),
+    "hfem_j2_commit": (C.c_int, [_vp, _vp]),
+    "hfem_j2_get": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "hfem_j2_set": (C.c_int, [_vp, _vp, _vp]),
+    "hfem_cg_setup_j2": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
 
 # float-row twins of the 1D / structured and the TRI3 / QUAD4 mesh-validity entry points (same argument lists; every array pointer

@@ -16,8 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["plan.cpp", "mg.cpp", "tri3_energy.hip", "tri3_stream.hip", "tri3_pair.hip", "tri3_pair_f32.hip", "tri3_pair_lab.hip", "tri3_pair_pipe.hip", "tri3_det.hip", "tri3_eval.hip", "line_rect.hip", "quad4.hip", "optim.hip", "exchange.hip", "peer.hip", "post.hip", "recover.hip", "lbfgs.hip", "cg.hip", "tri3_cg.hip", "quad4_cg.hip", "mesh_guard.hip", "amg.cpp", "tri3_amg.hip", "tri3_hyper.hip", "tri3_hyper_cg.hip", "quad4_hyper.hip", "quad4_hyper_cg.hip", "modal.hip", "dynamics.hip", "buckling.hip", "harmonic.hip", "topopt.hip"]
-HEADERS = ["hfem_common.h", "hfem_amg.h", "hfem_amg_hyper_dev.h", "hfem_cg_dev.h", "hfem_crossing_dev.h", "hfem_device.h", "hfem_hyper_dev.h", "hfem_mesh_dev.h", "hfem_mesh_elem_dev.h", "hfem_plan_dev.h", "hfem_quad4_dev.h", "hfem_quad4_hyper_dev.h", "hfem_recover_hyper_dev.h", "tri3_energy_lab.inc", os.path.join(ROOT, "include", "hidenn_fem.h")]
+SOURCES = ["plan.cpp", "mg.cpp", "tri3_energy.hip", "tri3_stream.hip", "tri3_pair.hip", "tri3_pair_f32.hip", "tri3_pair_lab.hip", "tri3_pair_pipe.hip", "tri3_det.hip", "tri3_eval.hip", "line_rect.hip", "quad4.hip", "optim.hip", "exchange.hip", "peer.hip", "post.hip", "recover.hip", "lbfgs.hip", "cg.hip", "tri3_cg.hip", "quad4_cg.hip", "mesh_guard.hip", "amg.cpp", "tri3_amg.hip", "tri3_hyper.hip", "tri3_hyper_cg.hip", "quad4_hyper.hip", "quad4_hyper_cg.hip", "modal.hip", "dynamics.hip", "buckling.hip", "harmonic.hip", "topopt.hip", "tri3_j2.hip"]
+HEADERS = ["hfem_common.h", "hfem_amg.h", "hfem_amg_hyper_dev.h", "hfem_cg_dev.h", "hfem_crossing_dev.h", "hfem_device.h", "hfem_hyper_dev.h", "hfem_j2_dev.h", "hfem_mesh_dev.h", "hfem_mesh_elem_dev.h", "hfem_plan_dev.h", "hfem_quad4_dev.h", "hfem_quad4_hyper_dev.h", "hfem_recover_hyper_dev.h", "tri3_energy_lab.inc", os.path.join(ROOT, "include", "hidenn_fem.h")]
 OUT = os.path.join(HERE, "libhidenn_hip.so")
 OUT_LAB = os.path.join(HERE, "libhidenn_hip_lab.so")
 ARCH = "gfx950"

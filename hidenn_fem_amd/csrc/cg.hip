@@ -27,6 +27,7 @@
 #include "hfem_amg.h"
 #include "hfem_cg_dev.h"
 #include "hfem_device.h"
+#include "hfem_j2_dev.h"
 #include "hfem_plan_dev.h"
 
 namespace hfem {
@@ -193,6 +194,11 @@ struct hfem_cg {
     // bound by hfem_cg_setup_hyper
     const double2 *u_lin = nullptr, *u_fixed = nullptr;
     hfem::HyperConsts hk{};
+    // bound by hfem_cg_setup_j2 (a handle of hfem_cg_create_hyper on a TRI3 plan): the J2 elastoplastic tangent from stored
+    // records (the kernels of tri3_j2.hip, their own LDS sizes: never more than the Neo-Hookean tangent's)
+    const hfem_j2 *j2 = nullptr;
+    double *j2_tan = nullptr;
+    size_t lds_apply_j2 = 0, lds_diag_j2 = 0;
     bool ready = false;
 };
 
@@ -204,14 +210,16 @@ hfem::CgElemArgs elem_args(const hfem_cg *c, size_t lds, hipStream_t s) {
     A.u_lin_free = c->u_lin; A.u_fixed = c->u_fixed; A.hk = c->hk; A.cq = c->cq;
     A.shifted = c->shifted; A.dm = c->dm;
     A.w_slot = c->w_slot;
+    A.j2 = c->j2; A.j2_tan = c->j2_tan;
     return A;
 }
 
 // the two places that choose the element
 void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, double *st, double *host, double *pq_out,
               hipStream_t s) {
-    const hfem::CgElemArgs A = elem_args(c, c->lds_apply, s);
-    if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    const hfem::CgElemArgs A = elem_args(c, c->j2 ? c->lds_apply_j2 : c->lds_apply, s);
+    if (c->j2) hfem::launch_tri3_j2_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
+    else if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->scaled && c->quad) hfem::launch_quad4_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->scaled) hfem::launch_tri3_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
@@ -220,8 +228,9 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
 }
 
 void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStream_t s) {
-    const hfem::CgElemArgs A = elem_args(c, c->lds_diag, s);
-    if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
+    const hfem::CgElemArgs A = elem_args(c, c->j2 ? c->lds_diag_j2 : c->lds_diag, s);
+    if (c->j2) hfem::launch_tri3_j2_diag(A, diag, c->dinv, precond, c->work, info);
+    else if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->scaled && c->quad) hfem::launch_quad4_scaled_diag(A, diag, c->dinv, precond);
     else if (c->scaled) hfem::launch_tri3_scaled_diag(A, diag, c->dinv, precond);
@@ -491,6 +500,7 @@ static int cg_setup_hyper(hfem_cg *c, const double *x_free, const double *x_fixe
     c->hk.lambda = c_k * lame[0]; c->hk.mu = c_k * lame[1];
     c->hk.W = c->quad ? 1.0 : W;                                      // QUAD4: the 2x2 rule's weights are 1, W is not read
     c->shifted = shifted; c->dm = shifted ? hfem::dyn_mass(c->quad, c_m, lumped != 0) : hfem::DynMass{};
+    c->j2 = nullptr; c->j2_tan = nullptr;
     cg_diag(c, diag_out, precond, info_out, s);
     if (int rc = hfem::launch_status(who)) return rc;
     c->ready = true;
@@ -514,6 +524,40 @@ extern "C" int hfem_cg_setup_hyper_shifted(hfem_cg *c, const double *x_free, con
                    "c_k and c_m must be finite, >= 0 and not both zero");
     return cg_setup_hyper(c, x_free, x_fixed, u_lin_free, u_fixed, lame, W, true, c_k, c_m, lumped, precond, diag_out, info_out,
                           stream, "hfem_cg_setup_hyper_shifted");
+}
+
+// The J2 elastoplastic tangent (tri3_j2.hip) on a handle of hfem_cg_create_hyper: the same plan kind, and no more LDS than
+// the Neo-Hookean tangent (one gathered row array less).  The linearisation launch runs the return map at u_lin_free against
+// j2's committed state and writes the tangent records into `tan`, bound as a POINTER: new records in the same buffer come
+// from another call, and a captured hfem_cg_iterate stays valid (hfem_cg_setup_hyper's rule).  Nothing of the handle changes
+// before every check has passed.
+extern "C" int hfem_cg_setup_j2(hfem_cg *c, hfem_j2 *j2, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                                const double *u_fixed, double *tan, int32_t precond, double *diag_out, double *info_out,
+                                void *stream) {
+    HFEM_ARG_CHECK(c && j2 && x_free && tan && (u_lin_free || c->n_u == 0), "null pointer");
+    HFEM_ARG_CHECK(c->hyper && !c->quad, "the J2 tangent binds a solver of hfem_cg_create_hyper on a TRI3 plan");
+    HFEM_ARG_CHECK(j2->plan == c->plan, "the J2 state handle and the solver were created on different plans");
+    HFEM_ARG_CHECK(precond == 0 || precond == 1, "precond: 0 none, 1 block Jacobi");
+    bool fixed_x = false, fixed_u = false;
+    const hfem::HostPlan &h = c->plan->host;
+    for (size_t i = 0; i + 1 < h.node_src.size(); i += 2) {
+        fixed_x = fixed_x || h.node_src[i] < 0;
+        fixed_u = fixed_u || h.node_src[i + 1] < 0;
+    }
+    HFEM_ARG_CHECK(x_fixed || !fixed_x, "the plan reads fixed coordinate rows: x_fixed must be given");
+    HFEM_ARG_CHECK(u_fixed || !fixed_u, "the plan reads Dirichlet rows: u_fixed must be given");
+    HFEM_ARG_CHECK(u_lin_free || !h.tiles.size(), "u_lin_free must be given");
+    if (int rc = hfem::use_device(c->device)) return rc;
+    c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
+    c->u_lin = (const double2 *)u_lin_free; c->u_fixed = (const double2 *)u_fixed;
+    c->shifted = false; c->dm = hfem::DynMass{};
+    c->j2 = j2; c->j2_tan = tan;
+    c->lds_apply_j2 = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 16 + (c->block / 64 + 2) * 8;
+    c->lds_diag_j2 = (size_t)h.max_nodes * 32 + (size_t)h.max_owned * 24 + (c->block / 64) * 8;
+    cg_diag(c, diag_out, precond, info_out, (hipStream_t)stream);
+    if (int rc = hfem::launch_status("hfem_cg_setup_j2")) return rc;
+    c->ready = true;
+    return 0;
 }
 
 extern "C" int hfem_cg_start(hfem_cg *c, const double *g0, const double *g_zero, double rtol, double atol, int64_t max_iter,

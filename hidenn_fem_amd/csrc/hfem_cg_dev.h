@@ -18,6 +18,8 @@
 #include "hfem_plan_dev.h"
 #include "hfem_quad4_dev.h"
 
+struct hfem_j2;                      // the J2 state handle (hfem_j2_dev.h)
+
 namespace hfem {
 
 __device__ __forceinline__ void publish(const double *st, double *host) {
@@ -331,6 +333,10 @@ struct CgElemArgs {
     // the element-scaled operator K(w) = sum_e w_e K_e (topopt.hip): one weight record per slot of the plan, addressed as
     // elem_pack (a paired TRI3 plan: double2 {w_A, w_B}; a QUAD4 plan: one double)
     const double *w_slot = nullptr;
+    // the J2 elastoplastic tangent (tri3_j2.hip): the state handle (material, committed state, element ids: read by the
+    // linearisation launch only) and the tangent records [n_tiles][5][elem_stride] it writes and the apply launches read
+    const hfem_j2 *j2 = nullptr;
+    double *j2_tan = nullptr;
 };
 // q = K p, or q = A p where A.shifted (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
@@ -361,5 +367,11 @@ void launch_quad4_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *p
                                unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_tri3_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 void launch_quad4_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
+// The J2 elastoplastic tangent (tri3_j2.hip; A.j2 and A.j2_tan bound; the one-element-per-slot TRI3 plan): q = K_T p from the
+// stored records, and the linearisation at A.u_lin_free -- records, blocks and info[2] = {plastic count, 0} (work: n_tiles
+// doubles; info may be NULL)
+void launch_tri3_j2_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
+                          unsigned *ticket, double *st, double *host, double *pq_out);
+void launch_tri3_j2_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
 
 }  // namespace hfem

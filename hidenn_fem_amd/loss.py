@@ -446,7 +446,12 @@ class Quad4NeoHookeanLoss2D(NeoHookeanLoss2D):
 
 def require_linear(loss_fn, who: str):
     """The linear tools (frozen-mesh solve, stiffness assembly, stress recovery) refuse a finite-strain loss: they would
-    silently work on its linearisation."""
+    silently work on its linearisation.  Likewise a ``J2PlasticityLoss2D`` (``hidenn_fem_amd.plasticity``): its potential is
+    incremental and has a history."""
+    if getattr(loss_fn, "elastoplastic", False):
+        raise NotImplementedError(f"{who}: small-strain linear elasticity only; a J2PlasticityLoss2D has a yield limit and a "
+                                  "history -- its load path is hidenn_fem_amd.plasticity.ElastoplasticSolver / "
+                                  "elastoplastic_solve_; or pass an EnergyLoss2D")
     if isinstance(loss_fn, NeoHookeanLoss2D):
         raise NotImplementedError(f"{who}: small-strain linear elasticity only; a NeoHookeanLoss2D would be linearised "
                                   "silently -- its equilibrium is hidenn_fem_amd.newton.NewtonKrylovSolver / newton_solve_ "

@@ -340,6 +340,10 @@ class _RAdaptBase:
     @classmethod
     def _check(cls, model, loss_fn):
         cls._mesh_cls.require(model, cls.__name__)
+        if getattr(loss_fn, "elastoplastic", False):
+            raise NotImplementedError(f"{cls.__name__}: small-strain linear elasticity only; a J2PlasticityLoss2D has a history "
+                                      "on the mesh it was loaded on -- no r-adaptation under plasticity; its load path is "
+                                      "hidenn_fem_amd.plasticity.ElastoplasticSolver")
         if isinstance(loss_fn, NeoHookeanLoss2D):
             raise NotImplementedError(f"{cls.__name__}: small-strain linear elasticity only (its frozen-mesh solve would "
                                       "linearise a NeoHookeanLoss2D silently); finite strain: HyperRAdaptiveSolver (TRI3) / "

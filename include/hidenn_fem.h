@@ -1193,6 +1193,48 @@ int hfem_topt_oc(hfem_topt *topt, const double *rho, const double *dc, const dou
                  int32_t n_bisect, double *rho_new, double *rho_f_new, void *stream);
 int hfem_topt_status(hfem_topt *topt, double *status_host, void *stream);
 
+/* ------------------------------------------------------------------ small-strain J2 elastoplasticity, TRI3, plane strain
+ * (csrc/tri3_j2.hip, csrc/hfem_j2_dev.h, csrc/cg.hip; hidenn_fem_amd/plasticity.py).  No reference counterpart.
+ * Rate-independent J2 plasticity with linear isotropic hardening: the closed-form radial return per element (TRI3 has one
+ * state point) against a COMMITTED state, the incremental potential Pi whose gradient is the internal force, and the
+ * consistent tangent as the PCG driver's J2 operator kind.  Physical gradient convention.  State per element, fp64:
+ * {eps^p_xx, eps^p_yy, eps^p_xy (tensor components), alpha}; stress {s_xx, s_yy, s_xy, s_zz}; both by global element id (the
+ * row order of the connectivity the plan was created from).
+ *   hfem_j2_create    plan: a TRI3 plan with one element per slot (plan_elem_order 3: hfem_tri3_hyper_energy_plan's), on a
+ *                     device; its elem_gid is uploaded.  mat = {mu, kappa, sigma_y, H} (mu, kappa, sigma_y > 0, H >= 0),
+ *                     W the sum of the triangle weights.  Committed, trial and stress arrays start at zero (virgin).
+ *   hfem_j2_slots     doubles of a tangent-record buffer of this plan: 5 x n_tiles x elem_stride; < 0 on NULL.
+ *   hfem_j2_update    one element launch + a one-block reduction at u_free (fp64 rows; u_fixed: the Dirichlet rows):
+ *                       out[3] = {Pi, plastic home elements, max dgamma},  g_out = dPi/du_free (every free row the plan owns),
+ *                       Pi = sum_e A_e Psi_e + load g_ext . u_free,  g = A_e B^T sigma + load g_ext
+ *                     g_ext (device, free rows; may be NULL: no external load): the gradient of the linear energy at u = 0 with
+ *                     zero Dirichlet values, formed once by the caller; it is not recomputed here.  The committed state is
+ *                     read by element id and never written.  write_state = 1: home slots also store the trial state and the
+ *                     stress by element id.
+ *   hfem_j2_commit    trial -> committed (a device copy).
+ *   hfem_j2_get       out[ne][4] (device) = the committed (which = 0) or trial (1) state or the stress (2).
+ *   hfem_j2_set       committed = trial = state[ne][4] (device); NULL: the virgin state.  The stress array is zeroed.
+ *   hfem_cg_setup_j2  binds the J2 tangent on a solver of hfem_cg_create_hyper (TRI3 plan, the plan j2 was created on): the
+ *                     linearisation launch runs the return map at u_lin_free against the committed state and writes one
+ *                     tangent record {theta, theta_bar, n_xx, n_yy, n_xy} per slot into tan (hfem_j2_slots doubles, planes
+ *                     [n_tiles][5][elem_stride]), the 2x2 diagonal blocks (diag_out may be NULL) and info_out[2] = {plastic
+ *                     home elements, 0} (may be NULL).  tan is bound as a POINTER: another call re-linearises into the same
+ *                     buffer and a captured hfem_cg_iterate stays valid, as after hfem_cg_setup_hyper.  hfem_cg_start / iterate /
+ *                     status / apply / start_amg / iterate_amg then work on K_T unchanged; the apply reads x rows, p rows and
+ *                     the records only.  A later hfem_cg_setup_hyper returns the solver to the Neo-Hookean tangent.
+ * Every entry point checks its arguments before it touches a device (negative code, message through hfem_last_error).       */
+typedef struct hfem_j2 hfem_j2;
+int hfem_j2_create(hfem_plan *plan, int64_t ne, const double mat[4], double W, hfem_j2 **out);
+int hfem_j2_destroy(hfem_j2 *j2);
+int64_t hfem_j2_slots(const hfem_j2 *j2);
+int hfem_j2_update(hfem_j2 *j2, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
+                   const double *g_ext, double load, int32_t write_state, double *out, double *g_out, void *stream);
+int hfem_j2_commit(hfem_j2 *j2, void *stream);
+int hfem_j2_get(hfem_j2 *j2, int32_t which, double *out, void *stream);
+int hfem_j2_set(hfem_j2 *j2, const double *state, void *stream);
+int hfem_cg_setup_j2(hfem_cg *cg, hfem_j2 *j2, const double *x_free, const double *x_fixed, const double *u_lin_free,
+                     const double *u_fixed, double *tan, int32_t precond, double *diag_out, double *info_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
