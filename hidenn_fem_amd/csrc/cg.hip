@@ -3,10 +3,10 @@
 // element: q = K p and the block-Jacobi blocks come from the element kernels of tri3_cg.hip (paired TRI3 plan), quad4_cg.hip
 // (the model's own QUAD4 plan), tri3_hyper_cg.hip or quad4_hyper_cg.hip (the Neo-Hookean tangent at a linearisation point,
 // on the one-element-per-slot TRI3 plan or the model's own QUAD4 plan: the inner solve of hidenn_fem_amd/newton.py), chosen in
-// cg_apply and cg_diag.  The element-scaled operator K(w) = sum_e w_e K_e (after hfem_cg_setup_scaled) is a fifth kind: the
-// sibling kernels of topopt.hip on the plain kernels' plans.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
-// hidenn_fem_amd/dynamics.py) is no element kind of its own: it is the MASS instance of the kernels of tri3_cg.hip and
-// quad4_cg.hip, picked by their launchers; likewise c_K K_T + c_M M of a finite-strain step (after
+// cg_apply and cg_diag.  The shifted operator c_K K + c_M M of a Newmark step (after hfem_cg_setup_shifted:
+// hidenn_fem_amd/dynamics.py) and the element-scaled operator K(w) = sum_e w_e K_e (after hfem_cg_setup_scaled) are no element
+// kinds of their own: they are the Mass and the Scaled instance of the kernels of tri3_cg.hip and quad4_cg.hip, picked by
+// their launchers from the bound shifted flag and w_slot; likewise c_K K_T + c_M M of a finite-strain step (after
 // hfem_cg_setup_hyper_shifted) is the MASS instance of the tangent kernels.  The residual r = -dE/du comes from the graded energy kernel, called by the host
 // once per solve.
 //   cg_vec_kernel   u += alpha p, r -= alpha q, z = D^-1 r, partials of r^T z and r^T r; the last workgroup sums them in block
@@ -183,13 +183,13 @@ struct hfem_cg {
     // bound by hfem_cg_setup
     const double2 *x_free = nullptr, *x_fixed = nullptr;
     hfem::Tri3Consts k{};
-    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; the MASS instances of tri3_cg.hip / quad4_cg.hip), or
+    // bound by hfem_cg_setup_shifted: A = c_K K + c_M M (k carries c_K; the Mass instances of tri3_cg.hip / quad4_cg.hip), or
     // by hfem_cg_setup_hyper_shifted: A = c_K K_T + c_M M (hk's lambda and mu carry c_K; the MASS instances of
     // tri3_hyper_cg.hip / quad4_hyper_cg.hip)
     bool shifted = false;
     hfem::DynMass dm{};
-    // bound by hfem_cg_setup_scaled: K(w) = sum_e w_e K_e, one weight record per slot of the plan (the kernels of topopt.hip)
-    bool scaled = false;
+    // bound by hfem_cg_setup_scaled (non-null: the Scaled instances of tri3_cg.hip / quad4_cg.hip): K(w) = sum_e w_e K_e, one
+    // weight record per slot of the plan.  Never together with shifted: each setup entry point clears what it does not bind
     const double *w_slot = nullptr;
     // bound by hfem_cg_setup_hyper
     const double2 *u_lin = nullptr, *u_fixed = nullptr;
@@ -221,8 +221,6 @@ void cg_apply(const hfem_cg *c, const double2 *z, double2 *q, unsigned *ticket, 
     if (c->j2) hfem::launch_tri3_j2_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
-    else if (c->scaled && c->quad) hfem::launch_quad4_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
-    else if (c->scaled) hfem::launch_tri3_scaled_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else if (c->quad) hfem::launch_quad4_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
     else hfem::launch_tri3_cg_apply(A, z, c->p[0], c->p[1], q, c->tile_part, ticket, st, host, pq_out);
 }
@@ -232,8 +230,6 @@ void cg_diag(const hfem_cg *c, double *diag, int precond, double *info, hipStrea
     if (c->j2) hfem::launch_tri3_j2_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper && c->quad) hfem::launch_quad4_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
     else if (c->hyper) hfem::launch_tri3_hyper_cg_diag(A, diag, c->dinv, precond, c->work, info);
-    else if (c->scaled && c->quad) hfem::launch_quad4_scaled_diag(A, diag, c->dinv, precond);
-    else if (c->scaled) hfem::launch_tri3_scaled_diag(A, diag, c->dinv, precond);
     else if (c->quad) hfem::launch_quad4_cg_diag(A, diag, c->dinv, precond);
     else hfem::launch_tri3_cg_diag(A, diag, c->dinv, precond);
 }
@@ -410,7 +406,7 @@ extern "C" int hfem_cg_setup(hfem_cg *c, const double *x_free, const double *x_f
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);   // QUAD4: the 2x2 rule's weights are 1 (hfem_quad4_energy_plan_ex)
     c->shifted = false; c->dm = hfem::DynMass{};
-    c->scaled = false; c->w_slot = nullptr;
+    c->w_slot = nullptr;
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup")) return rc;
     c->ready = true;
@@ -434,7 +430,7 @@ extern "C" int hfem_cg_setup_scaled(hfem_cg *c, const double *x_free, const doub
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr);
     c->shifted = false; c->dm = hfem::DynMass{};
-    c->scaled = true; c->w_slot = w_slot;
+    c->w_slot = w_slot;
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup_scaled")) return rc;
     c->ready = true;
@@ -458,7 +454,7 @@ extern "C" int hfem_cg_setup_shifted(hfem_cg *c, const double *x_free, const dou
     c->x_free = (const double2 *)x_free; c->x_fixed = (const double2 *)x_fixed;
     c->k = hfem::scaled_consts(hfem::make_consts(mat, c->quad ? 1.0 : W, nullptr), c_k);
     c->shifted = true; c->dm = hfem::dyn_mass(c->quad, c_m, lumped != 0);
-    c->scaled = false; c->w_slot = nullptr;
+    c->w_slot = nullptr;
     cg_diag(c, diag_out, precond, nullptr, s);
     if (int rc = hfem::launch_status("hfem_cg_setup_shifted")) return rc;
     c->ready = true;

@@ -3,7 +3,7 @@
 //   A u^ = b^,   A = z_K K + z_M M,   z_K = 1 + i (w beta_R + eta),   z_M = rho (-w^2 + i w alpha_R)
 // A is complex SYMMETRIC (not Hermitian) and its real part is indefinite above the first resonance, so neither the shifted
 // operator of cg.hip (coefficients >= 0) nor its PCG driver (halts on p^T A p <= 0) applies.  This file holds both new pieces:
-//   tri3_harm_apply_kernel / quad4_harm_apply_kernel   q = A p on complex vectors: siblings of the MASS instances of
+//   tri3_harm_apply_kernel / quad4_harm_apply_kernel   q = A p on complex vectors: siblings of the Mass instances of
 //                     tri3_cg.hip / quad4_cg.hip on the same tile plans, built from the same phases (hfem_cg_dev.h).  A complex
 //                     vector is an fp64 block vector [2][n_u][2]: plane 0 real, plane 1 imaginary, each in the storage order of
 //                     u_free (a plane is what hfem_amg_vcycle takes).  Coordinates and index records are read once per tile;

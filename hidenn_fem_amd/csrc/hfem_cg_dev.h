@@ -6,7 +6,8 @@
 // element, 3 or 4 corners, and the x row code.  For the shifted operator of implicit dynamics (the MASS instances of the
 // kernels of tri3_cg.hip, quad4_cg.hip, tri3_hyper_cg.hip and quad4_hyper_cg.hip and of amg_assemble_kernel, tri3_amg.hip): the
 // mass coefficients, the QUAD4 Gauss point determinants and shape values, one element's mass row, and one element's mass
-// part of an apply.  Last, the launchers of the element kernels, which the PCG
+// part of an apply.  For the five kernels that also apply the element-scaled operator K(w) (tri3_cg.hip, quad4_cg.hip,
+// amg_assemble_kernel): the operator tag ElemOp { Plain, Mass, Scaled } that replaces their MASS.  Last, the launchers of the element kernels, which the PCG
 // driver (cg.hip) calls by element kind.  What stays in the element files is what mirrors each element's energy kernel: the
 // index loads, the staging of coordinates and p, and the slot loop.
 #pragma once
@@ -207,6 +208,17 @@ __device__ __forceinline__ double with_mass(double v, double m) {
     if constexpr (MASS) return v + m;
     else return v;
 }
+// Which operator an instance of tri3_cg_apply_kernel, tri3_cg_diag_kernel, quad4_cg_apply_kernel, quad4_cg_diag_kernel or
+// amg_assemble_kernel applies: K, the shifted c_K K + c_M M, or the element-scaled K(w) = sum_e w_e K_e.  One tag,
+// so a mass-and-scaled instance cannot be written.  Mass and Scaled code sits behind if constexpr: the Plain instance gains
+// neither "+ 0.0" nor "* 1.0", and no instance reads the other's argument (DynMass dm | the weight pointer).
+enum class ElemOp { Plain, Mass, Scaled };
+// A stiffness entry times the element's weight in the Scaled instance, the entry itself otherwise
+template <ElemOp OP>
+__device__ __forceinline__ double with_weight(double v, double w) {
+    if constexpr (OP == ElemOp::Scaled) return w * v;
+    else return v;
+}
 inline Tri3Consts scaled_consts(Tri3Consts k, double c_k) {
     k.c11 *= c_k; k.c12 *= c_k; k.c22 *= c_k; k.c33 *= c_k;
     return k;
@@ -330,20 +342,28 @@ struct CgElemArgs {
     // quad4_hyper_cg.hip): hk's lambda and mu carry c_K
     bool shifted = false;
     DynMass dm{};
-    // the element-scaled operator K(w) = sum_e w_e K_e (topopt.hip): one weight record per slot of the plan, addressed as
-    // elem_pack (a paired TRI3 plan: double2 {w_A, w_B}; a QUAD4 plan: one double)
+    // non-null: the element-scaled operator K(w) = sum_e w_e K_e (the Scaled instances of tri3_cg.hip, quad4_cg.hip): one
+    // weight record per slot of the plan, addressed as elem_pack (a paired TRI3 plan: double2 {w_A, w_B}; a QUAD4 plan: one
+    // double).  Never together with shifted: every setup entry point that binds one clears the other (cg.hip)
     const double *w_slot = nullptr;
     // the J2 elastoplastic tangent (tri3_j2.hip): the state handle (material, committed state, element ids: read by the
     // linearisation launch only) and the tangent records [n_tiles][5][elem_stride] it writes and the apply launches read
     const hfem_j2 *j2 = nullptr;
     double *j2_tan = nullptr;
 };
-// q = K p, or q = A p where A.shifted (st != NULL an iteration, st == NULL the standalone apply)
+// The operator tag of a launch, where the launch macros of tri3_cg.hip and quad4_cg.hip picked MASS: LAUNCH(..., tag)
+#define HFEM_CG_OP(LAUNCH, ...)                                                                                               \
+    do {                                                                                                                      \
+        if (A.shifted) LAUNCH(__VA_ARGS__, Mass);                                                                             \
+        else if (A.w_slot) LAUNCH(__VA_ARGS__, Scaled);                                                                       \
+        else LAUNCH(__VA_ARGS__, Plain);                                                                                      \
+    } while (0)
+// q = K p, q = A p where A.shifted, q = K(w) p where A.w_slot (st != NULL an iteration, st == NULL the standalone apply)
 void launch_tri3_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                           unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
                            unsigned *ticket, double *st, double *host, double *pq_out);
-// 2x2 diagonal blocks of K (of A where A.shifted) and their inverses (store_jacobi_block)
+// 2x2 diagonal blocks of K (of A where A.shifted, of K(w) where A.w_slot) and their inverses (store_jacobi_block)
 void launch_tri3_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 void launch_quad4_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 // The Neo-Hookean tangent at A.u_lin_free (tri3_hyper_cg.hip, one-element-per-slot TRI3 plan): q = K_T p, and the blocks with
@@ -359,14 +379,6 @@ constexpr int kQuad4HyperCgBlock = 256;
 void launch_quad4_hyper_cg_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q,
                                  double *partials, unsigned *ticket, double *st, double *host, double *pq_out);
 void launch_quad4_hyper_cg_diag(const CgElemArgs &A, double *diag, double *dinv, int precond, double *work, double *info);
-// The element-scaled operator K(w) (topopt.hip; A.w_slot bound): siblings of the four plain launchers on the same tile plans
-// and the same dispatch, the same LDS sizes
-void launch_tri3_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
-                              unsigned *ticket, double *st, double *host, double *pq_out);
-void launch_quad4_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
-                               unsigned *ticket, double *st, double *host, double *pq_out);
-void launch_tri3_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
-void launch_quad4_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond);
 // The J2 elastoplastic tangent (tri3_j2.hip; A.j2 and A.j2_tan bound; the one-element-per-slot TRI3 plan): q = K_T p from the
 // stored records, and the linearisation at A.u_lin_free -- records, blocks and info[2] = {plastic count, 0} (work: n_tiles
 // doubles; info may be NULL)

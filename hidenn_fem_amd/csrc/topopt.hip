@@ -1,19 +1,9 @@
-// Element-scaled stiffness K(w) = sum_e w_e K_e, gfx950 (MI355X) (hidenn_fem_amd/solve.py set_element_scale): a
-// per-element weight through the matrix-free PCG solve -- two materials, or the SIMP interpolation of a density design.
-//   tri3_scaled_apply_kernel / quad4_scaled_apply_kernel   q = K(w) p: siblings of tri3_cg_apply_kernel / quad4_cg_apply_kernel
-//                     (tri3_cg.hip, quad4_cg.hip) on the same tile plans, the same dispatch and the same phases (hfem_cg_dev.h:
-//                     cg_iter, gather_p, store_q_p, wave_energy, apply_finish), so the fused p = z + beta p_old gather, the
-//                     ping-pong p buffers, the per-tile p^T q partial summed in tile order and the halt are the driver's.  The
-//                     one new input is w_slot: n_tiles x elem_stride weight records addressed exactly as elem_pack -- a paired
-//                     TRI3 plan: double2 {w_A, w_B}; a QUAD4 plan: one double -- loaded in the round of elem_pack /
-//                     elem_pack_hi (one coalesced read per slot row, lane t at record t) and held in registers: no extra LDS,
-//                     no index stream, no scattered gather (reading w[elem_gid[slot]] here would add both to every CG
-//                     iteration).  In the slot loop each element's gradient rows and energy are multiplied by its weight
-//                     before the in-register pair sum and the LDS atomics.  w_B is used inside the hasB branch only; the
-//                     record of a skipped or padded slot is never used (it may hold anything, NaN included).
-//   tri3_scaled_diag_kernel / quad4_scaled_diag_kernel     the 2x2 diagonal blocks of K(w) through store_jacobi_block: siblings
-//                     of the diag kernels, the element's three block entries times its weight.
-// The AMG fine level of K(w) is amg_assemble_scaled_kernel (tri3_amg.hip), by global element id.
+// Topology optimisation on the element-scaled stiffness K(w) = sum_e w_e K_e, gfx950 (MI355X) (hidenn_fem_amd/solve.py
+// set_element_scale): the design handle and its kernels.  The operator itself is no kernel of this file: q = K(w) p
+// and the diagonal blocks of K(w) are the Scaled instances of the element kernels of tri3_cg.hip / quad4_cg.hip (bound by
+// hfem_cg_setup_scaled, cg.hip), and the AMG fine level of K(w) is the Scaled instance of amg_assemble_kernel (tri3_amg.hip).
+// Of hfem_cg_dev.h this file uses the reduction pieces (put_partial, last_block, ordered_sum, block_sum) and the element
+// closed forms (tri3_element, quad4_element_u) only.
 //
 // The design handle hfem_topt holds what maps a density design onto those weights:
 //   topt_weights_kernel   w_e = e_min + rho_e^penal (1 - e_min): once by element id into w_elem, once per slot of the plan into
@@ -37,290 +27,6 @@
 
 namespace hfem {
 namespace {
-
-// ---------------------------------------------------------------- q = K(w) p, TRI3
-// st != NULL: an iteration; st == NULL: the standalone apply (tri3_cg_apply_kernel's contract).  LDS: the plain apply's.
-template <int BLOCK, int NPT, int EPT, bool PHYS>
-__global__ __launch_bounds__(BLOCK) void tri3_scaled_apply_kernel(
-    PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k,
-    const double2 *__restrict__ w_slot, double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out,
-    int cap_nodes, int cap_owned, int col_stride) {
-    if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
-    extern __shared__ double2 lds[];
-    double2 *nd_xy = lds, *nd_p = lds + cap_nodes;
-    double *acc0 = reinterpret_cast<double *>(lds + 2 * cap_nodes), *acc1 = acc0 + cap_owned;
-    double *red = acc1 + cap_owned;                         // BLOCK / 64 doubles + one flag word
-    const int tid = threadIdx.x;
-    const CgIter it = cg_iter(st, pbuf0, pbuf1);
-    const int slot = xcd_tile((int)blockIdx.x, (int)gridDim.x);
-    int2 s[NPT];
-    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
-    const TileDesc d = pd.tiles[slot];
-    uint32_t w0[EPT], w1[EPT];
-    double wa[EPT], wb[EPT];                                // the slot's weights (plain doubles: no local double2 array)
-    const size_t rec0 = (size_t)slot * pd.elem_stride;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const size_t i = rec0 + min(tid + j * col_stride, pd.elem_stride - 1);
-        w0[j] = pd.elem_pack[i];
-        w1[j] = pd.elem_pack_hi[i];
-        const double2 w = w_slot[i];
-        wa[j] = w.x; wb[j] = w.y;
-    }
-    double2 vx[NPT], vp[NPT];
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        vx[j] = s[j].x >= 0 ? x_free[s[j].x] : x_fixed[~s[j].x];
-        vp[j] = gather_p(it, z, s[j].y);
-    }
-    const int n_owned = d.n_owned;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j)
-        if (!(tid < col_stride && tid + j * col_stride < d.n_elem)) { w0[j] = kSkipBit; w1[j] = 0u; }
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < d.n_node) { nd_xy[l] = vx[j]; nd_p[l] = vp[j]; }
-        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; }
-    }
-    __syncthreads();
-    auto add_row = [&](int l, const double2 g) {
-        unsafeAtomicAdd(&acc0[l], g.x);
-        unsafeAtomicAdd(&acc1[l], g.y);
-    };
-    double e_loc = 0.0;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const uint32_t a = w0[j], b = w1[j];
-        if (!(a & kSkipBit)) {
-            const int ln = (int)(a & kLocalMask), lb = (int)((a >> kLocalBits) & kLocalMask),
-                      lc = (int)((a >> (2 * kLocalBits)) & kLocalMask);
-            const double2 Xn = nd_xy[ln], Pn = nd_p[ln], Xc = nd_xy[lc], Pc = nd_p[lc];
-            double2 sn, sc;
-            {
-                const double2 Xb = nd_xy[lb], Pb = nd_p[lb];
-                const double w = wa[j];
-                double2 gx[3], gu[3];
-                const double e = tri3_element<true, false, PHYS>(Xn, Xb, Xc, Pn, Pb, Pc, k, gx, gu);
-                if (a & kHomeBit) e_loc += w * e;
-                if (lb < n_owned) add_row(lb, make_double2(w * gu[1].x, w * gu[1].y));
-                sn = make_double2(w * gu[0].x, w * gu[0].y); sc = make_double2(w * gu[2].x, w * gu[2].y);
-            }
-            if (b & kHasBBit) {                             // B = (n, c, d): the only reader of w_B
-                const int ld = (int)(b & kLocalMask);
-                const double2 Xd = nd_xy[ld], Pd = nd_p[ld];
-                const double w = wb[j];
-                double2 gx[3], gu[3];
-                const double e = tri3_element<true, false, PHYS>(Xn, Xc, Xd, Pn, Pc, Pd, k, gx, gu);
-                if (b & kHomeBBit) e_loc += w * e;
-                if (ld < n_owned) add_row(ld, make_double2(w * gu[2].x, w * gu[2].y));
-                sn.x = __builtin_fma(w, gu[0].x, sn.x); sn.y = __builtin_fma(w, gu[0].y, sn.y);
-                sc.x = __builtin_fma(w, gu[1].x, sc.x); sc.y = __builtin_fma(w, gu[1].y, sc.y);
-            }
-            if (ln < n_owned) add_row(ln, sn);
-            if (lc < n_owned) add_row(lc, sc);
-        }
-    }
-    wave_energy(e_loc, red);
-    __syncthreads();
-    store_q_p<BLOCK>(s, n_owned, acc0, acc1, nd_p, q, it.p_new);
-    apply_finish<BLOCK>(red, partials, slot, ticket, n_tiles, st, host, pq_out);
-}
-
-// ---------------------------------------------------------------- 2x2 diagonal blocks of K(w), TRI3
-template <int BLOCK, int NPT, int EPT, bool PHYS>
-__global__ __launch_bounds__(BLOCK) void tri3_scaled_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
-                                                                 const double2 *__restrict__ x_fixed, Tri3Consts k,
-                                                                 const double2 *__restrict__ w_slot, double *__restrict__ diag,
-                                                                 double *__restrict__ dinv, int precond, int cap_nodes,
-                                                                 int cap_owned, int col_stride) {
-    extern __shared__ double2 lds[];
-    double2 *nd_xy = lds;
-    double *acc0 = reinterpret_cast<double *>(lds + cap_nodes), *acc1 = acc0 + cap_owned, *acc2 = acc1 + cap_owned;
-    const int tid = threadIdx.x;
-    const int slot = (int)blockIdx.x;
-    int2 s[NPT];
-    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
-    const TileDesc d = pd.tiles[slot];
-    const int n_owned = d.n_owned;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < d.n_node) nd_xy[l] = s[j].x >= 0 ? x_free[s[j].x] : x_fixed[~s[j].x];
-        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; }
-    }
-    __syncthreads();
-    // the three corner blocks of one element times its weight
-    auto element = [&](int l0, int l1, int l2, double w) {
-        const int ls[3] = {l0, l1, l2};
-        const double2 X[3] = {nd_xy[l0], nd_xy[l1], nd_xy[l2]};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (ls[a] >= n_owned) continue;
-            double2 gu[3], hu[3];
-            unit_columns<PHYS>(X, a, k, gu, hu);
-            unsafeAtomicAdd(&acc0[ls[a]], w * gu[a].x);
-            unsafeAtomicAdd(&acc1[ls[a]], w * (0.5 * (gu[a].y + hu[a].x)));
-            unsafeAtomicAdd(&acc2[ls[a]], w * hu[a].y);
-        }
-    };
-    for (int j = 0; j < EPT; ++j) {
-        if (!(tid < col_stride && tid + j * col_stride < d.n_elem)) continue;
-        const size_t i = (size_t)slot * pd.elem_stride + tid + j * col_stride;
-        const uint32_t a = pd.elem_pack[i], b = pd.elem_pack_hi[i];
-        if (a & kSkipBit) continue;
-        const double2 w = w_slot[i];
-        const int ln = (int)(a & kLocalMask), lb = (int)((a >> kLocalBits) & kLocalMask),
-                  lc = (int)((a >> (2 * kLocalBits)) & kLocalMask);
-        element(ln, lb, lc, w.x);
-        if (b & kHasBBit) element(ln, lc, (int)(b & kLocalMask), w.y);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < n_owned && s[j].y >= 0) store_jacobi_block(diag, dinv, s[j].y, precond, acc0[l], acc1[l], acc2[l]);
-    }
-}
-
-// ---------------------------------------------------------------- q = K(w) p, QUAD4
-// quad4_cg_apply_kernel's contract and LDS; one weight per slot.
-template <int BLOCK, int NPT, int EPT, bool PHYS>
-__global__ __launch_bounds__(BLOCK) void quad4_scaled_apply_kernel(
-    PlanDev pd, int n_tiles, const double2 *__restrict__ x_free, const double2 *__restrict__ x_fixed,
-    const double2 *__restrict__ z, double2 *pbuf0, double2 *pbuf1, double2 *__restrict__ q, Tri3Consts k,
-    const double *__restrict__ w_slot, double *__restrict__ partials, unsigned *ticket, double *st, double *host, double *pq_out,
-    int cap_nodes, int cap_owned) {
-    if (st && st[kHalted] != 0.0) return;                   // uniform over the grid: nothing is written after a halt
-    extern __shared__ double2 lds[];
-    double2 *nd_xy = lds, *nd_p = lds + cap_nodes;
-    double *acc0 = reinterpret_cast<double *>(lds + 2 * cap_nodes), *acc1 = acc0 + cap_owned;
-    double *red = acc1 + cap_owned;                         // BLOCK / 64 doubles + one flag word
-    const int tid = threadIdx.x;
-    const CgIter it = cg_iter(st, pbuf0, pbuf1);
-    const int slot = xcd_tile((int)blockIdx.x, (int)gridDim.x);
-    mem_phase_begin();                                      // prologue at raised wave priority (hfem_plan_dev.h)
-    int2 s[NPT];
-    uint32_t pk[EPT], pk3[EPT];
-    double we[EPT];
-    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
-    const size_t rec0 = (size_t)slot * pd.elem_stride;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const size_t i = rec0 + min(tid + j * BLOCK, pd.elem_stride - 1);
-        pk[j] = pd.elem_pack[i];
-        pk3[j] = pd.elem_pack_hi[i];
-        we[j] = w_slot[i];
-    }
-    const TileDesc d = pd.tiles[slot];
-    const int n_owned = d.n_owned;
-    double vxx[NPT], vxy[NPT], vpx[NPT], vpy[NPT];          // plain doubles (double2 arrays end up in scratch)
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const double2 tx = *(s[j].x >= 0 ? x_free + s[j].x : x_fixed + ~s[j].x);
-        vxx[j] = tx.x; vxy[j] = tx.y;
-        const double2 tp = gather_p(it, z, s[j].y);
-        vpx[j] = tp.x; vpy[j] = tp.y;
-    }
-#pragma unroll
-    for (int j = 0; j < EPT; ++j)
-        if (tid + j * BLOCK >= d.n_elem) { pk[j] = kSkipBit; pk3[j] = 0u; }
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < d.n_node) { nd_xy[l] = make_double2(vxx[j], vxy[j]); nd_p[l] = make_double2(vpx[j], vpy[j]); }
-        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; }
-    }
-    __syncthreads();
-    mem_phase_end();
-    double e_loc = 0.0;
-#pragma unroll
-    for (int jj = 0; jj < EPT; ++jj) {
-        const uint32_t p = pk[jj];
-        if (!(p & kSkipBit)) {
-            const int l[4] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask),
-                              (int)((p >> (2 * kLocalBits)) & kLocalMask), (int)(pk3[jj] & kLocalMask)};
-            const double w = we[jj];
-            double2 Xn[4], Pn[4], gu[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Xn[j] = nd_xy[l[j]];
-                Pn[j] = nd_p[l[j]];
-            }
-            const double e = quad4_element_u<PHYS>(Xn, Pn, k, gu);
-            if (p & kHomeBit) e_loc += w * e;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (l[j] < n_owned) {
-                    unsafeAtomicAdd(&acc0[l[j]], w * gu[j].x);
-                    unsafeAtomicAdd(&acc1[l[j]], w * gu[j].y);
-                }
-        }
-    }
-    wave_energy(e_loc, red);
-    __syncthreads();
-    store_q_p<BLOCK>(s, n_owned, acc0, acc1, nd_p, q, it.p_new);
-    apply_finish<BLOCK>(red, partials, slot, ticket, n_tiles, st, host, pq_out);
-}
-
-// ---------------------------------------------------------------- 2x2 diagonal blocks of K(w), QUAD4
-template <int BLOCK, int NPT, int EPT, bool PHYS>
-__global__ __launch_bounds__(BLOCK) void quad4_scaled_diag_kernel(PlanDev pd, const double2 *__restrict__ x_free,
-                                                                  const double2 *__restrict__ x_fixed, Tri3Consts k,
-                                                                  const double *__restrict__ w_slot, double *__restrict__ diag,
-                                                                  double *__restrict__ dinv, int precond, int cap_nodes,
-                                                                  int cap_owned) {
-    extern __shared__ double2 lds[];
-    double2 *nd_xy = lds;
-    double *acc0 = reinterpret_cast<double *>(lds + cap_nodes), *acc1 = acc0 + cap_owned, *acc2 = acc1 + cap_owned;
-    const int tid = threadIdx.x;
-    const int slot = (int)blockIdx.x;
-    int2 s[NPT];
-    const int2 *src = pd.node_src + (size_t)slot * pd.node_stride;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) s[j] = src[min(tid + j * BLOCK, pd.node_stride - 1)];
-    const TileDesc d = pd.tiles[slot];
-    const int n_owned = d.n_owned;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < d.n_node) nd_xy[l] = *(s[j].x >= 0 ? x_free + s[j].x : x_fixed + ~s[j].x);
-        if (l < n_owned) { acc0[l] = 0.0; acc1[l] = 0.0; acc2[l] = 0.0; }
-    }
-    __syncthreads();
-    for (int j = 0; j < EPT; ++j) {
-        if (tid + j * BLOCK >= d.n_elem) continue;
-        const size_t i = (size_t)slot * pd.elem_stride + tid + j * BLOCK;
-        const uint32_t p = pd.elem_pack[i];
-        if (p & kSkipBit) continue;
-        const double w = w_slot[i];
-        const int l[4] = {(int)(p & kLocalMask), (int)((p >> kLocalBits) & kLocalMask),
-                          (int)((p >> (2 * kLocalBits)) & kLocalMask), (int)(pd.elem_pack_hi[i] & kLocalMask)};
-        const double2 Xn[4] = {nd_xy[l[0]], nd_xy[l[1]], nd_xy[l[2]], nd_xy[l[3]]};
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            if (l[a] >= n_owned) continue;
-            double2 gu[4], hu[4];
-            unit_columns<PHYS>(Xn, a, k, gu, hu);
-            unsafeAtomicAdd(&acc0[l[a]], w * gu[a].x);
-            unsafeAtomicAdd(&acc1[l[a]], w * (0.5 * (gu[a].y + hu[a].x)));
-            unsafeAtomicAdd(&acc2[l[a]], w * hu[a].y);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) {
-        const int l = tid + j * BLOCK;
-        if (l < n_owned && s[j].y >= 0) store_jacobi_block(diag, dinv, s[j].y, precond, acc0[l], acc1[l], acc2[l]);
-    }
-}
 
 // ---------------------------------------------------------------- the design handle's kernels
 constexpr int kToptBlock = 256;
@@ -582,81 +288,6 @@ __global__ __launch_bounds__(kToptBlock) void topt_oc_final_kernel(int64_t ne, c
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------- launchers of the scaled element kernels
-// launch_tri3_cg_apply's dispatch (seven tile shapes x two conventions) and launch_tri3_cg_diag's.
-void launch_tri3_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
-                              unsigned *ticket, double *st, double *host, double *pq_out) {
-    const HostPlan &h = A.plan->host;
-    const PlanDev pd = plan_dev(A.plan);
-#define HFEM_SC_APPLY(BLOCK, NPT, EPT, PH)                                                                                    \
-    hipLaunchKernelGGL((tri3_scaled_apply_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd,         \
-                       A.n_tiles, A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, (const double2 *)A.w_slot, partials, ticket,  \
-                       st, host, pq_out, h.max_nodes, h.max_owned, h.col_stride)
-#define HFEM_SC_A(BLOCK, NPT, EPT)                                                                                            \
-    do {                                                                                                                      \
-        if (A.phys) HFEM_SC_APPLY(BLOCK, NPT, EPT, true);                                                                     \
-        else HFEM_SC_APPLY(BLOCK, NPT, EPT, false);                                                                           \
-    } while (0)
-    if (A.block == 512) HFEM_SC_A(512, 2, 2);
-    else if (h.max_nodes <= 3 * 256) {
-        if (h.max_rows <= 3) HFEM_SC_A(256, 3, 3);
-        else if (h.max_rows == 4) HFEM_SC_A(256, 3, 4);
-        else HFEM_SC_A(256, 3, 6);
-    } else {
-        if (h.max_rows <= 3) HFEM_SC_A(256, 4, 3);
-        else if (h.max_rows == 4) HFEM_SC_A(256, 4, 4);
-        else HFEM_SC_A(256, 4, 6);
-    }
-#undef HFEM_SC_A
-#undef HFEM_SC_APPLY
-}
-
-void launch_tri3_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
-    const HostPlan &h = A.plan->host;
-    const PlanDev pd = plan_dev(A.plan);
-#define HFEM_SC_DIAG(BLOCK, NPT, EPT, PH)                                                                                     \
-    hipLaunchKernelGGL((tri3_scaled_diag_kernel<BLOCK, NPT, EPT, PH>), dim3(A.n_tiles), dim3(BLOCK), A.lds, A.s, pd, A.x_free, \
-                       A.x_fixed, A.k, (const double2 *)A.w_slot, diag, dinv, precond, h.max_nodes, h.max_owned, h.col_stride)
-    if (A.block == 512) {
-        if (A.phys) HFEM_SC_DIAG(512, 2, 2, true);
-        else HFEM_SC_DIAG(512, 2, 2, false);
-    } else {
-        if (A.phys) HFEM_SC_DIAG(256, 4, 6, true);
-        else HFEM_SC_DIAG(256, 4, 6, false);
-    }
-#undef HFEM_SC_DIAG
-}
-
-void launch_quad4_scaled_apply(const CgElemArgs &A, const double2 *z, double2 *pbuf0, double2 *pbuf1, double2 *q, double *partials,
-                               unsigned *ticket, double *st, double *host, double *pq_out) {
-    const HostPlan &h = A.plan->host;
-    const PlanDev pd = plan_dev(A.plan);
-#define HFEM_Q4SC_APPLY(NPT, EPT, PH)                                                                                        \
-    hipLaunchKernelGGL((quad4_scaled_apply_kernel<256, NPT, EPT, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.n_tiles, \
-                       A.x_free, A.x_fixed, z, pbuf0, pbuf1, q, A.k, A.w_slot, partials, ticket, st, host, pq_out,            \
-                       h.max_nodes, h.max_owned)
-    if (h.max_nodes <= 3 * 256 && h.max_elems <= 3 * 256) {
-        if (A.phys) HFEM_Q4SC_APPLY(3, 3, true);
-        else HFEM_Q4SC_APPLY(3, 3, false);
-    } else {
-        if (A.phys) HFEM_Q4SC_APPLY(4, 4, true);
-        else HFEM_Q4SC_APPLY(4, 4, false);
-    }
-#undef HFEM_Q4SC_APPLY
-}
-
-void launch_quad4_scaled_diag(const CgElemArgs &A, double *diag, double *dinv, int precond) {
-    const HostPlan &h = A.plan->host;
-    const PlanDev pd = plan_dev(A.plan);
-#define HFEM_Q4SC_DIAG(PH)                                                                                                   \
-    hipLaunchKernelGGL((quad4_scaled_diag_kernel<256, 4, 4, PH>), dim3(A.n_tiles), dim3(256), A.lds, A.s, pd, A.x_free,       \
-                       A.x_fixed, A.k, A.w_slot, diag, dinv, precond, h.max_nodes, h.max_owned)
-    if (A.phys) HFEM_Q4SC_DIAG(true);
-    else HFEM_Q4SC_DIAG(false);
-#undef HFEM_Q4SC_DIAG
-}
-
 }  // namespace hfem
 
 // ---------------------------------------------------------------- the design handle

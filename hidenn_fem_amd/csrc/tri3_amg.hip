@@ -23,7 +23,8 @@
 //                         operator hfem_cg_apply applies on a hyper handle.  No atomics: bit-deterministic.
 //   amg_ns0_kernel        with u_free: the rotation column at the deformed position, (-(y + v), x + u).
 // Shifted setup (hfem_amg_setup_shifted, a Newmark step of implicit dynamics): the same numeric setup on
-// A_ff = c_K K_ff + c_M M_ff, assembled by the MASS instance of amg_assemble_kernel.
+// A_ff = c_K K_ff + c_M M_ff, assembled by the Mass instance of amg_assemble_kernel.  Scaled setup (hfem_amg_setup_scaled;
+// DESIGN 30): the same on K(w)_ff = sum_e w_e K_e,ff, assembled by its Scaled instance.
 // Everything from setup_level down is shared.  One handle may be set up by either entry point, in any order: pointers and
 // patterns never change, only values do, so a captured hfem_cg_iterate_amg graph stays valid across re-setups of either kind.
 // V-cycle (amg_cycle): Chebyshev degree 2 on D^-1 A over [lambda_hat / 30, lambda_hat], the same polynomial before and after
@@ -62,9 +63,11 @@ __device__ __forceinline__ int32_t find_slot(const int32_t *__restrict__ col, in
 }
 
 // ---------------------------------------------------------------- assembly (fine level, 2x2 blocks)
-// MASS: A_ff = c_K K_ff + c_M M_ff (implicit dynamics): the same walk, k scaled by c_K on the host, plus the
-// corner's mass row (dyn_mass_row, hfem_cg_dev.h) on xx and yy of every block.  MASS = false does not read dm.
-template <int NPE, bool PHYS, bool MASS>
+// Mass: A_ff = c_K K_ff + c_M M_ff (implicit dynamics): the same walk, k scaled by c_K on the host, plus the
+// corner's mass row (dyn_mass_row, hfem_cg_dev.h) on xx and yy of every block.  Scaled: K(w)_ff = sum_e w_e K_e,ff (a design
+// iteration or a multi-material solve): the same walk, the element's four block entries times its weight, read by
+// global element id from w_elem.  Only the Mass instance reads dm, only the Scaled one w_elem.
+template <int NPE, bool PHYS, ElemOp OP>
 __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
                                                               const int32_t *__restrict__ fan_elem,
                                                               const int32_t *__restrict__ fan_corner,
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
                                                               const double2 *__restrict__ x_free,
                                                               const double2 *__restrict__ x_fixed,
                                                               const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
-                                                              Tri3Consts k, DynMass dm) {
+                                                              Tri3Consts k, DynMass dm, const double *__restrict__ w_elem) {
     const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (r >= n) return;
     for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
@@ -81,21 +84,27 @@ __global__ __launch_bounds__(kBlock) void amg_assemble_kernel(int32_t n, const i
     for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
         const int32_t e = fan_elem[f], a = fan_corner[f];
         const int32_t *cx = conn_x + NPE * (size_t)e;
+        double w = 0.0;                                        // the element's weight (Scaled only)
+        if constexpr (OP == ElemOp::Scaled) w = w_elem[e];
         double2 X[NPE], gu[NPE], hu[NPE];
-        double mrow[NPE];                                      // M_e[a][.] (MASS only)
+        double mrow[NPE];                                      // M_e[a][.] (Mass only)
 #pragma unroll
         for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
         unit_columns<PHYS>(X, a, k, gu, hu);                   // column (a, x) and (a, y) of K_e = rows (a, x) and (a, y)
-        if constexpr (MASS) dyn_mass_row(X, a, dm, mrow);
+        if constexpr (OP == ElemOp::Mass) dyn_mass_row(X, a, dm, mrow);
 #pragma unroll
         for (int b = 0; b < NPE; ++b) {
             const int32_t s = fan_slot[NPE * (size_t)f + b];
             if (s < 0) continue;
             double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
             double4 v = *p;
-            double xx = gu[b].x, yy = hu[b].y;
-            if constexpr (MASS) { xx += mrow[b]; yy += mrow[b]; }   // never "+ 0.0" in the plain instance
-            v.x += xx; v.y += gu[b].y; v.z += hu[b].x; v.w += yy;
+            if constexpr (OP == ElemOp::Scaled) {
+                v.x += w * gu[b].x; v.y += w * gu[b].y; v.z += w * hu[b].x; v.w += w * hu[b].y;
+            } else {
+                double xx = gu[b].x, yy = hu[b].y;
+                if constexpr (OP == ElemOp::Mass) { xx += mrow[b]; yy += mrow[b]; }   // never "+ 0.0" in the plain instance
+                v.x += xx; v.y += gu[b].y; v.z += hu[b].x; v.w += yy;
+            }
             *p = v;
         }
     }
@@ -579,44 +588,6 @@ __global__ __launch_bounds__(kBlock) void amg_coarse_gemv_kernel(int32_t N, cons
 
 inline dim3 grid_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
 
-// K(w)_ff = sum_e w_e K_e,ff (hfem_amg_assemble_scaled): amg_assemble_kernel's walk with the element's weight,
-// read by global element id, multiplied into its four block entries.  One thread per row, no atomics: bit-reproducible.
-// The scaled setup (hfem_amg_setup_scaled: a design iteration or a multi-material solve) is the numeric setup above on these
-// values.  Defined behind the file's last kernel: the compiler's resource reports name source lines, and no kernel above moves.
-template <int NPE, bool PHYS>
-__global__ __launch_bounds__(kBlock) void amg_assemble_scaled_kernel(int32_t n, const int32_t *__restrict__ fan_ptr,
-                                                                     const int32_t *__restrict__ fan_elem,
-                                                                     const int32_t *__restrict__ fan_corner,
-                                                                     const int32_t *__restrict__ fan_slot,
-                                                                     const int32_t *__restrict__ conn_x,
-                                                                     const double2 *__restrict__ x_free,
-                                                                     const double2 *__restrict__ x_fixed,
-                                                                     const int32_t *__restrict__ a_ptr, double *__restrict__ a_val,
-                                                                     Tri3Consts k, const double *__restrict__ w_elem) {
-    const int32_t r = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
-    if (r >= n) return;
-    for (int32_t s = a_ptr[r]; s < a_ptr[r + 1]; ++s)
-        *reinterpret_cast<double4 *>(a_val + 4 * (size_t)s) = make_double4(0.0, 0.0, 0.0, 0.0);
-    for (int32_t f = fan_ptr[r]; f < fan_ptr[r + 1]; ++f) {
-        const int32_t e = fan_elem[f], a = fan_corner[f];
-        const int32_t *cx = conn_x + NPE * (size_t)e;
-        const double w = w_elem[e];
-        double2 X[NPE], gu[NPE], hu[NPE];
-#pragma unroll
-        for (int b = 0; b < NPE; ++b) X[b] = x_row(x_free, x_fixed, cx[b]);
-        unit_columns<PHYS>(X, a, k, gu, hu);
-#pragma unroll
-        for (int b = 0; b < NPE; ++b) {
-            const int32_t s = fan_slot[NPE * (size_t)f + b];
-            if (s < 0) continue;
-            double4 *p = reinterpret_cast<double4 *>(a_val + 4 * (size_t)s);
-            double4 v = *p;
-            v.x += w * gu[b].x; v.y += w * gu[b].y; v.z += w * hu[b].x; v.w += w * hu[b].y;
-            *p = v;
-        }
-    }
-}
-
 }  // namespace
 }  // namespace hfem
 
@@ -743,9 +714,10 @@ struct Shift {
     bool lumped;
 };
 
-// sh == nullptr: K_ff; otherwise the shifted operator, the MASS instance of the same kernel
+// sh: the shifted operator, the Mass instance; w_elem (device, one weight per element by global id): K(w)_ff, the Scaled
+// instance; neither: K_ff.  Never both (no entry point passes both).
 void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, const Shift *sh,
-              hipStream_t s) {
+              const double *w_elem, hipStream_t s) {
     const DevLevel &L = a->lv[0];
     const bool quad = a->npe == 4;
     hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);        // QUAD4: the 2x2 rule's weights are 1, W is not read
@@ -754,38 +726,22 @@ void assemble(hfem_amg *a, const double *x_free, const double *x_fixed, const do
         k = hfem::scaled_consts(k, sh->c_k);
         dm = hfem::dyn_mass(quad, sh->c_m, sh->lumped);
     }
-#define HFEM_AMG_ASM(NPE, PH, MASS)                                                                                           \
-    hipLaunchKernelGGL((hfem::amg_assemble_kernel<NPE, PH, MASS>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,         \
-                       a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed,  \
-                       L.a_ptr, L.a_val, k, dm)
-#define HFEM_AMG_A(NPE)                                                                                                       \
+#define HFEM_AMG_ASM(NPE, PH, OP)                                                                                             \
+    hipLaunchKernelGGL((hfem::amg_assemble_kernel<NPE, PH, hfem::ElemOp::OP>), grid_of(L.n), dim3(kBlock), 0, s, L.n,         \
+                       a->fan_ptr, a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free,               \
+                       (const double2 *)x_fixed, L.a_ptr, L.a_val, k, dm, w_elem)
+#define HFEM_AMG_P(NPE, PH)                                                                                                   \
     do {                                                                                                                      \
-        if (a->phys && sh) HFEM_AMG_ASM(NPE, true, true);                                                                     \
-        else if (a->phys) HFEM_AMG_ASM(NPE, true, false);                                                                     \
-        else if (sh) HFEM_AMG_ASM(NPE, false, true);                                                                          \
-        else HFEM_AMG_ASM(NPE, false, false);                                                                                 \
+        if (sh) HFEM_AMG_ASM(NPE, PH, Mass);                                                                                  \
+        else if (w_elem) HFEM_AMG_ASM(NPE, PH, Scaled);                                                                       \
+        else HFEM_AMG_ASM(NPE, PH, Plain);                                                                                    \
     } while (0)
-    if (quad) HFEM_AMG_A(4);
-    else HFEM_AMG_A(3);
-#undef HFEM_AMG_A
+    if (quad && a->phys) HFEM_AMG_P(4, true);
+    else if (quad) HFEM_AMG_P(4, false);
+    else if (a->phys) HFEM_AMG_P(3, true);
+    else HFEM_AMG_P(3, false);
+#undef HFEM_AMG_P
 #undef HFEM_AMG_ASM
-}
-
-// K(w)_ff: w_elem[ne] by global element id (device)
-void assemble_scaled(hfem_amg *a, const double *x_free, const double *x_fixed, const double mat[4], double W, const double *w_elem,
-                     hipStream_t s) {
-    const DevLevel &L = a->lv[0];
-    const bool quad = a->npe == 4;
-    const hfem::Tri3Consts k = consts(mat, quad ? 1.0 : W);
-#define HFEM_AMG_ASM_SCALED(NPE, PH)                                                                                          \
-    hipLaunchKernelGGL((hfem::amg_assemble_scaled_kernel<NPE, PH>), grid_of(L.n), dim3(kBlock), 0, s, L.n, a->fan_ptr,        \
-                       a->fan_elem, a->fan_corner, a->fan_slot, a->conn_x, (const double2 *)x_free, (const double2 *)x_fixed,  \
-                       L.a_ptr, L.a_val, k, w_elem)
-    if (quad && a->phys) HFEM_AMG_ASM_SCALED(4, true);
-    else if (quad) HFEM_AMG_ASM_SCALED(4, false);
-    else if (a->phys) HFEM_AMG_ASM_SCALED(3, true);
-    else HFEM_AMG_ASM_SCALED(3, false);
-#undef HFEM_AMG_ASM_SCALED
 }
 
 void assemble_hyper(hfem_amg *a, const double *x_free, const double *x_fixed, const double *u_free, const double *u_fixed,
@@ -891,7 +847,7 @@ extern "C" int hfem_amg_assemble(hfem_amg *a, const double *x_free, const double
                                  void *stream) {
     HFEM_ARG_CHECK(a && x_free && mat, "null pointer");
     if (int rc = hfem::use_device(a->device)) return rc;
-    assemble(a, x_free, x_fixed, mat, W, nullptr, (hipStream_t)stream);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, nullptr, (hipStream_t)stream);
     return hfem::launch_status("hfem_amg_assemble");
 }
 
@@ -900,7 +856,7 @@ extern "C" int hfem_amg_setup(hfem_amg *a, const double *x_free, const double *x
     HFEM_ARG_CHECK(a && x_free && mat && coarse_out, "null pointer");
     if (int rc = hfem::use_device(a->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    assemble(a, x_free, x_fixed, mat, W, nullptr, s);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, nullptr, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup");
@@ -921,7 +877,7 @@ extern "C" int hfem_amg_assemble_shifted(hfem_amg *a, const double *x_free, cons
     HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
     if (int rc = hfem::use_device(a->device)) return rc;
     const Shift sh{c_k, c_m, lumped != 0};
-    assemble(a, x_free, x_fixed, mat, W, &sh, (hipStream_t)stream);
+    assemble(a, x_free, x_fixed, mat, W, &sh, nullptr, (hipStream_t)stream);
     return hfem::launch_status("hfem_amg_assemble_shifted");
 }
 
@@ -933,7 +889,7 @@ extern "C" int hfem_amg_setup_shifted(hfem_amg *a, const double *x_free, const d
     if (int rc = hfem::use_device(a->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const Shift sh{c_k, c_m, lumped != 0};
-    assemble(a, x_free, x_fixed, mat, W, &sh, s);
+    assemble(a, x_free, x_fixed, mat, W, &sh, nullptr, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup_shifted");
@@ -946,7 +902,7 @@ extern "C" int hfem_amg_assemble_scaled(hfem_amg *a, const double *x_free, const
     HFEM_ARG_CHECK(w_elem, "w_elem must be given (one weight per element)");
     HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
     if (int rc = hfem::use_device(a->device)) return rc;
-    assemble_scaled(a, x_free, x_fixed, mat, W, w_elem, (hipStream_t)stream);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, w_elem, (hipStream_t)stream);
     return hfem::launch_status("hfem_amg_assemble_scaled");
 }
 
@@ -957,7 +913,7 @@ extern "C" int hfem_amg_setup_scaled(hfem_amg *a, const double *x_free, const do
     HFEM_ARG_CHECK(a->conn_x_fixed == 0 || x_fixed, "the mesh has fixed coordinate rows: x_fixed must be given");
     if (int rc = hfem::use_device(a->device)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    assemble_scaled(a, x_free, x_fixed, mat, W, w_elem, s);
+    assemble(a, x_free, x_fixed, mat, W, nullptr, w_elem, s);
     hipLaunchKernelGGL(hfem::amg_ns0_kernel, grid_of(a->n_u), dim3(kBlock), 0, s, a->n_u, a->row_x, (const double2 *)x_free,
                        (const double2 *)x_fixed, (const double2 *)nullptr, a->lv[0].ns);
     return setup_levels(a, coarse_out, s, "hfem_amg_setup_scaled");

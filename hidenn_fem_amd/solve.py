@@ -119,9 +119,9 @@ class _FrozenSolverBase:
         ``> 0`` (``ValueError`` otherwise).  ``None`` restores the homogeneous solve exactly: the same calls as before this
         method existed.  The values are copied; call again after changing them.
 
-        With a scale set the matrix-vector product, the block-Jacobi blocks and the AMG fine level are the scaled sibling
-        kernels (``csrc/topopt.hip``, ``amg_assemble_scaled_kernel``), and ``solve()`` forms its first residual as
-        ``g0 = g_zero + K(w) u_0`` with one standalone scaled apply instead of the energy launch at ``u_0``.  The Dirichlet
+        With a scale set the matrix-vector product, the block-Jacobi blocks and the AMG fine level are the ``Scaled``
+        instances of the plain kernels (``csrc/tri3_cg.hip`` / ``csrc/quad4_cg.hip``, ``amg_assemble_kernel``), and
+        ``solve()`` forms its first residual as ``g0 = g_zero + K(w) u_0`` with one standalone scaled apply instead of the energy launch at ``u_0``.  The Dirichlet
         lift of the homogeneous energy launch would be wrong for ``K(w)``, so a scale requires ``u_fixed == 0``
         (``ValueError`` at the next refresh otherwise).  The energy losses themselves stay homogeneous: ``loss_fn(model)`` and
         the stress recovery do not see the scale."""

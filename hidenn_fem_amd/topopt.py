@@ -5,7 +5,7 @@
 
 One design iteration (``TopologyOptimizer.step``) is, in order: the weights launch (``hfem_topt_weights``), the numeric AMG
 setup on ``K(w)`` or its 2x2 blocks (``hfem_amg_setup_scaled`` / ``hfem_cg_setup_scaled``), a warm-started PCG solve through
-the scaled sibling kernels of ``csrc/topopt.hip``, one launch for the element energies ``ce_e = u_e^T K_e u_e`` and
+the ``Scaled`` instances of the plain element kernels, one launch for the element energies ``ce_e = u_e^T K_e u_e`` and
 ``dc/drho~_e = -penal rho~_e^(penal-1) (1 - e_min) ce_e`` (``hfem_topt_energy``), the transpose filter ``dc/drho = F^T dc/drho~``
 and the optimality-criteria update with its bisection on the device (``hfem_topt_oc``: launches only; the host reads one status
 record per iteration).  The PCG driver, the AMG hierarchy (patterns and aggregates are the mesh's; only values are rebuilt) and

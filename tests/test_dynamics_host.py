@@ -42,21 +42,22 @@ def test_dynamics_symbols_are_exported_bound_and_match_the_header():
     assert "dynamics.hip" in build.SOURCES
     assert not [s for s in build.SOURCES if s.endswith("_dyn_cg.hip")]
     usage = build.resource_usage()
-    # The shifted operator is the MASS instance of the plain kernels: the last template argument (Lb0E | Lb1E in the mangled
-    # name).  One instance matrix, compiled without and with the mass: TRI3 apply (512,2,2) and (256, 3|4, 3|4|6) x PHYS, TRI3
-    # diag (512,2,2), (256,4,6) x PHYS; QUAD4 apply (256,3,3), (256,4,4) x PHYS, QUAD4 diag (256,4,4) x PHYS; assembly 3|4 x PHYS.
+    # The shifted operator is the Mass instance of the plain kernels: the last template argument is the operator tag ElemOp
+    # { Plain, Mass, Scaled } (L..6ElemOpE0E | 1E | 2E in the mangled name).  One instance matrix, compiled for each of the three:
+    # TRI3 apply (512,2,2) and (256, 3|4, 3|4|6) x PHYS, TRI3 diag (512,2,2), (256,4,6) x PHYS; QUAD4 apply (256,3,3), (256,4,4) x
+    # PHYS, QUAD4 diag (256,4,4) x PHYS; assembly 3|4 x PHYS.
     for kernel, count in (("tri3_cg_apply_kernel", 14), ("tri3_cg_diag_kernel", 4), ("quad4_cg_apply_kernel", 4),
                           ("quad4_cg_diag_kernel", 2), ("amg_assemble_kernel", 4)):
-        by_mass = {False: {}, True: {}}
+        by_op = {"0": {}, "1": {}, "2": {}}
         for name, v in usage.items():
-            m = re.search(r"\d+" + kernel + r"I((?:L[ib]\d+E)+)E", name)
+            m = re.search(r"\d+" + kernel + r"I((?:L[ib]\d+E)+)(.*?)EEv", name)   # ...E of the template list, E of the name
             if m:
-                last = re.findall(r"L([ib])(\d+)E", m.group(1))[-1]
-                assert last[0] == "b", f"{name}: the last template argument is not the bool MASS"
-                by_mass[last[1] == "1"][name] = v
-        for mass, inst in by_mass.items():
-            assert len(inst) == count, (kernel, mass, sorted(inst))
-            assert all(v["scratch"] == 0 for v in inst.values()), (kernel, mass, inst)
+                tag = re.fullmatch(r"L[^L]*6ElemOpE(\d)E", m.group(2))
+                assert tag, f"{name}: the last template argument is not the operator tag ElemOp"
+                by_op[tag.group(1)][name] = v
+        for op, inst in by_op.items():
+            assert len(inst) == count, (kernel, op, sorted(inst))
+            assert all(v["scratch"] == 0 for v in inst.values()), (kernel, op, inst)
     for kernel in ("newmark_predict_kernel", "newmark_rhs_kernel", "newmark_correct_kernel"):
         inst = {k: v for k, v in usage.items() if kernel in k}
         assert inst, kernel

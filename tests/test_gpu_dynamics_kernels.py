@@ -1,7 +1,7 @@
 """The kernels of implicit dynamics one by one: the shifted apply and its p^T A p, the 2x2 diagonal blocks and the
 assembled A of ``c_K K + c_M M`` against the reference matrix -- K from ``assemble_stiffness``, M element by element from
 tests/modal_reference.py with rho = 2, as tests/test_gpu_modal.py::dense_pencil, both held SPARSE (scipy CSR, the same entries:
-the larger shapes have 10^4 dofs).  The shifted operator is the ``MASS`` instance of the plain kernels (``tri3_cg.hip``,
+the larger shapes have 10^4 dofs).  The shifted operator is the ``Mass`` instance of the plain kernels (``tri3_cg.hip``,
 ``quad4_cg.hip``, ``amg_assemble_kernel``), picked by the plain launchers; the shapes reach every tile shape of their dispatch
 (restated here and asserted: all seven TRI3 shapes, both QUAD4 ones) with the mass, in both conventions; the three vector kernels against their formulas in ``longdouble``; the
 V-cycle of the hierarchy built on A.

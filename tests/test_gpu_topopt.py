@@ -182,7 +182,7 @@ def test_row_order_fp32_models_and_run_stops_on_tol(kind):
         out[order] = (np.array([i.compliance for i in infos]), opt.filtered_density.cpu().numpy())
     assert np.abs(out["off"][0] - out["hilbert"][0]).max() <= 1e-6 * out["off"][0].max()     # two solves at rtol 1e-8
     assert np.abs(out["off"][1] - out["hilbert"][1]).max() <= 1e-5
-    # the same on the reordered model with AMG: its fine level reads w_elem by global element id (amg_assemble_scaled_kernel)
+    # the same on the reordered model with AMG: its fine level reads w_elem by global element id (the Scaled instance of amg_assemble_kernel)
     m = _fresh(kind, reorder="hilbert")
     assert not torch.equal(m._idx_ufree.cpu(), _fresh(kind, reorder="off")._idx_ufree.cpu())     # the rows did move
     opt = TopologyOptimizer(m, lf, 0.4, e_min=1e-3, precond="amg")

@@ -170,6 +170,63 @@ def test_a_later_plain_setup_returns_the_solver_to_k_and_a_hyper_solver_is_refus
         lib.hfem_cg_destroy(h)
 
 
+@pytest.mark.parametrize("conv", CONVS)
+@pytest.mark.parametrize("kind,shape", [("tri3", "a"), ("quad4", "S600")])
+def test_one_handle_rebound_scaled_shifted_scaled_applies_what_was_bound_last(kind, shape, conv):
+    """The launchers pick the kernel instance from what the handle has bound (the shifted flag, the weight pointer), so a stale
+    binding would select the wrong operator.  One ``hfem_cg`` handle through the library calls: scaled, then shifted -- the
+    apply and the returned blocks are ``c_K K + c_M M`` with the weights ignored -- then scaled again -- ``K(w)`` with no mass.
+    References: ``topopt_reference.scaled_stiffness`` and the shifted matrix as tests/test_gpu_dynamics_kernels.py builds it
+    (K from ``assemble_stiffness``, M from its ``_mass``); 1e-12 x max as the neighbouring tests."""
+    from hidenn_fem_amd import _lib
+    from hidenn_fem_amd.solve import ElementWeights, assemble_stiffness
+    m, lf, plan, Ke, dofs, w = _case(kind, shape, conv)
+    s = _solver(m, lf)
+    assert s.plan is plan
+    s.refresh()                                              # the coordinate rows the direct calls below bind
+    n = s.n_u
+    ew = ElementWeights(plan, len(w), _dev())
+    ew.set(torch.from_numpy(w).to(_dev()))
+    p = torch.randn(n, 2, dtype=F64, generator=torch.Generator().manual_seed(11)).to(_dev())
+    pn = p.cpu().numpy().reshape(-1)
+    Kw = TR.scaled_stiffness(Ke, dofs, w, 2 * n)
+    K = DK._scipy(assemble_stiffness(m, lf))
+    c_k, c_m, lumped = 0.3, 1.7, False
+    A = (c_k * 0.5 * (K + K.T) + c_m * DK._mass(m, lumped)).tocsr()
+    lib, st = _lib.lib(), _lib.stream_ptr(_dev())
+    mat, W = (C.c_double * 4)(*lf._mat), float(lf._W)
+    xf, xfix_p = s._xf.data_ptr(), s._xfix.data_ptr() if s._xfix.numel() else None
+    blocks = torch.empty(n, 3, dtype=F64, device=_dev())
+    q = torch.empty_like(p)
+    pq = torch.empty((), dtype=F64, device=_dev())
+
+    def bind_scaled():
+        _lib.check(lib.hfem_cg_setup_scaled(s._h, xf, xfix_p, mat, W, ew.w_slot.data_ptr(), 1, blocks.data_ptr(), st),
+                   "hfem_cg_setup_scaled")
+
+    def bind_shifted():
+        _lib.check(lib.hfem_cg_setup_shifted(s._h, xf, xfix_p, mat, W, c_k, c_m * DK.RHO, int(lumped), 1, blocks.data_ptr(), st),
+                   "hfem_cg_setup_shifted")
+
+    for step, (bind, ref) in enumerate(((bind_scaled, Kw), (bind_shifted, A), (bind_scaled, Kw))):
+        blocks.fill_(float("nan"))
+        q.fill_(float("nan"))
+        bind()
+        _lib.check(lib.hfem_cg_apply(s._h, p.data_ptr(), q.data_ptr(), pq.data_ptr(), st), "hfem_cg_apply")
+        want = ref @ pn
+        d0, up, lo = ref.diagonal(0), ref.diagonal(1), ref.diagonal(-1)
+        wb = np.stack([d0[0::2], 0.5 * (up[0::2] + lo[0::2]), d0[1::2]], axis=1)
+        err = np.abs(q.cpu().numpy().reshape(-1) - want).max() / np.abs(want).max()
+        err_pq = abs(pq.item() - pn @ want) / abs(pn @ want)
+        err_b = np.abs(blocks.cpu().numpy() - wb).max() / np.abs(wb).max()
+        print(f"{kind} {shape} {conv} binding {step}: apply {err:.2e} p^T A p {err_pq:.2e} blocks {err_b:.2e}")
+        assert err <= 1e-12
+        assert err_pq <= 1e-12
+        assert err_b <= 1e-12
+    # the two operators differ by far more than the bound, so each comparison above tells them apart
+    assert np.abs((A - Kw) @ pn).max() > 1e-3 * np.abs(A @ pn).max()
+
+
 @pytest.mark.parametrize("kind,shape", ALL_SHAPES, ids=IDS)
 def test_weights_by_element_and_by_slot_match_the_formula(kind, shape):
     from hidenn_fem_amd.solve import ElementWeights

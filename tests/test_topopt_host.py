@@ -1,6 +1,7 @@
 """The host surface of element-scaled stiffness and topology optimisation, without a GPU: the new C entry points are
-exported, bound and match the header; the scaled element kernels exist as siblings in ``topopt.hip`` -- 14 + 4 apply instances
-on the plain apply's dispatch, the diag instances, none with scratch, none inside ``tri3_cg.hip`` / ``quad4_cg.hip``; argument
+exported, bound and match the header; the scaled operator is the ``ElemOp::Scaled`` instance of the plain element kernels of
+``tri3_cg.hip`` / ``quad4_cg.hip`` / ``tri3_amg.hip`` -- 14 + 4 apply instances on the plain apply's dispatch, the diag and
+assembly instances, none with scratch, no sibling kernel left -- and ``topopt.hip`` holds the design kernels only; argument
 errors come back as negative codes with a message before any device is touched; ``TopologyOptimizer`` refuses what it does not
 support; ``set_element_scale(None)`` leaves the solver's sequence of library calls as it was."""
 import ctypes as C
@@ -44,33 +45,41 @@ def test_symbols_are_exported_bound_and_match_the_header():
     assert L.lib().hfem_version() == 114
 
 
-def test_scaled_kernels_are_siblings_in_topopt_hip_without_scratch():
+def test_scaled_operator_is_the_scaled_instance_of_the_plain_kernels_without_scratch():
     _lib()
     from hidenn_fem_amd.csrc import build
     assert "topopt.hip" in build.SOURCES
     use = build.resource_usage()
-    mine = {k: v for k, v in use.items() if v["source"] == "topopt.hip"}
-    for kernel, count in (("tri3_scaled_apply_kernel", 14), ("quad4_scaled_apply_kernel", 4), ("tri3_scaled_diag_kernel", 4),
-                          ("quad4_scaled_diag_kernel", 2), ("tri3_topt_energy_kernel", 4), ("quad4_topt_energy_kernel", 2),
-                          ("topt_weights_kernel", 2), ("topt_filter_kernel", 2), ("topt_oc_init_kernel", 1),
-                          ("topt_oc_step_kernel", 2), ("topt_oc_final_kernel", 2)):
-        inst = {k: v for k, v in mine.items() if kernel in k}
+    # no sibling kernels: K(w) is the ElemOp::Scaled instance (the last template argument, value 2) of the plain kernels
+    gone = [k for k in use if "scaled_apply_kernel" in k or "scaled_diag_kernel" in k or "amg_assemble_scaled_kernel" in k]
+    assert not gone, gone
+    scaled = {k: v for k, v in use.items() if re.search(r"L[^L]*6ElemOpE2EE", k)}
+    for kernel, count, source in (("tri3_cg_apply_kernel", 14, "tri3_cg.hip"), ("quad4_cg_apply_kernel", 4, "quad4_cg.hip"),
+                                  ("tri3_cg_diag_kernel", 4, "tri3_cg.hip"), ("quad4_cg_diag_kernel", 2, "quad4_cg.hip"),
+                                  ("amg_assemble_kernel", 4, "tri3_amg.hip")):
+        inst = {k: v for k, v in scaled.items() if re.search(r"\d+" + kernel + "I", k)}
         assert len(inst) == count, (kernel, sorted(inst))
-        assert all(v["scratch"] == 0 for v in inst.values()), (kernel, inst)
+        assert all(v["scratch"] == 0 and v["source"] == source for v in inst.values()), (kernel, inst)
+    assert len(scaled) == 28, sorted(scaled)
     # the TRI3 apply instances are the plain dispatch's seven tile shapes in both conventions, the QUAD4 ones its two
-    shapes = sorted(re.search(r"tri3_scaled_apply_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", k).groups()
-                    for k in mine if "tri3_scaled_apply_kernel" in k)
+    shapes = sorted(re.search(r"tri3_cg_apply_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])EL", k).groups()
+                    for k in scaled if "tri3_cg_apply_kernel" in k)
     want = sorted((b, n, e, p) for b, n, e in (("512", "2", "2"), ("256", "3", "3"), ("256", "3", "4"), ("256", "3", "6"),
                                                 ("256", "4", "3"), ("256", "4", "4"), ("256", "4", "6")) for p in "01")
     assert shapes == want
-    q = sorted(re.search(r"quad4_scaled_apply_kernelILi256ELi(\d)ELi(\d)ELb([01])E", k).groups()
-               for k in mine if "quad4_scaled_apply_kernel" in k)
+    q = sorted(re.search(r"quad4_cg_apply_kernelILi256ELi(\d)ELi(\d)ELb([01])EL", k).groups()
+               for k in scaled if "quad4_cg_apply_kernel" in k)
     assert q == sorted((n, n, p) for n in "34" for p in "01")
-    # nothing of them outside topopt.hip, except the fine-level assembly, which lives with its plain sibling
-    out = {k: v["source"] for k, v in use.items() if ("scaled_" in k or "topt_" in k) and v["source"] != "topopt.hip"}
-    assert set(out.values()) <= {"tri3_amg.hip"} and all("amg_assemble_scaled_kernel" in k for k in out), out
-    amg = {k: v for k, v in use.items() if "amg_assemble_scaled_kernel" in k}
-    assert len(amg) == 4 and all(v["scratch"] == 0 for v in amg.values())
+    # topopt.hip holds the design handle's kernels and nothing else; none of them lives elsewhere
+    mine = {k: v for k, v in use.items() if v["source"] == "topopt.hip"}
+    for kernel, count in (("tri3_topt_energy_kernel", 4), ("quad4_topt_energy_kernel", 2), ("topt_weights_kernel", 2),
+                          ("topt_filter_kernel", 2), ("topt_oc_init_kernel", 1), ("topt_oc_step_kernel", 2),
+                          ("topt_oc_final_kernel", 2)):
+        inst = {k: v for k, v in mine.items() if kernel in k}
+        assert len(inst) == count, (kernel, sorted(inst))
+        assert all(v["scratch"] == 0 for v in inst.values()), (kernel, inst)
+    assert all("topt_" in k for k in mine), sorted(k for k in mine if "topt_" not in k)
+    assert not [k for k, v in use.items() if "topt_" in k and v["source"] != "topopt.hip"]
 
 
 def test_argument_errors_are_negative_codes_with_messages():
